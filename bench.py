@@ -5,11 +5,21 @@ Metric (BASELINE.json): Mvoxel/s of the heightmap+normals render (interval + poi
 evaluation) of prospero.vm at 1024^3, nominal volume / wall time
 (W*H*D / t / 1e6, the convention of the reference's README.md:152-156).
 
-    python bench.py --gpus N --steps K --warmup W
+    python bench.py --gpus N --steps K --warmup W [--dump-outputs DIR] [--full]
 
 One process per GPU (the driver launches N>1 through torch.distributed.run).  A step is one full frame,
 inputs resident in HBM, output left in HBM; frames are queued back to back and the library pipelines them
 (the coarse levels of frame n + 1 beside the slabs of frame n).
+
+A plain run does only what the headline needs: it sets up, warms up (W frames, then the frames the library's arrangement
+tuner takes), times the K steps and prints the line with `value` / `ms_per_step` and the contract's fields.  Everything
+else below - the general path, single-frame latencies, the host-buffer frame, per-kernel profiles and rooflines, the CPU
+baseline and parity, the other configurations, the details file; at N > 1 the other shardings and the stage model - is
+measured only under --full.
+
+--dump-outputs DIR: after the timed steps, the image the timed path computed in its last step, as a caller of render3d
+receives it: DIR/normal.npy (float32 [n, n, 3]) and DIR/depth.npy (depth as float32 [n, n], exact below 2^24); when that
+would exceed DUMP_BYTES, a fixed seeded sample of the pixels, with their flat indices in DIR/pixel_index.npy (float64).
 
 What the ONE JSON line says, and how to read it:
 
@@ -108,7 +118,13 @@ def main():
     ap.add_argument("--no-cpu", action="store_true", help="skip the cpu_baseline / parity / configuration-3 leg")
     ap.add_argument("--no-general", action="store_true", help="skip the frames with the column-invariance short cuts off (profiling runs: per-kernel statistics of the default path only)")
     ap.add_argument("--only-general", action="store_true", help="profiling runs: time only the frames with the short cuts off")
+    ap.add_argument("--full", action="store_true", help="everything beyond the headline: general path, latencies, profiles and rooflines, "
+                                                        "CPU baseline and parity, other configurations, details file (N > 1: other shardings)")
+    ap.add_argument("--dump-outputs", metavar="DIR", default=None, help="write the timed path's last image to DIR/*.npy")
     args = ap.parse_args()
+    if args.steps < 1:
+        ap.error("--steps must be at least 1")
+    full = args.full
 
     import torch
     import torch.distributed as dist
@@ -178,10 +194,12 @@ def main():
     n = args.size
     stream = torch.cuda.current_stream(dev)
     mem_info = getattr(torch.cuda, "mem_get_info", None)
-    try:        # (device memory the library takes: hipMalloc'd by the context, not by torch)
-        free_before = mem_info(dev)[0]
-    except Exception:       # noqa: BLE001
-        free_before = None
+    free_before = None
+    if full:
+        try:        # (device memory the library takes: hipMalloc'd by the context, not by torch)
+            free_before = mem_info(dev)[0]
+        except Exception:       # noqa: BLE001
+            free_before = None
     hip = F.HipContext(local, stream.cuda_stream)
     shape = F.Shape.from_vm(os.path.join(ROOT, "models", args.model), hip=hip)
     out = torch.zeros((n, n, 4), dtype=torch.int32, device=dev)  # GeometryPixel = 4 x 32-bit words
@@ -271,22 +289,24 @@ def main():
     general = None
     host_frame = None
     lat_general = None
+    lat_default = None
     if world > 1:
         # the stream of the context is torch's current stream: collectives and renders are ordered on it
         dt_b = timed(step_blocks)
         img_b, ms_b = out.clone(), list(frame_ms)
-        lat_b = latency(step_blocks)
+        lat_b = latency(step_blocks) if full else None
         dt_c = timed(step_columns)
-        ms_c = list(frame_ms)
-        lat_c = latency(step_columns)
-        partitions = {"columns": {"ms_per_step": dt_c / args.steps * 1e3, "frame_latency_ms": lat_c, "scaling": "strong",
-                                  "combine": "1 RCCL reduce (SUM) of the full image"},
-                      "blocks": {"ms_per_step": dt_b / args.steps * 1e3, "frame_latency_ms": lat_b, "scaling": "strong", "split": list(split),
+        img_c, ms_c = out.clone(), list(frame_ms)
+        lat_c = latency(step_columns) if full else None
+        partitions = {"columns": {"ms_per_step": dt_c / args.steps * 1e3, "scaling": "strong", "combine": "1 RCCL reduce (SUM) of the full image"},
+                      "blocks": {"ms_per_step": dt_b / args.steps * 1e3, "scaling": "strong", "split": list(split),
                                  "combine": "RCCL gather of each rank's rectangle + front-to-back depth merge on rank 0"}}
+        if full:
+            partitions["columns"]["frame_latency_ms"], partitions["blocks"]["frame_latency_ms"] = lat_c, lat_b
+    if world > 1 and full:
         if rank == 0:
-            partitions["images_equal"] = bool(torch.equal(img_b, out))
+            partitions["images_equal"] = bool(torch.equal(img_b, img_c))
             frames_recv = torch.zeros((world, n, n, 4), dtype=torch.int32, device=dev)
-        img_c = out.clone()
         dt_f = timed(step_frames)        # one step = `world` frames
         partitions["frames"] = {"ms_per_step": dt_f / args.steps * 1e3, "frames_per_step": world, "scaling": "weak",
                                 "combine": "none inside a frame: every rank renders whole frames of the sequence; RCCL gather of the finished frames (16 MiB each) to rank 0",
@@ -313,22 +333,25 @@ def main():
             partitions["blocks_colonnade"] = {"ms_per_step": dt_z / args.steps * 1e3, "frame_latency_ms": latency(step_blocks_z), "scaling": "strong", "split": list(split),
                                               "what": "colonnade.vm 1024^3 (reads z), octant blocks"}
         step_blocks()
+    if world > 1:
         for k, f in (("columns", 1), ("blocks", 1), ("frames", world), ("blocks_general_path", 1), ("blocks_colonnade", 1)):
             if k in partitions:
                 partitions[k]["value"] = (n ** 3) * f / (partitions[k]["ms_per_step"] * 1e-3) / 1e6
         # `value`: ONE frame sharded over the ranks - the north star's number - by the better of the two partitions
         if dt_c <= dt_b:
             dt, step, sharding, lat_default = dt_c, step_columns, "root-tile columns round-robin, 1 RCCL reduce", lat_c
-            frame_ms[:] = ms_c
+            frame_ms[:], dump_img = ms_c, img_c
         else:
             dt, step, sharding, lat_default = dt_b, step_blocks, f"blocks {split[0]}x{split[1]}x{split[2]} (octant split), RCCL gather + depth merge", lat_b
-            frame_ms[:] = ms_b
+            frame_ms[:], dump_img = ms_b, img_b
     else:
         step = step_columns
         sharding = "single GPU"
         if args.only_general:
             hip.set_option("no_column_inv", 1)
         dt = timed(step)
+        dump_img = out.clone() if args.dump_outputs else None       # (the last timed frame's image: the --full legs below render into `out` again)
+    if world == 1 and full:
         lat_default = latency(step)
         img_default = out.clone()
         if free_before is not None:       # what the context holds for the path `value` times (before the general path's frames grow the arena)
@@ -356,9 +379,10 @@ def main():
         for _ in range(2):
             F.render3d(shape, n, host_out=pinned)
         host_frame = float(np.median([F.render3d(shape, n, host_out=pinned)[2] * 1e3 for _ in range(9)]))
-    hip.sync()
-    counters = hip.counters()
-    device_bytes = None
+    counters, device_bytes = None, None
+    if full:
+        hip.sync()
+        counters = hip.counters()
     if free_before is not None:
         try:
             device_bytes = int(free_before - mem_info(dev)[0])
@@ -390,19 +414,20 @@ def main():
             hip.profile(False)
         return {"prof": prof, "kern": kern, "leaf": leaf, "tiles": tiles}
 
-    prof_default = profiled(False) if not args.only_general else None
-    prof_general = profiled(True) if (world == 1 and not args.no_general) else None
-    F.render3d(shape, n, out=out, shard=rank, n_shards=world)       # (leaves the timed path's image in `out`)
-    if world > 1:
-        step()  # leave `out` holding the combined image on rank 0
-    fence()
+    prof_default = profiled(False) if (full and not args.only_general) else None
+    prof_general = profiled(True) if (full and world == 1 and not args.no_general) else None
+    if full:
+        F.render3d(shape, n, out=out, shard=rank, n_shards=world)       # (leaves the timed path's image in `out`)
+        if world > 1:
+            step()  # leave `out` holding the combined image on rank 0
+        fence()
 
     # N > 1: what each rank's share of a frame costs, stage by stage (sums of kernel times over the rank's profiled frames, columns
     # sharding): the coarse chain - root level forward + prune, level 1 - is as LONG on every rank as on one GPU (each parent / child is
     # one wave whatever their number), the per-slab tile stage, the leaves and the normals shrink with the rank's share; a scaling curve
     # taken with this line can be read against these
     per_rank = None
-    if world > 1:
+    if world > 1 and full:
         k, pr = prof_default["kern"], prof_default["prof"]
         ms = lambda d, key: (d.get(key, (0.0, 0))[0]) / PROF_FRAMES
         coarse = sum(ms(k, x) for x in ("fh_tiles", "fh_prune1", "fh_tiles_v64"))
@@ -426,13 +451,9 @@ def main():
         "higher_is_better": True, "scaling": "strong", "vs_baseline": None,
         "dtype": "f32", "data": "synthetic",
         "tuning_frames": tuning["frames"],
-        "frame_latency_ms": lat_default,
-        "device_bytes": device_bytes, "device_bytes_timed_path": bytes_default,
         "frame_arrangement": {"untimed_frames_beyond_warmup": tuning["frames"], "per_kind": tuning["per_kind"], "last_measured": tuning["last"],
                               "note": "the library measures a run of queued frames of one kind under its stage pipeline and on its frame lanes and keeps the faster "
                                       "(DESIGN.md section 4); bench.py lets that finish before the timed frames"},
-        "general": general,
-        "host_output_frame_ms": host_frame,
         "config": {"workload": f"{args.model} 3D heightmap+normals {n}^3, HipShape render hints (the library's tiles: 128/32/8, or 32/8 when the root level has few tiles), world_to_model=I",
                    "sharding": sharding,
                    "general_path": None if not general else {"ms_per_step": general["ms_per_step"], "value": general["value"],
@@ -443,16 +464,28 @@ def main():
                    "column_invariance": ("off for every number of this line (--only-general)" if args.only_general else
                                          "prospero.vm reads no z, so `value` evaluates each tape once per pixel column (DESIGN.md section 2); "
                                          "general_path = the same frames with that short cut off, what a model with z gets")},
+    }
+    if partitions:
+        result["partitions"] = partitions
+        result["collectives"] = direct_note
+    if not full:        # a plain run: the headline and nothing else
+        emit(result, False, dump_img, args.dump_outputs)
+        if world > 1:
+            dist.destroy_process_group()
+        return
+    result.update({
+        "frame_latency_ms": lat_default,
+        "device_bytes": device_bytes, "device_bytes_timed_path": bytes_default,
+        "general": general,
+        "host_output_frame_ms": host_frame,
         "kernel_ms_per_frame": {k: v[0] / PROF_FRAMES for k, v in pmain["prof"].items()},
         "kernel_launches_per_frame": {k: v[1] // PROF_FRAMES for k, v in pmain["prof"].items()},
         "asm_kernel_ms_per_frame": {k: v[0] / PROF_FRAMES for k, v in pmain["kern"].items() if v[1]},
         "arena_ops_last_slab": counters["arena_ops"], "arena_overflow": counters["arena_overflow"],
-    }
+    })
     if prof_general and prof_default:
         result["general"]["asm_kernel_ms_per_frame"] = {k: v[0] / PROF_FRAMES for k, v in prof_general["kern"].items() if v[1]}
     if partitions:
-        result["partitions"] = partitions
-        result["collectives"] = direct_note
         result["per_rank"] = per_rank
         result["predicted"] = predict_from_stages(per_rank, n, world, partitions)
 
@@ -659,15 +692,49 @@ def main():
                 result["c5_mesh"] = c5 if c5 else {"error": f"tools/mesh_times.py 10: rc {r.returncode}", "stderr_tail": r.stderr[-400:]}
             except Exception as e:      # (a time-out included: the line's other fields do not depend on this leg)
                 result["c5_mesh"] = {"error": repr(e)}
+    emit(result, True, dump_img, args.dump_outputs)
+    if world > 1:
+        dist.destroy_process_group()
+
+
+def emit(result, details, dump_img, dump_dir):
+    """The end of a run on rank 0: the timed path's last image to `dump_dir` (--dump-outputs), the details file (--full), the ONE line."""
+    if dump_dir:
+        dump_outputs(dump_img, dump_dir)
     line = compact_line(result)
-    details_path = write_details(result)
-    if details_path:
-        line["details"] = details_path
+    if details:
+        details_path = write_details(result)
+        if details_path:
+            line["details"] = details_path
     text = json.dumps(line, separators=(",", ":"))
     assert len(text) < LINE_LIMIT, len(text)
     print(text)
-    if world > 1:
-        dist.destroy_process_group()
+
+
+DUMP_BYTES = 60_000_000     # --dump-outputs: at most this much in all (16 B per pixel: up to 1 936^2 pixels whole, a sample beyond)
+DUMP_SEED = 20261016
+
+
+def dump_outputs(img, path):
+    """`img`: the [h, w, 4] int32 GeometryPixel words of a frame (normal x y z as f32 bits, depth as u32) -> path/normal.npy (float32
+    [h, w, 3]) and path/depth.npy (float32 [h, w]).  A frame of more than DUMP_BYTES: the same pixels of it every run (a sample drawn
+    with DUMP_SEED), flat, with path/pixel_index.npy (float64, row-major index of each pixel)."""
+    h, w = int(img.shape[0]), int(img.shape[1])
+    words = img.cpu().numpy().view(np.uint32).reshape(h * w, 4)
+    normal = np.ascontiguousarray(words[:, :3]).view(np.float32)
+    depth = words[:, 3].astype(np.float32)
+    os.makedirs(path, exist_ok=True)
+    index_path = os.path.join(path, "pixel_index.npy")
+    if h * w * 16 <= DUMP_BYTES:
+        if os.path.exists(index_path):       # (left by a sampled dump of a larger frame)
+            os.remove(index_path)
+        np.save(os.path.join(path, "normal.npy"), normal.reshape(h, w, 3))
+        np.save(os.path.join(path, "depth.npy"), depth.reshape(h, w))
+        return
+    idx = np.sort(np.random.default_rng(DUMP_SEED).choice(h * w, DUMP_BYTES // 24, replace=False))
+    np.save(os.path.join(path, "normal.npy"), normal[idx])
+    np.save(os.path.join(path, "depth.npy"), depth[idx])
+    np.save(index_path, idx.astype(np.float64))
 
 
 TUNING_CAP = 64         # untimed frames beyond --warmup the library's arrangement tuner may take PER KIND of frame (windows of 12, 12 + 4 and 12 queued frames + the verdict; `tuning_frames`
@@ -851,7 +918,8 @@ def compact_line(result):
                                                                   "images_equal")} if isinstance(v, dict) else v
         line["partitions"] = short
         line["collectives"] = (result.get("collectives") or "")[:100]
-        line["per_rank"] = result.get("per_rank")
+        if result.get("per_rank") is not None:     # (--full)
+            line["per_rank"] = result["per_rank"]
     line = _rnd(line)
     # should the line still outgrow the limit (a long error text, 8 ranks of stage times): shed the optional objects, never the contract's
     for k in ("per_rank", "multi_gpu_predicted", "c2_2d", "c4z_colonnade", "c3_bear", "c5_mesh", "parity", "roofline_timed_path"):

@@ -29,7 +29,7 @@ def _frame():
     return full
 
 
-def _worker(rank, world, port, out_path, direct):
+def _worker(rank, world, port, out_path, direct, extra=("--full",)):
     import torch
     import torch.distributed as dist
     os.environ.update(MASTER_ADDR="127.0.0.1", MASTER_PORT=str(port), RANK=str(rank), WORLD_SIZE=str(world), LOCAL_RANK=str(rank))
@@ -120,8 +120,11 @@ def _worker(rank, world, port, out_path, direct):
             assert os.path.exists(path)
             return Shape()
 
+    renders = [0]
+
     def render3d(shape, n, out=None, shard=0, n_shards=1, block=None, **kw):
         assert n == N and out is not None
+        renders[0] += 1
         if block is not None:
             part = _parts_of(full, block[1], N, block[0], np.random.default_rng(block[0]))
         elif n_shards > 1:
@@ -136,11 +139,13 @@ def _worker(rank, world, port, out_path, direct):
     F.merge_depth = lambda a, b, d, hip=None: merge_ref(a, b, d)
 
     import bench
-    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--size", str(N)]
+    sys.argv = ["bench.py", "--gpus", str(world), "--steps", "3", "--warmup", "1", "--size", str(N)] + list(extra)
     if rank == 0:
         sys.stdout = open(out_path, "w")
     bench.main()
     sys.stdout.flush()
+    with open(f"{out_path}.renders{rank}", "w") as f:
+        f.write(str(renders[0]))
 
 
 @pytest.mark.parametrize("direct,world", [(False, 2), (True, 2), (True, 4), (True, 8)])     # 8: the node the scaling run uses (octants 2 x 2 x 2)
@@ -184,6 +189,81 @@ def test_bench_two_ranks_protocol(tmp_path, direct, world):
     assert all({"coarse_chain_ms", "slab_ms", "tile_stage_ms", "leaf_ms", "normals_ms"} <= set(q) for q in r["per_rank"])
     if world == 8:
         assert p["blocks"]["split"] == [2, 2, 2]
+
+
+def _spawn_bench(tmp_path, world, extra):
+    """bench.main() on `world` stand-in ranks (torch.distributed collectives) -> (rank 0's one line, every rank's count of frames rendered)"""
+    import torch.multiprocessing as mp
+    s = socket.socket()
+    s.bind(("127.0.0.1", 0))
+    port = s.getsockname()[1]
+    s.close()
+    out_path = str(tmp_path / "rank0.out")
+    mp.spawn(_worker, args=(world, port, out_path, False, tuple(extra)), nprocs=world, join=True)
+    lines = [l for l in open(out_path).read().splitlines() if l.strip()]
+    assert len(lines) == 1, lines
+    return json.loads(lines[0]), [int(open(f"{out_path}.renders{r}").read()) for r in range(world)]
+
+
+def _assert_dump_is_the_frame(d):
+    full = _frame()
+    normal, depth = np.load(d / "normal.npy"), np.load(d / "depth.npy")
+    assert normal.dtype == np.float32 and normal.shape == (N, N, 3) and depth.dtype == np.float32 and depth.shape == (N, N)
+    assert (normal.view(np.int32) == full[..., :3]).all() and (depth == full[..., 3].astype(np.float32)).all()
+    assert not (d / "pixel_index.npy").exists()
+
+
+@pytest.mark.parametrize("world", [1, 2])
+def test_a_plain_run_times_the_headline_and_nothing_else(tmp_path, world):
+    """Without --full, bench.py renders the warm-up frames and the timed steps (at N > 1: for each of the two shardings `value` chooses
+    from, with the fixed count of untimed frames every rank takes) and nothing more; its line holds the contract's fields, not the legs
+    that --full adds; --dump-outputs writes the last timed frame as float32 arrays."""
+    d = tmp_path / "outputs"
+    r, renders = _spawn_bench(tmp_path, world, ["--dump-outputs", str(d)])
+    for key in ("metric", "value", "unit", "n_gpus", "steps", "warmup", "ms_per_step", "higher_is_better", "scaling", "vs_baseline", "dtype", "data", "config"):
+        assert key in r, key
+    assert r["n_gpus"] == world and r["steps"] == 3 and r["warmup"] == 1 and r["unit"] == "Mvoxel/s" and r["higher_is_better"] is True and r["dtype"] == "f32"
+    assert abs(r["value"] - N ** 3 / (r["ms_per_step"] * 1e-3) / 1e6) <= 1e-3 * r["value"]
+    for key in ("frame_latency_ms", "host_output_frame_ms", "device_bytes", "roofline", "roofline_timed_path", "cpu_baseline", "parity", "c3_bear",
+                "c5_mesh", "c2_2d", "c4z_colonnade", "multi_gpu_predicted", "predicted", "per_rank", "details"):
+        assert key not in r, key
+    assert r["config"]["general_path"] is None
+    if world == 1:
+        assert renders == [1 + 3]
+    else:
+        assert set(r["partitions"]) == {"columns", "blocks"}
+        assert abs(r["value"] - max(r["partitions"][k]["value"] for k in ("columns", "blocks"))) <= 1e-6 * r["value"]
+        assert renders == [2 * (1 + 60 + 3)] * world
+    _assert_dump_is_the_frame(d)
+
+
+def test_full_run_dumps_the_timed_path_s_last_frame(tmp_path):
+    """--full renders into the output again after the timed steps (general path, profiled frames, ...); what --dump-outputs writes is still
+    the frame of the last timed step."""
+    d = tmp_path / "outputs"
+    r, _ = _spawn_bench(tmp_path, 2, ["--full", "--dump-outputs", str(d)])
+    assert "predicted" in r and "frames" in r["partitions"]
+    _assert_dump_is_the_frame(d)
+
+
+def test_a_large_frame_is_dumped_as_a_fixed_sample(tmp_path, monkeypatch):
+    import torch
+    bench = _bench_module()
+    full = _frame()
+    monkeypatch.setattr(bench, "DUMP_BYTES", 24 * 1000)
+    a, b = tmp_path / "a", tmp_path / "b"
+    bench.dump_outputs(torch.from_numpy(full), str(a))
+    bench.dump_outputs(torch.from_numpy(full.copy()), str(b))
+    idx = np.load(a / "pixel_index.npy")
+    assert idx.dtype == np.float64 and idx.shape == (1000,) and (np.diff(idx) > 0).all() and idx[-1] < N * N
+    for name in ("pixel_index", "normal", "depth"):
+        assert np.load(a / f"{name}.npy").tobytes() == np.load(b / f"{name}.npy").tobytes(), name       # the same pixels every run
+    flat = full.reshape(N * N, 4)[idx.astype(np.int64)]
+    assert (np.load(a / "normal.npy").view(np.int32) == flat[:, :3]).all() and (np.load(a / "depth.npy") == flat[:, 3]).all()
+    assert sum(os.path.getsize(a / f) for f in os.listdir(a)) <= 24 * 1000 + 3 * 256
+    monkeypatch.setattr(bench, "DUMP_BYTES", 60_000_000)
+    bench.dump_outputs(torch.from_numpy(full), str(a))        # (a whole frame into the same folder: no index left from the sample)
+    _assert_dump_is_the_frame(a)
 
 
 def test_c5_mesh_leg_reads_the_mesh_tools_output():

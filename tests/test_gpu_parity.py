@@ -371,6 +371,9 @@ def test_render3d_arrangement_tuner(model, n):
         assert (a[:, :, 3] == b["depth"]).all() and same_bits_f32(a[:, :, :3].copy().view(np.float32), b["normal"])
     taken = F.lib().fhip_debug_lane_frames(hip._h)
     assert taken >= 10          # (the lanes' window at least)
+    # (a frame takes the lanes only while the frame before it is still under way, capi_render.hpp lanes_possible: the stream is held busy
+    # so that every one of the 12 is queued behind work whatever the host's pace - the first, behind a finished frame, is a frame alone)
+    torch.cuda._sleep(200_000_000)
     for i in range(12):         # decided: the run goes on in the arrangement kept
         F.render3d(shape, n, out=outs[i % 7])
     hip.sync()

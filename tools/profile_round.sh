@@ -11,7 +11,7 @@ mkdir -p $OUT
 cd /tmp && export TMPDIR=/tmp
 for PATHNAME in default general; do
   if [ $PATHNAME = default ]; then FLAG="--no-general"; else FLAG="--only-general"; fi
-  CMD="python $R/bench.py --steps 5 --warmup 1 --no-cpu $FLAG"
+  CMD="python $R/bench.py --full --steps 5 --warmup 1 --no-cpu $FLAG"
   if [ -z "${PROFILE_ROUND_QUICK:-}" ]; then
   rm -rf /tmp/p_stats
   rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/p_stats -o s -- $CMD > $OUT/stats_run_$PATHNAME.log 2>&1
@@ -34,7 +34,7 @@ import csv, sys, collections, re, json, glob, os
 out = sys.argv[1]
 sys.path.insert(0, "tools")
 from src_hash import source_hash
-res = {"_comment": "per-kernel PMC totals of `bench.py --steps 5 --warmup 1 --no-cpu [--no-general | --only-general]` under rocprofv3 --pmc, one pass per counter "
+res = {"_comment": "per-kernel PMC totals of `bench.py --full --steps 5 --warmup 1 --no-cpu [--no-general | --only-general]` under rocprofv3 --pmc, one pass per counter "
                    "group and path; frames = launches of k_finish3d in the pass; FETCH_SIZE / WRITE_SIZE in KB as reported (bench.py doubles FETCH_SIZE as "
                    "MI355X_MICROARCH.md prescribes for gfx950)",
        "source_hash": source_hash()}

@@ -12,7 +12,7 @@ grep -v "^RCCL\|^HIP ver\|^ROCm\|^Hostname\|^Librccl" $O/gpu_tests.log | tail -4
 timeout -k 5 900 bash tools/profile_round.sh $TAG > $O/profile_round.log 2>&1; tail -30 $O/profile_round.log | cut -c1-200
 cp gpurun_out/prof_$TAG/traffic.json profiles/traffic_r06.json 2>/dev/null
 cp gpurun_out/prof_$TAG/*.csv gpurun_out/prof_$TAG/*.txt gpurun_out/prof_$TAG/*.json $O/ 2>/dev/null
-timeout -k 5 600 python bench.py > $O/bench.json 2> $O/bench.err; cp gpurun_out/bench_details_n1.json $O/ 2>/dev/null; cat $O/bench.json
+timeout -k 5 600 python bench.py --full > $O/bench.json 2> $O/bench.err; cp $O/../bench_details_n1.json $O/ 2>/dev/null; cat $O/bench.json
 timeout -k 5 300 python tools/config_times.py > $O/config_times.log 2>&1; cp gpurun_out/other_configs.json $O/; tail -12 $O/config_times.log | cut -c1-300
 # the leaf kernel's per-launch time by the profiler and by the library's events over the SAME steady frames (profiled mode, frames alone)
 (cd /tmp && export TMPDIR=/tmp && rm -rf /tmp/ss && timeout -k 5 300 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/ss -o s -- python $R/tools/steady_stats.py prospero.vm 1024 general 30 > $O/steady_stats_general.log 2>&1; find /tmp/ss -name "*kernel_stats.csv" -exec cp {} $O/kernel_stats_general_steady.csv \;)

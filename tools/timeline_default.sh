@@ -5,7 +5,7 @@ TAG=${1:-x}
 R=$PWD
 cd /tmp && export TMPDIR=/tmp
 rm -rf /tmp/tl
-timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tl -o t -- python $R/bench.py --steps 40 --warmup 5 --no-cpu --no-general > /tmp/tl.log 2>&1
+timeout 200 rocprofv3 --kernel-trace --stats --output-format csv -d /tmp/tl -o t -- python $R/bench.py --full --steps 40 --warmup 5 --no-cpu --no-general > /tmp/tl.log 2>&1
 python $R/tools/timeline.py /tmp/tl 3 +9 > $R/gpurun_out/timeline_$TAG.txt 2>&1
 find /tmp/tl -name "*kernel_stats.csv" -exec cp {} $R/gpurun_out/kernel_stats_$TAG.csv \;
 exit 0
