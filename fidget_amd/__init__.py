@@ -25,7 +25,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -52,7 +52,7 @@ EXPORTS = [
     "fhip_ctx_create", "fhip_ctx_destroy", "fhip_ctx_trim", "fhip_ctx_reserve_arena", "fhip_libm_probe", "fhip_last_error", "fhip_ctx_sync", "fhip_cancel", "fhip_cancel_reset", "fhip_cancel_watch", "fhip_ctx_set_option", "fhip_ctx_get_option",
     "fhip_tape_from_bytecode", "fhip_tape_free", "fhip_tape_len", "fhip_tape_reg_tape", "fhip_tape_choice_count", "fhip_tape_reg_count",
     "fhip_tape_var_count", "fhip_tape_output_count", "fhip_tape_ops", "fhip_simplify", "fhip_interval_eval",
-    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge",
+    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -156,6 +156,7 @@ def lib():
             "fhip_point_eval": (i32, [vp, vp, vp, u32, u32, vp, vp, vp]),
             "fhip_float_eval": (i32, [vp, vp, vp, vp, u32, vp]),
             "fhip_grad_eval": (i32, [vp, vp, vp, vp, u32, vp]),
+            "fhip_solve": (i32, [vp, vp, u32, vp, vp, vp, u32, vp, u32, u32, vp, vp, vp, vp]),
             "fhip_render2d": (i32, [vp, vp, C.POINTER(_Cfg2D), vp, i32]),
             "fhip_render3d": (i32, [vp, vp, C.POINTER(_Cfg3D), vp, i32]),
             "fhip_render3d_shard": (i32, [vp, vp, C.POINTER(_Cfg3D), vp, i32, u32, u32]),
@@ -1145,3 +1146,61 @@ def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False):
     finally:
         lib().fhip_mesh_free(h)
     return leaves, {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
+
+
+# ---- constraint solver (fidget::solver, fidget-solver/src/lib.rs) ---------------------------------------------------------
+class Free(float):
+    """Parameter::Free(start) (fidget-solver/src/lib.rs:11-17): a variable the solver moves, from this start"""
+
+
+class Fixed(float):
+    """Parameter::Fixed(value): a variable held at this value"""
+
+
+SOLVE_EXITS = {0: "zero_residual", 1: "no_change", 2: "zero_error", 3: "zero_damping", 4: "stalled", 5: "max_iterations",
+               6: "max_retries"}       # include/fidget_hip.h FHIP_SOLVE_*
+SOLVE_MAX_FREE = 64
+
+
+def solve_key(key):
+    """'x' | 'y' | 'z' | int (a Var::V index, as Context.var) -> (axis, index) of fhip_solve"""
+    if isinstance(key, str):
+        return "xyz".index(key.lower()), 0
+    return 3, int(key)
+
+
+def solve_batch(constraints, keys, free_mask, values, max_iterations=0, hip=None):
+    """fhip_solve: every row of `values` ([n_instances][n_params]: the start of a free parameter, the value of a fixed one) is one
+    solve of the same constraints (a list of Shape; residual = output 0).  keys: per parameter 'x' | 'y' | 'z' | int; free_mask:
+    per parameter, true = free.  Returns (out [n_instances][n_free] - the free parameters in parameter order -, err, iterations,
+    exit_reason - SOLVE_EXITS)."""
+    keys = list(keys)
+    free = np.ascontiguousarray(np.asarray(free_mask, dtype=bool).reshape(len(keys)), dtype=np.uint8)
+    vals = np.ascontiguousarray(np.asarray(values, dtype=np.float32).reshape(-1, len(keys)))
+    n_inst, n_free = vals.shape[0], int(free.sum())
+    ax = np.array([solve_key(k)[0] for k in keys], dtype=np.int32)
+    ix = np.array([solve_key(k)[1] for k in keys], dtype=np.uint64)
+    hip = hip or (constraints[0].hip if constraints else default_context())
+    tapes = (C.c_void_p * max(len(constraints), 1))(*[s._h.value for s in constraints])
+    out = np.zeros((n_inst, n_free), dtype=np.float32)
+    err = np.zeros(n_inst, dtype=np.float32)
+    its = np.zeros(n_inst, dtype=np.uint32)
+    ex = np.zeros(n_inst, dtype=np.int32)
+    st = lib().fhip_solve(hip._h, tapes, len(constraints), _p(ax), _p(ix), _p(free), len(keys), _p(vals), n_inst,
+                          int(max_iterations), _p(out), _p(err), _p(its), _p(ex))
+    if st in (1, 5, 6):
+        raise ValueError(f"{STATUS[st]}: {lib().fhip_last_error(hip._h).decode()}")
+    hip.check(st)
+    return out, err, its, ex
+
+
+def solve(constraints, params, max_iterations=0, hip=None):
+    """fidget::solver::solve (fidget-solver/src/lib.rs:191): params maps 'x' | 'y' | 'z' | int to Free(start) or Fixed(value);
+    returns {key: value} for the free variables"""
+    keys = list(params)
+    for k in keys:
+        if not isinstance(params[k], (Free, Fixed)):
+            raise TypeError(f"parameter {k!r}: Free(v) or Fixed(v), not {params[k]!r}")
+    free = [isinstance(params[k], Free) for k in keys]
+    out = solve_batch(constraints, keys, free, [[float(params[k]) for k in keys]], max_iterations, hip)[0][0]
+    return {k: float(v) for k, v in zip([k for k, f in zip(keys, free) if f], out)}

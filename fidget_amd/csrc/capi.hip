@@ -23,11 +23,12 @@
 #include "effects.hip"
 #include "mesh.hip"
 #include "prune2.hip"
+#include "solve.hip"
 #include "host_mesh.hpp"
 
 #define FH_LDS_MAX 163840  // 160 KiB per workgroup on gfx950
 
-// The C ABI as one translation unit in eight fragments (each was a section of this file when it was 2 900 lines long): the fragments are
+// The C ABI as one translation unit in nine fragments (each was a section of this file when it was 2 900 lines long): the fragments are
 // not stand-alone headers - they are included here, in this order, and share the static helpers of capi_core.hpp.
 #include "capi_core.hpp"
 
@@ -39,6 +40,7 @@ extern "C" {
 #include "capi_render.hpp"
 #include "capi_effects.hpp"
 #include "capi_mesh.hpp"
+#include "capi_solve.hpp"
 #include "capi_debug.hpp"
 
 }  // extern "C"

@@ -153,6 +153,29 @@ fhip_status fhip_float_eval(fhip_ctx* ctx, const fhip_tape* tape, const float* c
 fhip_status fhip_grad_eval(fhip_ctx* ctx, const fhip_tape* tape, const float* const* vars, const uint32_t* lens,
                            uint32_t n_vars, float* const* out);
 
+/* ---- constraint solver ---------------------------------------------------------------
+ * fidget::solver::solve (fidget-solver/src/lib.rs:191-289), batched: n_instances independent Levenberg-Marquardt solves of the
+ * same constraints, in one launch.  Residual i is output 0 of constraints[i].  Parameter p names a variable as fhip_graph_var
+ * does (param_axis 0 X, 1 Y, 2 Z, 3 Var::V(param_index[p])); param_free[p] != 0 makes it free.  A variable a tape reads that no
+ * parameter names evaluates as 0.  values: [n_instances][n_params], the start of a free parameter or the value of a fixed one.
+ * out: [n_instances][n_free], the free parameters in parameter order; err: [n_instances] the error sum_i r_i^2 at the result
+ * (0 after FHIP_SOLVE_ZERO_RESIDUAL, +inf if no step was accepted); iterations: accepted steps; exit_reason: FHIP_SOLVE_*.
+ * err, iterations and exit_reason may be NULL.  max_iterations = 0: 1000.  Differences from the reference (the free
+ * variables' order, the caps, the linear solve): SOLVER.md.  FHIP_ERR_UNSUPPORTED: more than 64 free parameters;
+ * FHIP_ERR_BAD_VAR_SLICE: a variable named twice, an axis outside 0..3; FHIP_ERR_BAD_TAPE: a constraint with no output -
+ * each returned before any launch.  Blocking; host buffers. */
+#define FHIP_SOLVE_ZERO_RESIDUAL 0   /* every residual exactly 0 */
+#define FHIP_SOLVE_NO_CHANGE 1       /* the accepted step changed no free parameter */
+#define FHIP_SOLVE_ZERO_ERROR 2      /* the error of the accepted step is 0 */
+#define FHIP_SOLVE_ZERO_DAMPING 3    /* the damping underflowed to 0 */
+#define FHIP_SOLVE_STALLED 4         /* the last four errors are equal */
+#define FHIP_SOLVE_MAX_ITERATIONS 5  /* max_iterations steps accepted */
+#define FHIP_SOLVE_MAX_RETRIES 6     /* 128 trial steps in a row rejected */
+fhip_status fhip_solve(fhip_ctx* ctx, const fhip_tape* const* constraints, uint32_t n_constraints, const int32_t* param_axis,
+                       const uint64_t* param_index, const uint8_t* param_free, uint32_t n_params, const float* values,
+                       uint32_t n_instances, uint32_t max_iterations, float* out, float* err, uint32_t* iterations,
+                       int32_t* exit_reason);
+
 /* ---- batched renders (the throughput path) ------------------------------------------ */
 /* fidget_raster::pixel::{RenderConfig, EvalConfig} (fidget-raster/src/pixel.rs:27-57) */
 typedef struct fhip_render2d_config {

@@ -69,6 +69,10 @@ extern "C" {
                            n_vars: u32, out: *const *mut f32) -> fhip_status;
     pub fn fhip_grad_eval(ctx: *mut fhip_ctx, tape: *const fhip_tape, vars: *const *const f32, lens: *const u32,
                           n_vars: u32, out: *const *mut f32) -> fhip_status;
+    /// fidget::solver::solve (fidget-solver/src/lib.rs:191), batched over `n_instances` parameter sets
+    pub fn fhip_solve(ctx: *mut fhip_ctx, constraints: *const *const fhip_tape, n_constraints: u32, param_axis: *const i32,
+                      param_index: *const u64, param_free: *const u8, n_params: u32, values: *const f32, n_instances: u32,
+                      max_iterations: u32, out: *mut f32, err: *mut f32, iterations: *mut u32, exit_reason: *mut i32) -> fhip_status;
 
     pub fn fhip_render2d(ctx: *mut fhip_ctx, tape: *const fhip_tape, cfg: *const fhip_render2d_config,
                          out: *mut f32, out_is_device: c_int) -> fhip_status;
