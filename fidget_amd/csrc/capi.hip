@@ -13,6 +13,7 @@
 #include <mutex>
 #include <string>
 #include <functional>
+#include <memory>
 #include <vector>
 
 #include "../../include/fidget_hip.h"
@@ -28,7 +29,7 @@
 
 #define FH_LDS_MAX 163840  // 160 KiB per workgroup on gfx950
 
-// The C ABI as one translation unit in nine fragments (each was a section of this file when it was 2 900 lines long): the fragments are
+// The C ABI as one translation unit in ten fragments (each was a section of this file when it was 2 900 lines long): the fragments are
 // not stand-alone headers - they are included here, in this order, and share the static helpers of capi_core.hpp.
 #include "capi_core.hpp"
 
@@ -37,6 +38,7 @@ extern "C" {
 #include "capi_context.hpp"
 #include "capi_tapes.hpp"
 #include "capi_eval.hpp"
+#include "capi_bound.hpp"
 #include "capi_render.hpp"
 #include "capi_effects.hpp"
 #include "capi_mesh.hpp"

@@ -15,6 +15,17 @@ struct DevBuf {
 };
 
 static std::atomic<uint64_t> g_tape_serial{1};
+// The bound tapes of a tape that reads more input slots than a render binds (capi_bound.hpp), one per binding, the last few kept
+struct BoundCache {
+    struct Entry {
+        uint64_t hash = 0, used = 0;
+        std::vector<uint64_t> key;                  // the device, then per input slot: axis << 32, or 3 << 32 | the bound value's bits
+        std::shared_ptr<const fhip_tape> tape;
+    };
+    std::mutex lock;
+    std::vector<Entry> entries;
+    uint64_t clock = 0;
+};
 struct fhip_tape {
     const uint64_t serial = g_tape_serial.fetch_add(1);   // identity for "these tapes are already in the arena"
     fh::HostTape t;
@@ -40,6 +51,10 @@ struct fhip_tape {
     // used from several devices should be built per device)
     mutable std::mutex upload_lock;
     mutable int device = -1;
+    // A bound tape (capi_bound.hpp): the parent's serial (what the lane tuner keys on) and the handle that frames hold it by; 0 / empty otherwise
+    uint64_t parent_serial = 0;
+    std::weak_ptr<const fhip_tape> self;
+    mutable BoundCache bound;             // ... and a parent's bound tapes
 };
 struct fhip_graph {
     fh::Graph g;
@@ -105,6 +120,7 @@ struct FrameBufs {
     bool async_pending = false;     // the last render of this set left its result on the device: its overflow flags have not been read yet
     hipEvent_t ev_done = nullptr;   // recorded when the last frame of this set has been queued completely
     bool ev_done_valid = false;
+    std::shared_ptr<const fhip_tape> bound_hold;   // the bound tape of the last frame of this set (capi_bound.hpp), kept until that frame is over
     void release_all() {
         DevBuf* bufs[] = {&state, &arena, &leaves, &leaf_table, &zbuf, &normals, &fp_lists, &mind, &squeue, &slots[0], &slots[1],
                           &leaves_b, &leaf_table_b, &fp_lists_b, &chw[0], &chw[1], &tvals, &topch, &chwr, &gscratch, &rare_scratch};
@@ -112,6 +128,7 @@ struct FrameBufs {
         for (auto& q : queue) q.release();
         if (ev_done) (void)hipEventDestroy(ev_done);
         ev_done = nullptr;
+        bound_hold.reset();
     }
 };
 struct fhip_ctx : FrameBufs {

@@ -394,6 +394,13 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
     const bool keep = mode != MESH_SAMPLE && !dev_asm;
     if (depth > 20) return fail(ctx, FHIP_ERR_UNSUPPORTED, "octree depth above 20");
     if (n_parts < 1 || n_parts > 8 || part >= n_parts) return fail(ctx, FHIP_ERR_UNSUPPORTED, "mesh parts: 1..8, part < n_parts");
+    std::shared_ptr<const fhip_tape> bound;     // (more input slots than a mesh binds: its bound tape, capi_bound.hpp; held for the call, which waits for its work)
+    if (tape->t.n_vars > FH_MAX_INPUTS) {
+        const fhip_status bs = bound_tape(ctx, tape, axis_slots, var_keys, var_values, n_vars, bound);
+        if (bs) return bs;
+        tape = bound.get();
+        axis_slots = BOUND_AXES; var_keys = nullptr; var_values = nullptr; n_vars = 0;
+    }
     const fh::HostTape& t = tape->t;
     if (t.n_outputs != 1) return fail(ctx, FHIP_ERR_BAD_TAPE, "shape tapes have exactly one output");
     (void)hipSetDevice(ctx->device);

@@ -572,6 +572,7 @@ static fhip_status upload_frame(fhip_ctx* ctx, const fhip_tape* tape, RenderSetu
     }
     memcpy(sg.p, &R.S, sizeof(FhRenderState));
     if (roots_bytes) memcpy((char*)sg.p + sizeof(FhRenderState), R.roots.data(), roots_bytes);
+    { const fhip_status hs = hold_bound(ctx, tape); if (hs) return hs; }
     // The root tape and its groups sit below arena_root_end, where no frame writes: a shape rendered
     // again finds them there (17 small copies, 0.1 ms of a 4 ms frame, otherwise).
     if (ctx->resident_serial != tape->serial || ctx->resident_groups != R.S.n_tgroups) {
@@ -1483,7 +1484,7 @@ static bool lane_mode(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_
     const bool prior = ctx->use_asm && !ctx->opt.no_columns_t && !tape_asm_ok(tape->t);
     if (!possible) { ctx->tune_last_key = 0; return false; }       // (a frame alone, a profiled frame, ...: the stage pipeline; the sequence is broken)
     if (!ctx->opt.lanes_tune) return prior;
-    uint64_t key = tape->serial * 0x9E3779B97F4A7C15ull;
+    uint64_t key = (tape->parent_serial ? tape->parent_serial : tape->serial) * 0x9E3779B97F4A7C15ull;   // (a bound tape: its parent's entry)
     key ^= ((uint64_t)cfg->width << 42) ^ ((uint64_t)cfg->height << 21) ^ (uint64_t)cfg->depth;
     key ^= (((uint64_t)part.shard * 64 + part.n_shards) * 0xD6E8FEB86659FD93ull) ^ ((((uint64_t)part.ix * 16 + part.iy) * 16 + part.iz) * 4096 + (part.nx * 16 + part.ny) * 16 + part.nz) * 0xA24BAED4963EE407ull;
     key |= 1;
@@ -1556,6 +1557,15 @@ static fhip_status frame_queued(fhip_ctx* ctx, int out_is_device) {      // (the
 static fhip_status render3d_part(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_config* cfg, void* out,
                                  int out_is_device, const PartSpec& part) {
     (void)hipSetDevice(ctx->device);
+    std::shared_ptr<const fhip_tape> bound;     // (more input slots than a render binds: its bound tape, capi_bound.hpp)
+    fhip_render3d_config bcfg;
+    if (tape->t.n_vars > FH_MAX_INPUTS) {
+        const fhip_status bs = bound_tape(ctx, tape, cfg->axis_slots, cfg->var_keys, cfg->var_values, cfg->n_vars, bound);
+        if (bs) return bs;
+        tape = bound.get();
+        bcfg = *cfg; bcfg.axis_slots = BOUND_AXES; bcfg.var_keys = nullptr; bcfg.var_values = nullptr; bcfg.n_vars = 0;
+        cfg = &bcfg;
+    }
     fhip_status st = lane_mode(ctx, tape, cfg, out_is_device, part)
         ? run_on_lane(ctx, 8, (size_t)cfg->width * cfg->height * sizeof(FhGeometryPixel), out,
                       [&](fhip_ctx* L, void* img) { return render3d_frame(L, tape, cfg, img, 1, part); })
@@ -1572,6 +1582,15 @@ static fhip_status render3d_part(fhip_ctx* ctx, const fhip_tape* tape, const fhi
 // one-stream contexts in turn (profiles/r04r/frame_major3.txt)
 fhip_status fhip_render2d(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render2d_config* cfg, float* out, int out_is_device) {
     (void)hipSetDevice(ctx->device);
+    std::shared_ptr<const fhip_tape> bound;     // (as render3d_part)
+    fhip_render2d_config bcfg;
+    if (tape->t.n_vars > FH_MAX_INPUTS) {
+        const fhip_status bs = bound_tape(ctx, tape, cfg->axis_slots, cfg->var_keys, cfg->var_values, cfg->n_vars, bound);
+        if (bs) return bs;
+        tape = bound.get();
+        bcfg = *cfg; bcfg.axis_slots = BOUND_AXES; bcfg.var_keys = nullptr; bcfg.var_values = nullptr; bcfg.n_vars = 0;
+        cfg = &bcfg;
+    }
     ctx->tune_cur = -1;
     ctx->tune_last_key = 0;       // (a 2D frame between two 3D frames of one kind: their window starts again)
     fhip_status st = lanes_possible(ctx, out_is_device)

@@ -246,19 +246,20 @@ struct SsaOp {
     uint32_t out, a, b;
     uint32_t imm;  // f32 bits or slot
 };
+// A tape's VarMap: any number of variables (a hash from Var::V index to slot, so that a tape of thousands of them builds in linear time)
 struct VarTable {
     int axis[3] = {-1, -1, -1};
-    std::vector<std::pair<uint64_t, int>> named;  // Var::V(index) -> slot
+    std::unordered_map<uint64_t, int> named;  // Var::V(index) -> slot
     int count = 0;
     int slot_of(uint8_t vkind, uint64_t index) const {
         if (vkind < 3) return axis[vkind];
-        for (auto& p : named) if (p.first == index) return p.second;
-        return -1;
+        auto it = named.find(index);
+        return it == named.end() ? -1 : it->second;
     }
     void touch(uint8_t vkind, uint64_t index) {
         if (slot_of(vkind, index) >= 0) return;
         if (vkind < 3) axis[vkind] = count++;
-        else named.push_back({index, count++});
+        else named.emplace(index, count++);
     }
 };
 struct SsaProgram {
@@ -492,7 +493,7 @@ static inline bool from_bytecode(const uint32_t* w, size_t n_words, SsaProgram& 
             fwd.push_back({FH_OUTPUT, 0, a, 0, imm});
             if (imm + 1 > n_out) n_out = imm + 1;
         } else if (op == 1) {  // Input
-            if (imm >= 16) { err = "input slot out of range (16 variables at most)"; return false; }   // FH_MAX_INPUTS
+            if (imm >= FH_MAX_TAPE_VARS) { err = "input slot out of range"; return false; }
             cur[r1] = next;
             fwd.push_back({FH_INPUT, next++, 0, 0, imm});
             if (imm + 1 > max_in) max_in = imm + 1;

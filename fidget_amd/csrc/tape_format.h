@@ -59,6 +59,9 @@ FH_HD static inline uint64_t fh_pack(uint32_t op, uint32_t out, uint32_t a, uint
 #define FH_W_OUT(w0) (((w0) >> 8) & 0xFFFu)
 #define FH_W_A(w0) ((w0) >> 20)
 #define FH_MAX_REGS 4096u
+// Input slots of a tape: the only bound on its variables (a bytecode slot would otherwise size per-slot tables at up to 2^32 entries).
+// Renders and meshes bind every variable but the axes to a constant, so they need FH_MAX_INPUTS (render_state.h) slots at most.
+#define FH_MAX_TAPE_VARS (1u << 20)
 
 // Choice values, identical to the reference (fidget-core/src/vm/choice.rs:15-29)
 enum { FH_CHOICE_UNKNOWN = 0, FH_CHOICE_LEFT = 1, FH_CHOICE_RIGHT = 2, FH_CHOICE_BOTH = 3 };

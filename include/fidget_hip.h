@@ -88,7 +88,9 @@ fhip_status fhip_ctx_get_option(const fhip_ctx* ctx, const char* name, int* valu
  * (fidget-bytecode/src/lib.rs:11-42, 203-332).  Replaces JitFunction's
  * `point_tape/interval_tape/float_slice_tape/grad_slice_tape` compilation
  * (fidget-jit/src/lib.rs:875-908): one device tape serves all four evaluators.
- * Variable slots are the reference's VarMap indices. */
+ * Variable slots are the reference's VarMap indices, any number of them (input slots below 2^20).  The evaluators and
+ * fhip_solve take every tape; renders and meshes of a tape that reads more than 16 input slots run its bound tape, the same
+ * ops with the bound variables as immediates (BOUND_TAPES.md): the same image, FHIP_ERR_MISSING_VAR before any launch. */
 fhip_status fhip_tape_from_bytecode(fhip_ctx* ctx, const uint32_t* words, size_t n_words, fhip_tape** out);
 void fhip_tape_free(fhip_tape* tape);
 uint32_t fhip_tape_len(const fhip_tape* tape);          /* Function::size      eval/mod.rs:171 */

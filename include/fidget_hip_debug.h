@@ -39,6 +39,10 @@ int fhip_debug_lane_tune(const fhip_ctx* ctx, float ms[3], int* lanes);
  * against the routine as the HIP kernels inline it: out = {results whose bits differ, an input where they do} */
 fhip_status fhip_debug_trans_probe(fhip_ctx* ctx, uint32_t copy, uint32_t fn, uint32_t first, uint64_t n, uint64_t out[2]);
 uint32_t fhip_debug_arena(fhip_ctx* ctx, uint32_t off, uint32_t n, uint64_t* out);  /* ops of the tape arena after a frame */
+/* The bound tape that a render or mesh of `tape` with this binding runs (the render configs' axis_slots, var_keys, var_values, n_vars):
+ * its ops one for one, bound inputs as immediates, axes as slots 0 / 1 / 2 (BOUND_TAPES.md).  A tape of its own: fhip_tape_free frees it */
+fhip_status fhip_debug_bound_tape(fhip_ctx* ctx, const fhip_tape* tape, const int32_t* axis_slots, const uint64_t* keys, const float* vals,
+                                  uint32_t n, fhip_tape** out);
 /* Times `reps` passes of the point interpreter over `tape` in `n_waves` waves
  * (variant 0: 16 registers x 4 voxels, 1: 32 x 2, 2: LDS register file, 3: 32 x 1). */
 fhip_status fhip_debug_bench(fhip_ctx* ctx, const fhip_tape* tape, uint32_t n_waves, uint32_t reps, int variant,

@@ -1,7 +1,8 @@
 #!/usr/bin/env python3
 """Batch times of the constraint solver (fhip_solve, solve.hip) against its host build on N threads (tests/host_build/solve_host.cpp),
 the same instances on both: 65 536 instances of a 2-variable system (small_quadratic), 4 096 starts of one medium_linear system (10 free),
-64 of a banded 50-variable system, and the projection of 65 536 points onto prospero.vm.  fhip_solve is blocking (it ends with a stream
+64 of a banded 50-variable system, medium_linear (1 000 draws) and big_linear (50) with the matrix as
+fixed parameters, and the projection of 65 536 points onto prospero.vm.  fhip_solve is blocking (it ends with a stream
 synchronise), so a call's wall time is the device time plus its copies.  Warm-up, then repeats: median, min and max.
 usage: tools/solve_times.py [--repeats R] [--threads N] [--skip-host]   (one JSON line per case)"""
 import argparse
@@ -45,8 +46,12 @@ def main():
     fs, keys, free, _ = U.linear_const(F, mat, U.mat_vec(mat, vals))
     cases.append(("medium_linear_4096", fs, U.linear_const(O, mat, U.mat_vec(mat, vals))[0], keys, free,
                   U.rand_f32(rng, 4096, 10)))
-    fs, keys, free = U.banded_system(F, 50)      # (50 unknowns in one row exceed a device tape's 16 inputs: a banded system of 50)
+    fs, keys, free = U.banded_system(F, 50)
     cases.append(("banded_50_64", fs, U.banded_system(O, 50)[0], keys, free, U.rand_f32(rng, 64, 50)))
+    # the reference's medium_linear and big_linear with the matrix as fixed parameters: 21 and 101 inputs per tape, one call per batch
+    for n, count in ((10, 1000), (50, 50)):
+        fs, keys, free = U.linear_system(F, n)
+        cases.append((f"linear_{n}_params_{count}", fs, U.linear_system(O, n)[0], keys, free, U.linear_draws(rng, n, count)[0]))
     p = os.path.join(ROOT, "models", "prospero.vm")
     cases.append(("prospero_projection_65536", [F.Shape.from_vm(p)], [O.Shape.from_vm(p)], ["x", "y"], [True, True],
                   rng.uniform(-1, 1, (65536, 2)).astype(np.float32)))
