@@ -80,7 +80,7 @@ static const uint32_t V32_REGS = 32, V32_CHOICES = 256, V64_REGS = 64, V64_CHOIC
     X(no_asm, 0) X(no_split, 0) X(no_asm_tiles, 0) X(no_tiles_v, 0) X(no_asm_tiles_t, 0) X(no_columns_t, 0) X(no_asm_normals, 0)   \
     X(no_tape_groups, 0) X(prune2, 1)                                                                                           \
     /* short cuts: column invariance off everywhere; no_zrep 1 = no sharing of tiles along z at all, 2 = only not at the root level, 3 = every slab rendered;     \
-       column_walk: the leaf kernel by footprint columns - 1 in frames whose tapes read no z, 0 never, 2 always; column_group: every other frame by groups of 2^g layers of a column (0: by blocks of four footprints of a layer) */                  \
+       column_walk: the leaf kernel by footprint columns - 1 in frames whose tapes read no z, and then by the slab's list of leaves (no leaf table, k_classify3d, k_hits3d), 3 the same frames by the table, 0 never, 2 always; column_group: every other frame by groups of 2^g layers of a column (0: by blocks of four footprints of a layer) */                  \
     X(no_column_inv, 0) X(no_zrep, 0) X(root32_max, 4096) X(column_walk, 1) X(column_group, 2)                                                    \
     /* pipelining and resources */                                                                                             \
     X(no_pipeline, 0) X(frame_lanes, 4) X(lanes_tune, 1) X(lanes_fail, 0) X(slab_layers, 4) X(arena_mb, 4096)  \

@@ -1038,6 +1038,18 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     FhGeometryPixel* d_out = (FhGeometryPixel*)out;
     if (!out_is_device) { HIP_TRY(ctx, ctx->tmp_out.ensure(npix * sizeof(FhGeometryPixel))); d_out = (FhGeometryPixel*)ctx->tmp_out.p; }
     FhRenderState* dS = (FhRenderState*)ctx->state.p;
+    // Sparse columns (option column_walk, see the leaf kernel's launch below): the frames whose tapes guarantee at most one leaf per pixel
+    // column and slab.  `by_list` (column_walk 1): their leaf stage is driven by the slab's FhLeaf records themselves - wave i of fh_columns
+    // and of fh_normals takes leaf i - instead of by the [layer][footprint] table, which for 5.5 k leaves in 1 M entries was cleared, scanned
+    // whole by k_classify3d, scanned whole again by fh_columns and walked per footprint by k_hits3d in every frame.  The push then writes no
+    // table (render_state.h leaf_list), k_classify3d and k_hits3d shrink to their rare-mode blocks, and both kernels' grids follow the leaf
+    // count the last finished frame of this context reported (host_flags[3]: a hint - waves loop over the list, any grid is right).
+    const bool sparse_columns = R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
+    const bool by_list = ctx->opt.column_walk == 1 && sparse_columns && R.split && R.zrep && R.asm_points && R.asm_normals && P.slab / 8 <= 64 && ctx->host_flags;
+    R.S.leaf_list = by_list ? 1u : 0u;
+    const uint32_t table_words = by_list ? 0u : R.table_words;
+    uint32_t list_waves = (R.n_footprints + 63) / 64 * 64;      // (no frame has reported yet: what the column walk launches)
+    if (by_list && ctx->host_flags[3]) list_waves = std::min(list_waves, (ctx->host_flags[3] + ctx->host_flags[3] / 8 + 63) / 64 * 64);
     // (FHIP_DEBUG_ZFILL, diagnostics: every pixel already at the far depth - the front slab's leaf kernel then finds all its
     // leaves but nothing pending, which times its per-workgroup and per-leaf set-up without the interpretation)
     const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u},
@@ -1047,7 +1059,7 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     FH_SPAN(2);
     const uint32_t n_groups = R.groups_per_slab;
     const uint32_t pre = R.S.pre_levels;
-    const int reset_blocks = (int)std::max<uint32_t>(1, std::min<uint32_t>(1024, (std::max(R.table_words, n_groups) + 255) / 256));
+    const int reset_blocks = (int)std::max<uint32_t>(1, std::min<uint32_t>(1024, (std::max(table_words, n_groups) + 255) / 256));
     const int class_blocks = (int)((R.n_footprints + FH_CLASSIFY_FP - 1) / FH_CLASSIFY_FP);
     // Pipelined frames: the root level stays on the pre-pass stream, the level below it moves to the head of this frame's tile
     // chains on the side stream.  The two coarse levels of a frame are one dependent chain of ~0.9 ms that, on one stream, set
@@ -1180,16 +1192,16 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
             const bool pyr2 = P.n_levels == 2 && P.tiles[1] == 8 && P.tiles[0] == 32 && pre == 1;
             if (rebuild && pyr2) {
                 const uint32_t n0 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
-                FH_KLAUNCH(k_slab_begin2, dim3(n0 + reset_blocks), dim3(256), 0, ctx->stream, dS, n0, R.table_words, (uint32_t)k, n_groups);
+                FH_KLAUNCH(k_slab_begin2, dim3(n0 + reset_blocks), dim3(256), 0, ctx->stream, dS, n0, table_words, (uint32_t)k, n_groups);
                 return;
             }
             if (rebuild && pyr3 && pre == 2) {
                 const uint32_t n1 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
-                FH_KLAUNCH(k_slab_begin3, dim3(n1 + reset_blocks), dim3(256), 0, ctx->stream, dS, n1, R.table_words, (uint32_t)k, n_groups);
+                FH_KLAUNCH(k_slab_begin3, dim3(n1 + reset_blocks), dim3(256), 0, ctx->stream, dS, n1, table_words, (uint32_t)k, n_groups);
                 return;
             }
             // (workgroups of one wave: they find room beside a leaf kernel that fills the machine - 73 us per launch on the general path with four)
-            FH_KLAUNCH(k_reset_slab, dim3(reset_blocks * 4), dim3(WAVE), 0, ctx->stream, dS, R.table_words, (uint32_t)k, n_groups,
+            FH_KLAUNCH(k_reset_slab, dim3(reset_blocks * 4), dim3(WAVE), 0, ctx->stream, dS, table_words, (uint32_t)k, n_groups,
                                (pyr3 && rebuild) ? 1u : 0u);
             if (rebuild && pyr3) {
                 const uint32_t n1 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
@@ -1233,7 +1245,10 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
         const bool tail = pipe && ctx->stream3 && tail_mode > 0 && R.asm_points && !on_main && !R.alt_pre;   // (the HIP leaf kernels walk the footprint lists)
         const uint32_t z_lo = (uint32_t)k * P.slab, z_hi = z_lo + P.slab;
         auto classify_work = [&] {
-            launch(ctx, FHIP_K_OTHER, [&] {
+            // (by_list: nothing to classify - what is left of the launch is rare mode's blocks for the leaves beyond the leaf kernel's file)
+            if (by_list && rare && P.max_regs > R.S.leaf_asm_regs)
+                launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_classify3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, ctx->stream, dS, 1, 0u, rare_file(ctx, dS), ctx->rare_stride); });
+            else if (!by_list) launch(ctx, FHIP_K_OTHER, [&] {
                 FH_KLAUNCH(k_classify3d, dim3(class_blocks + (rare ? FH_RARE_BLOCKS : 0u)), dim3(P.slab / 8 > 16 ? 256 : WAVE), 0, ctx->stream, dS, R.asm_points ? 1 : 0, (uint32_t)class_blocks,
                            rare_file(ctx, dS), ctx->rare_stride);
             });
@@ -1250,7 +1265,15 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
 #endif
             launch(ctx, FHIP_K_NORMALS, [&] {
                 const int gs = blocks_for(ctx, R.lds_normals_small, 8), gb = blocks_big(ctx, R, R.lds_normals_big, 8);
-                if (R.asm_normals) {
+                if (by_list) {
+                    // (the leaf that owns a pixel's hit is its column's leaf or nobody: fh_normals takes the slab's leaves one per wave pass and
+                    // looks at the z-buffer itself; k_hits3d: rare mode's blocks for the footprints the push put on list 2)
+                    if (rare && P.max_regs > R.S.norm_asm_regs)
+                        FH_KLAUNCH(k_hits3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, ctx->stream, dS, z_lo, z_hi, R.hit_bucket_cap, 0u, rare_file(ctx, dS), ctx->rare_stride);
+                    struct { FhRenderState* S; uint32_t n_waves, slots, z_lo, z_hi, bucket_cap, mode; } kn = {dS, list_waves, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 1u};
+                    (void)launch_asm(ctx, R.asm_points_t ? FH_ASM_NORMALS_T : FH_ASM_NORMALS, kn.n_waves, &kn, sizeof(kn));
+                }
+                else if (R.asm_normals) {
                     // (lists 0 and 1 of k_classify3d hold every footprint whose leaves need <= 32 registers - the assembly interpreter's file:
                     // k_hits3d turns them into the list of leaves that own a hit, the normals kernel takes one leaf per wave pass)
                     const uint32_t hb = std::min<uint32_t>(R.n_footprints, (uint32_t)ctx->n_cu * 64);
@@ -1289,8 +1312,9 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
                 // 71 us.  By columns it is 16 384 waves, each with its column's 64 entries in one load.  Leaves of a column are then
                 // taken one after the other by one wave, front to back, which is wrong for frames with a leaf in most layers (the
                 // launch would last as long as its fullest column: measured in round 3, bear.vm 2.40 -> 4.07 ms): option column_walk
-                // 1 = only where the tapes guarantee sparse columns, 0 never, 2 always (tests).
-                const bool by_columns = ctx->opt.column_walk == 2 || (ctx->opt.column_walk == 1 && R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3));
+                // 1 = only where the tapes guarantee sparse columns - and then by the list of leaves, `by_list` above -, 3 = the same frames
+                // by the table (parity runs), 0 never, 2 always (tests).
+                const bool by_columns = ctx->opt.column_walk == 2 || ((ctx->opt.column_walk == 1 || ctx->opt.column_walk == 3) && sparse_columns);
                 const uint32_t layers = P.slab / 8;
                 // (the slab context's leaf table, as k_fork_state lays the contexts out: the kernel takes it - with the table's shape - from its
                 // kernarg, so that a wave whose part of the table is empty leaves after one dependent load)
@@ -1305,6 +1329,13 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
                 // 2 / 3: 1.24 / 0.97 / 1.09 / 1.33; prospero.vm's 22-op leaves on the general path: 0.433 / 0.424 ms per launch by g = 1 / 2)
                 const uint32_t g_opt = (uint32_t)std::min(std::max(ctx->opt.column_group, 0), 6);
                 const uint32_t g = by_columns ? 6u : (R.smooth_tape && g_opt > 1 ? g_opt - 1 : g_opt);
+                if (by_list) {      // (flags bit 21: table = the slab context's FhLeaf records, nfpl = their capacity, pad[0] = the launch's waves)
+                    const void* const slab_leaves = sk == 0 ? (const void*)R.S.leaves : (const void*)((const FhLeaf*)ctx->leaves_b.p + (size_t)(sk - 1) * R.S.leaf_cap);
+                    struct { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; } ka =
+                        {dS, 0u, R.col_slots, R.col_depmask, R.col_flags | (3u << 20) | (6u << 24), {list_waves, 0}, slab_leaves, R.S.leaf_cap, layers};
+                    (void)launch_asm(ctx, R.asm_points_t ? FH_ASM_COLUMNS_T : FH_ASM_COLUMNS, list_waves, &ka, sizeof(ka), 0, 1, leaf_stream);
+                    return;
+                }
                 if ((by_columns && layers <= 64) || (!by_columns && g > 0)) {
                     struct { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; } ka =
                         {dS, 0u, R.col_slots, R.col_depmask, R.col_flags | (1u << 20) | (g << 24), {0, 0}, slab_table, R.n_footprints, layers};

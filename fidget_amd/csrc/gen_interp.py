@@ -1444,7 +1444,7 @@ def _gen_columns_body(a, variants, off, kname, trans):
 	s_bfe_i32 {S_SLOTY}, s49, 0x80008
 	s_bfe_i32 {S_SLOTZ}, s49, 0x80010
 	s_mov_b32 {S_DEPMASK}, s50
-	s_and_b32 s51, s51, 0x0f1f0000                   ; flags bit 16: projective; 17 .. 19: x / y / z of the model changes along a pixel column; 20: column mode; 24 .. 27: log2 of the layers a wave of column mode takes (bit 28, set here: the lane's pixel state is valid)
+	s_and_b32 s51, s51, 0x0f3f0000                   ; flags bit 16: projective; 17 .. 19: x / y / z of the model changes along a pixel column; 20: column mode; 21: ... by the list of leaves; 24 .. 27: log2 of the layers a wave of column mode takes (bit 28, set here: the lane's pixel state is valid)
 	s_or_b32 {S_WGY}, {S_WGY}, s51
 	; ({S_DEPMASK}, from the kernarg: the input slots whose value changes along a pixel column - the axis' matrix row has a z
 	; coefficient, or the matrix is projective.  A leaf tape that reads none of them has ONE value per pixel for its 8
@@ -1538,6 +1538,8 @@ def _gen_columns_body(a, variants, off, kname, trans):
 	; nearly empty, and the (blocks, layers) grid above is 16 x as many workgroups that find nothing: 66 of the launch's 71 us
 	; at 1024^3.  Workgroup ids go round the 8 XCDs: id = 64 q + 8 a + b runs on XCD b and takes footprint 64 q + 8 b + a, so that
 	; the eight footprints whose entries share a 128-byte line of a layer's row are read through one L2.
+	s_bitcmp1_b32 {S_WGY}, 21
+	s_cbranch_scc1 .Lfh_columns_list
 	s_and_b32 {S_T0}, {S_I}, 7
 	s_lshr_b32 {S_T1}, {S_I}, 6
 	s_add_u32 {S_T0}, {S_T0}, {S_T1}                  ; (the XCD's eight footprints move one place per group of 64: a fixed place would
@@ -1590,6 +1592,7 @@ def _gen_columns_body(a, variants, off, kname, trans):
 	s_lshr_b32 {S_RC}, {S_T0}, 24
 	s_and_b32 {S_FX}, {S_T1}, 0xffff
 	s_lshr_b32 {S_FY}, {S_T1}, 16
+.Lfh_columns_haveleaf:
 	s_cmp_gt_u32 {S_RC}, {its[-1].nr}                          ; needs the LDS register file: left to k_leaves3d<2> (never requested ahead)
 	s_cbranch_scc1 .Lfh_columns_leaf
 	s_lshl_b64 {S_TBASE}, {S_TBASE}, 3
@@ -1866,12 +1869,45 @@ def _gen_columns_body(a, variants, off, kname, trans):
 	s_waitcnt vmcnt(0) lgkmcnt(0)                   ; (the next leaf's tape may be on its way)
 .Lfh_columns_blockend:
 	s_bitcmp1_b32 {S_WGY}, 28
-	s_cbranch_scc0 .Lfh_columns_block
+	s_cbranch_scc0 .Lfh_columns_blocknext
 	v_cmp_ne_u32 vcc, 0, {V_HIT}
 	s_and_saveexec_b64 {S_SAVE}, vcc
 	global_atomic_umax_x2 {V_PIX}, v[4:5], {S_ZBUF}
 	s_mov_b64 exec, {S_SAVE}
-	s_branch .Lfh_columns_block
+.Lfh_columns_blocknext:
+	s_bitcmp1_b32 {S_WGY}, 21
+	s_cbranch_scc0 .Lfh_columns_block
+	s_bitset0_b32 {S_WGY}, 28                         ; list mode: the wave's next leaf is another footprint
+	s_add_u32 {S_I}, {S_I}, {S_RCP}
+.Lfh_columns_list:
+	; ---- list mode (flags bit 21 beside bit 20: frames whose columns hold at most one leaf per slab): no table - the kernarg's table
+	; pointer is the slab's FhLeaf records, its footprints-per-layer word their capacity, its reciprocal word the number of waves.
+	; Wave i takes leaf i, i + waves, ...: the record (clamped to the array) and the leaf count are requested together, one wait,
+	; and a wave without a leaf leaves before any pixel set-up.  One leaf is one "column": set-up, hits and their one atomic as above.
+	s_sub_u32 {S_T0}, {S_NFPL}, 1
+	s_min_u32 {S_T0}, {S_T0}, {S_I}
+	s_mul_hi_u32 {S_T1}, {S_T0}, {o['sizeof_leaf']}
+	s_mul_i32 {S_T0}, {S_T0}, {o['sizeof_leaf']}
+	s_add_u32 s86, s34, {S_T0}
+	s_addc_u32 s87, s35, {S_T1}
+	s_load_dword s90, {S_STATE}, {o['n_leaves']}
+	s_load_dwordx4 s[92:95], {S_PC}, 0x0                 ; FhLeaf: tape offset, length, registers | choices << 16, corner x
+	s_load_dwordx2 s[96:97], {S_PC}, 0x10                ; corner y, z
+	s_mov_b64 {S_LAYMASK}, 0
+	s_mov_b32 {S_NXTV}, 0
+	s_waitcnt lgkmcnt(0)                            ; (the state's words of the prologue too)
+	s_min_u32 s90, s90, {S_NFPL}
+	s_cmp_ge_u32 {S_I}, s90
+	s_cbranch_scc1 .Lfh_columns_exit
+	s_add_u32 {S_ID}, {S_I}, 1
+	s_mov_b32 s84, s92
+	s_mov_b32 s85, 0
+	s_mov_b32 {S_LEN0}, s93
+	s_and_b32 {S_RC}, s94, 0xffff
+	s_mov_b32 {S_FX}, s95
+	s_mov_b32 {S_FY}, s96
+	s_mov_b32 {S_LZ}, s97
+	s_branch .Lfh_columns_haveleaf
 .Lfh_columns_exit:""")
     kernel_footer(a, kname, 48, nvg, 102, True, wg_y=True)
     a(f"\t.p2align 8\n.L{kname}_lut:")

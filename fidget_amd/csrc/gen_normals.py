@@ -19,8 +19,12 @@ of all the leaves among its pixels one after the other: a launch lasted as long 
 Tapes with a modulo keep the C++ kernel (its gradient needs div_euclid); fh_normals_t has the transcendental, rng and atan2 handlers.
 
 kernarg: { FhRenderState* S; u32 n_waves (a multiple of 64); u32 axis slots x | y << 8 | z << 16 (0xFF: none); u32 z_lo; u32 z_hi;
-           u32 entries per list of k_hits3d; u32 pad }
+           u32 entries per list of k_hits3d; u32 mode }
          - this launch's hits are those with z_lo < depth <= z_hi.
+
+Mode bit 0 (frames whose leaf stage is driven by the slab's `leaves`, render_state.h leaf_list: at most one leaf per pixel column, so the
+leaf that owns a pixel's hit is the column's leaf or nobody): no list of k_hits3d - wave pass i takes leaf i, i + n_waves, ... of the slab
+and finds out from the z-buffer words whether it has a hit, as above; a leaf of more registers than the file holds is skipped.
 """
 from gen_interp import (Interp, OPS, FILE, S_KERNARG, S_STATE, S_MAT, S_SIGN, S_ABSM, S_ARENA, S_TAPE, S_LEN, S_W1, S_T0, S_OUT, S_A, S_T1, S_PC, S_SAVE,
                         S_M, S_RET, V_LANE, V_QNAN, V_SQRTC, VT, VU, VW, VD, SRC0, SRC1, DST, kernel_header, kernel_footer, common_consts,
@@ -35,6 +39,7 @@ S_ZLO, S_ZHI = "s26", "s27"
 S_NORMALS, S_LEAVES, S_ZBUF, S_FPLIST = "s[32:33]", "s[34:35]", "s[36:37]", "s[38:39]"
 S_TODO = "s[80:81]"
 S_CUR = "s78"
+S_MODE = "s41"          # kernarg word 7: bit 0 = by the slab's leaves (no hit lists)
 V_PIX, V_ID, V_DEPTH, V_NOFF = "v1", "v2", "v3", "v4"       # byte offset of the pixel's z-buffer word, its two halves, byte offset of its normal
 V_PX, V_PY, V_PZ = "v5", "v6", "v7"
 VRES = ["v10", "v11", "v12", "v13"]
@@ -359,6 +364,7 @@ def gen_normals(a, off, trans=None):
 	s_load_dwordx2 {S_STATE}, {S_KERNARG}, 0x0
 	s_load_dwordx4 s[48:51], {S_KERNARG}, 0x8
 	s_load_dword s52, {S_KERNARG}, 0x18
+	s_load_dword {S_MODE}, {S_KERNARG}, 0x1c
 	s_mov_b32 {S_WI}, s2""")
     common_consts(a)
     handler_base(a, it)
@@ -378,6 +384,8 @@ def gen_normals(a, off, trans=None):
 	s_mov_b32 {S_ZLO}, s50
 	s_mov_b32 {S_ZHI}, s51
 	s_waitcnt lgkmcnt(0)
+	s_bitcmp1_b32 {S_MODE}, 0
+	s_cbranch_scc1 .L{name}_byleaves
 	s_and_b32 {S_T0}, {S_WI}, 63
 	s_lshr_b32 {S_WI}, {S_WI}, 6
 	s_lshl_b32 {S_T1}, {S_T0}, 8                    ; the list's counter: FH_HIT_STRIDE words apart
@@ -395,6 +403,8 @@ def gen_normals(a, off, trans=None):
 	; ---- next leaf of the list (k_hits3d: the slab's leaves that own a hit): static round robin over the waves --------------------
 	s_cmp_ge_u32 {S_WI}, {S_NFP}
 	s_cbranch_scc1 .L{name}_exit
+	s_bitcmp1_b32 {S_MODE}, 0
+	s_cbranch_scc1 .L{name}_nextleaf
 	s_lshl_b32 {S_T0}, {S_WI}, 2
 	s_add_u32 {S_WI}, {S_WI}, {S_NWG}
 	s_add_u32 s86, s38, {S_T0}
@@ -403,6 +413,7 @@ def gen_normals(a, off, trans=None):
 	v_and_b32 {V_PX}, 7, {V_LANE}
 	v_lshrrev_b32 {V_PY}, 3, {V_LANE}
 	s_waitcnt lgkmcnt(0)
+.L{name}_leaf:
 	s_sub_u32 {S_T0}, {S_CUR}, 1
 	s_mul_hi_u32 {S_T1}, {S_T0}, {o['sizeof_leaf']}
 	s_mul_i32 {S_T0}, {S_T0}, {o['sizeof_leaf']}
@@ -411,6 +422,9 @@ def gen_normals(a, off, trans=None):
 	s_load_dwordx4 s[48:51], {S_PC}, 0x0                 ; FhLeaf: tape offset, length, registers | choices, corner x  (the interpreter's
 	s_load_dword s52, {S_PC}, 0x10                       ; corner y                                       op batches: free between two tapes)
 	s_waitcnt lgkmcnt(0)
+	s_and_b32 {S_T0}, s50, 0xffff                        ; (by leaves: nobody sorted out the tapes of more registers than the file - k_normals3d<big>'s)
+	s_cmp_gt_u32 {S_T0}, {NR}
+	s_cbranch_scc1 .L{name}_next
 	v_add_u32 {V_PX}, s51, {V_PX}
 	v_add_u32 {V_PY}, s52, {V_PY}
 	v_cmp_gt_u32_e64 {S_M[0]}, {S_WIDTH}, {V_PX}
@@ -474,6 +488,19 @@ def gen_normals(a, off, trans=None):
 	global_store_dword {V_PIX}, {V_ID}, {S_ZBUF}
 	s_mov_b64 exec, {S_SAVE}
 	s_branch .L{name}_next
+.L{name}_byleaves:
+	; ---- mode bit 0: the slab's leaves themselves, wave pass i = leaf i ---------------------------------------------------------------
+	s_mov_b32 {S_NWG}, s48
+	s_load_dwordx2 s[86:87], {S_STATE}, {o['leaf_cap']}  ; leaf_cap, n_leaves
+	s_waitcnt lgkmcnt(0)
+	s_min_u32 {S_NFP}, s86, s87
+	s_branch .L{name}_next
+.L{name}_nextleaf:
+	s_add_u32 {S_CUR}, {S_WI}, 1
+	s_add_u32 {S_WI}, {S_WI}, {S_NWG}
+	v_and_b32 {V_PX}, 7, {V_LANE}
+	v_lshrrev_b32 {V_PY}, 3, {V_LANE}
+	s_branch .L{name}_leaf
 .L{name}_exit:
 	s_waitcnt vmcnt(0)""")
     kernel_footer(a, name, 32, nvg, 102, True)

@@ -1109,7 +1109,13 @@ FH_DEV void tpush_body(FhRenderState* S, int level, uint32_t first, uint32_t str
                     S->leaves[lb + slot] = lf;
                     if (child.n_regs > S->norm_asm_regs) S->rare_seen = 1u;
                     if (child.n_regs > S->leaf_asm_regs) atomicAdd(&S->n_leaves_lds, 1u);  // rare: lets k_leaves3d<2> return at once otherwise
-                    if (IS3D)
+                    if (IS3D && S->leaf_list) {      // (render_state.h leaf_list: no table; the one list a later kernel cannot make from `leaves`)
+                        if (child.n_regs > S->norm_asm_regs) {
+                            const uint32_t at = atomicAdd(&S->fp_count[2], 1u);
+                            if (at < ntx * ((P.height + T - 1) / T)) S->fp_list[2][at] = ((cy / T) << 16) | (cx / T);
+                            else atomicAdd(&S->queue_overflow, 1u);
+                        }
+                    } else if (IS3D)
                         S->leaf_table[(size_t)((iz % P.slab) / T) * (ntx * ((P.height + T - 1) / T)) + (size_t)(cy / T) * ntx + cx / T] =
                             FhLeafRef{lb + slot + 1, child.off, child.len | (min((uint32_t)child.n_regs, 255u) << 24), cx | (cy << 16)};  // [layer][footprint]
                 } else if (amb) atomicAdd(&S->queue_overflow, 1u);
@@ -1746,6 +1752,9 @@ __global__ void k_finish3d(FhRenderState* S, FhGeometryPixel* out, uint32_t n_ct
             uint32_t r = 0;
             for (uint32_t k = 0; k < n_ctx; k++) r |= S[k].rare_seen;
             host_flags[2] = r;      // the frame met a large tape: the next frames launch the kernels for them on their own again (capi_render.hpp rare mode)
+            uint32_t nl = 0;
+            for (uint32_t k = 0; k < n_ctx; k++) nl = max(nl, S[k].n_leaves);
+            host_flags[3] = nl;     // the leaves of a slab (the last one each context took): what sizes the next frame's launches by the list of leaves (capi_render.hpp by_list)
         }
     }
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {

@@ -135,6 +135,10 @@ struct FhRenderState {
     FhLeafRef* leaf_table;  // 3D: [layer][footprint] -> leaf id + 1 and what the leaf kernel needs of the leaf (layer = 8-voxel layer of the slab)
     uint32_t slab_z;        // 3D: z of the current slab's first voxel (a leaf's z = slab_z + 8 * layer)
     uint32_t frame_stamp;   // a number no other frame of this context has: what the linked prune signs the links it leaves in the arena with (prune2.hip)
+    // 3D: the slab's leaf stage is driven by `leaves` itself (capi_render.hpp by_list: frames whose tapes guarantee sparse columns) - wave i of the
+    // leaf kernel and of the normals kernel takes leaf i; the push writes no leaf table (nobody reads or clears it) and puts the footprint of a
+    // leaf beyond norm_asm_regs on fp_list[2] itself, which is all that is left of k_classify3d's work in such a frame
+    uint32_t leaf_list, pad_leaf_list;
     // 3D: footprints that own leaves this slab, by register-file class (<=16, <=32, LDS)
     uint32_t* fp_list[3];
     uint32_t fp_count[3], fp_cursor[3];
