@@ -26,6 +26,7 @@
 #include "prune2.hip"
 #include "solve.hip"
 #include "host_mesh.hpp"
+#include "frame_schedule.hpp"
 
 #define FH_LDS_MAX 163840  // 160 KiB per workgroup on gfx950
 

@@ -68,8 +68,6 @@ extern "C" const char fh_interp_co[];
 enum { FH_ASM_COLUMNS = 0, FH_ASM_FLOAT_16x4, FH_ASM_FLOAT_32x2, FH_ASM_TILES, FH_ASM_PRUNE1, FH_ASM_TILES_V32, FH_ASM_TILES_V64, FH_ASM_PROBE, FH_ASM_UBENCH, FH_ASM_COLUMNS_T, FH_ASM_NORMALS, FH_ASM_NORMALS_T, FH_ASM_TILES_T, FH_ASM_TILES_V32_T, FH_ASM_TILES_V64_T, FH_ASM_FLOAT_16x4_T, FH_ASM_FLOAT_32x2_T, FH_ASM_TRANS_PROBE, FH_ASM_COUNT };
 static const char* const FH_ASM_NAMES[FH_ASM_COUNT] = {"fh_columns", "fh_float_eval_16x4", "fh_float_eval_32x2", "fh_tiles", "fh_prune1",
                                                        "fh_tiles_v32", "fh_tiles_v64", "fh_probe", "fh_ubench", "fh_columns_t", "fh_normals", "fh_normals_t", "fh_tiles_t", "fh_tiles_v32_t", "fh_tiles_v64_t", "fh_float_eval_16x4_t", "fh_float_eval_32x2_t", "fh_trans_probe"};
-// register-file shapes of the VGPR tile kernels (gen_tilesv.py): registers, choices
-static const uint32_t V32_REGS = 32, V32_CHOICES = 256, V64_REGS = 64, V64_CHOICES = 512;
 
 // Behaviour switches of a context - diagnostics and tuning, none is needed in normal use.  They are part of the context, not of
 // the process: read ONCE from the environment when the context is created (FHIP_<NAME IN CAPITALS>, for runs of unmodified
@@ -145,7 +143,6 @@ struct fhip_ctx : FrameBufs {
     uint32_t pre_turn = 0;              // ... frames whose root levels alternate between it and the tail stream: whose turn
     hipEvent_t ev_rest_fork = nullptr, ev_rest_join = nullptr;
     hipEvent_t ev_pre = nullptr, ev_l0 = nullptr, ev_l1 = nullptr;
-    hipStream_t post_v64_stream = nullptr;   // launch_tiles_split: where the launches behind level 1's fh_tiles_v64 go (side_only_l1), or null
     hipModule_t asm_mod = nullptr;
     hipFunction_t asm_fn[FH_ASM_COUNT] = {};
     bool use_asm = true;  // FHIP_NO_ASM=1 keeps everything on the C++ kernels (diagnostics)
@@ -159,7 +156,7 @@ struct fhip_ctx : FrameBufs {
     FhRenderState last_state_b;
     uint32_t slab_contexts = 4;   // FHIP_SLAB_CONTEXTS (2 .. 4): how far the tile chain may run ahead of the leaf chain (measured: 2.03 / 1.60 / 1.55 ms per frame with 2 / 3 / 4)
     int device = 0;
-    hipStream_t stream = nullptr;
+    hipStream_t stream = nullptr;   // the caller's stream, from fhip_ctx_create to fhip_ctx_destroy: a render never assigns it (every launch helper takes its stream)
     int n_cu = 256;
     std::string err;
     bool launch_failed = false;     // an assembly kernel launch of the current frame failed (reported when the frame has been queued)
@@ -209,9 +206,7 @@ struct fhip_ctx : FrameBufs {
     uint32_t lane_next = 0;
     // Rare mode of a 3D frame (capi_render.hpp): the launches that exist for tapes too large for the assembly kernels' register files - three or
     // four per slab, empty in nearly every frame - folded into launches the slab makes anyway; taken while the last finished frame met no such tape
-    bool rare_now = false;            // ... this frame
-    uint32_t rare_stride = 0;         // bytes of a rare block's register file in rare_scratch
-    uint64_t rare_frames = 0;         // frames rendered that way so far (fhip_debug_rare_frames)
+    uint64_t rare_frames = 0;         // ... frames rendered that way so far (fhip_debug_rare_frames)
     uint64_t lane_frames = 0;         // frames that went to a lane so far (fhip_debug_lane_frames)
     uint64_t lane_frames_wanted = 0;  // ... not counting the tuner's measuring windows
     hipEvent_t ev_last = nullptr;     // the end of the last 3D frame on the caller's stream ("is the frame before still under way?")
@@ -268,14 +263,14 @@ static fhip_status fail(fhip_ctx* ctx, fhip_status s, const std::string& msg) {
     } while (0)
 
 template <class F>
-static void launch(fhip_ctx* ctx, int klass, F&& f) {
+static void launch(fhip_ctx* ctx, hipStream_t st, int klass, F&& f) {
     if (ctx->profiling) {
         hipEvent_t a, b;
         (void)hipEventCreate(&a);
         (void)hipEventCreate(&b);
-        (void)hipEventRecord(a, ctx->stream);
+        (void)hipEventRecord(a, st);
         f();
-        (void)hipEventRecord(b, ctx->stream);
+        (void)hipEventRecord(b, st);
         ctx->prof_events.push_back({klass, {a, b}});
     } else {
         f();

@@ -98,7 +98,7 @@ uint32_t fhip_debug_groups(fhip_ctx* ctx, int kind, uint32_t index, void* out, u
 fhip_status fhip_debug_probe(fhip_ctx* ctx, float* out) {
     HIP_TRY(ctx, ctx->io_a.ensure(16 * 256));
     struct { void* p; } ka = {ctx->io_a.p};
-    if (launch_asm(ctx, FH_ASM_PROBE, 1, &ka, sizeof(ka)) != hipSuccess) return FHIP_ERR_HIP;
+    if (launch_asm(ctx, ctx->stream, FH_ASM_PROBE, 1, &ka, sizeof(ka)) != hipSuccess) return FHIP_ERR_HIP;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, ctx->io_a.p, 16 * 256, hipMemcpyDeviceToHost));
     return FHIP_OK;
@@ -110,7 +110,7 @@ fhip_status fhip_debug_ubench(fhip_ctx* ctx, uint32_t test, uint32_t iters, uint
     HIP_TRY(ctx, ctx->io_a.ensure((size_t)n_waves * 4));
     HIP_TRY(ctx, hipMemsetAsync(ctx->io_a.p, 0, (size_t)n_waves * 4, ctx->stream));
     struct { void* p; uint32_t test, iters; } ka = {ctx->io_a.p, test, iters};
-    if (launch_asm(ctx, FH_ASM_UBENCH, n_waves, &ka, sizeof(ka), 64) != hipSuccess) return FHIP_ERR_HIP;
+    if (launch_asm(ctx, ctx->stream, FH_ASM_UBENCH, n_waves, &ka, sizeof(ka), 64) != hipSuccess) return FHIP_ERR_HIP;
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     HIP_TRY(ctx, hipMemcpy(out, ctx->io_a.p, (size_t)n_waves * 4, hipMemcpyDeviceToHost));
     return FHIP_OK;
@@ -146,7 +146,7 @@ fhip_status fhip_debug_trans_probe(fhip_ctx* ctx, uint32_t copy, uint32_t fn, ui
     HIP_TRY(ctx, hipMemsetAsync(ctx->io_a.p, 0x5A, n * 4, ctx->stream));
     HIP_TRY(ctx, hipMemsetAsync(ctx->io_b.p, 0, 64, ctx->stream));
     struct { void* out; uint32_t first, copy, fn, pad; } ka = {ctx->io_a.p, first, copy, fn, 0};
-    if (launch_asm(ctx, FH_ASM_TRANS_PROBE, (uint32_t)(n / 256), &ka, sizeof(ka)) != hipSuccess) return FHIP_ERR_HIP;
+    if (launch_asm(ctx, ctx->stream, FH_ASM_TRANS_PROBE, (uint32_t)(n / 256), &ka, sizeof(ka)) != hipSuccess) return FHIP_ERR_HIP;
     hipLaunchKernelGGL(k_trans_compare, dim3(ctx->n_cu * 16), dim3(256), 0, ctx->stream, (int)fn, first, (size_t)n, (const uint32_t*)ctx->io_a.p,
                        (unsigned long long*)ctx->io_b.p);
     HIP_TRY(ctx, hipGetLastError());

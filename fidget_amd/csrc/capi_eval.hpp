@@ -93,7 +93,7 @@ static fhip_status bulk_eval(fhip_ctx* ctx, const fhip_tape* tape, const float* 
         struct { const uint64_t* tape; const float* vars; float* out; uint32_t len, n; } ka = {
             tape->d_ops, (const float*)ctx->io_a.p, (float*)ctx->io_b.p, (uint32_t)t.ops.size(), n};
         const uint32_t per = nr <= 16 ? 256 : 128;
-        HIP_TRY(ctx, launch_asm(ctx, nr <= 16 ? (plain ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T), (n + per - 1) / per, &ka,
+        HIP_TRY(ctx, launch_asm(ctx, ctx->stream, nr <= 16 ? (plain ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T), (n + per - 1) / per, &ka,
                                 sizeof(ka)));
     } else if (comp == 1) {
         if (g) hipLaunchKernelGGL(k_eval_f32<true>, dim3(grid), dim3(WAVE), 0, ctx->stream, tape->d_ops, (uint32_t)t.ops.size(),

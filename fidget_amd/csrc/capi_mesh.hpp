@@ -644,7 +644,7 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
                 const bool plain_c = tape_asm_ok(t);
                 const uint32_t per_c = P.n_regs <= 16 ? 256 : 128;
                 const int which_c = P.n_regs <= 16 ? (plain_c ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain_c ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T);
-                ck(launch_asm(ctx, which_c, (np + per_c - 1) / per_c, &kc, sizeof(kc)));
+                ck(launch_asm(ctx, ctx->stream, which_c, (np + per_c - 1) / per_c, &kc, sizeof(kc)));
                 hipLaunchKernelGGL(fhm::k_mesh_corner_masks, dim3((cnt + 7) / 8), dim3(WAVE), 0, ctx->stream, cells, cnt, (const float*)edge_vals.p, (const FhMdcTable*)table.p, recs,
                                    (uint32_t*)edge_count.p, (uint32_t*)edge_list.p);
                 ck(hipGetLastError());
@@ -679,7 +679,7 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
                     hipLaunchKernelGGL(fhm::k_mesh_edge_points, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, P, (const FhMeshLeaf*)recs, (const uint32_t*)edge_list.p,
                                        (const fhmesh::EdgeBracket*)edge_br.p, n_edges, (float*)edge_vars.p, n);
                     ck(hipGetLastError());
-                    ck(launch_asm(ctx, which, (n + per - 1) / per, &ka, sizeof(ka)));
+                    ck(launch_asm(ctx, ctx->stream, which, (n + per - 1) / per, &ka, sizeof(ka)));
                     hipLaunchKernelGGL(fhm::k_mesh_edge_narrow, dim3((n_edges + 255) / 256), dim3(256), 0, ctx->stream, (fhmesh::EdgeBracket*)edge_br.p, (const float*)edge_vals.p, n_edges);
                     ck(hipGetLastError());
                 }

@@ -1,57 +1,8 @@
 // Fragment of capi.hip (the 2D / 3D tile renderers: frame set-up, the coarse levels, slabs, streams and frame pipelining); not a stand-alone header: included by capi.hip only.
 // ---- renders ---------------------------------------------------------------------------
 static const uint32_t VM_TILES_2D[] = {128, 32, 8};        // fidget-core/src/vm/mod.rs:255-257
-static const uint32_t VM_TILES_3D[] = {128, 64, 32, 16, 8};  // fidget-core/src/vm/mod.rs:251-253
-// RenderHints of the HIP shape (the reference lets every shape type pick its own, shape.rs RenderHints):
-// a fan-out of 4^3 = 64 children fills a wavefront
-// (128 -> 32 -> 8).  The root tile stays the one the reference's VmShape hints give for the image
-// size, so that exactly the same voxels are covered (a root tile overhanging the image in z is
-// evaluated there by the reference too).
-
 static const uint32_t FH_LEAF_REGS = 40, FH_LEAF_REGS_T = 44;      // (gen_interp.py main(): fh_columns' 40 x 2 shape, fh_columns_t's 44 x 4)
 static const uint32_t FH_NORMAL_REGS = 40;                         // (gen_normals.py NR)
-struct RenderSetup {
-    FhRenderState S;
-    std::vector<FhGroup> roots;
-    uint32_t n_slabs = 1, n_layers = 1;      // z-slabs (steps of the per-slab chains), root-tile layers
-    uint32_t slab_lo = 0, slab_hi = 1;   // z-slabs this render covers (all of them unless the volume is split in z: octant shards)
-    size_t lds_tiles_mid = 0, lds_tiles_big = 0, lds_tiles_small = 0, lds_points_big = 0, lds_normals_big = 0, lds_normals_small = 0;
-    uint32_t table_words = 0, n_footprints = 0, groups_per_slab = 0;
-    bool smooth_tape = false;      // the root tape has a choice in fewer than every tenth op (and more than 200 ops): a blend whose leaves stay long
-    uint32_t hit_bucket_cap = 0;   // the normals kernel's work lists (k_hits3d): entries per bucket, words of the whole thing per slab context
-    size_t hit_words = 0;
-    size_t mind_words = 0;      // words of the min-depth pyramid (cleared at the head of the frame)
-    uint32_t tl = 16;  // sibling tiles per wave in the tile kernel (16 or 64)
-    bool full = false;  // tape uses transcendental / modulo ops -> FULL kernel variants
-    bool asm_points = false;  // leaf stage on the assembly interpreters
-    bool asm_points_t = false;  // ... on fh_columns_t (tapes with transcendental / modulo / rng opcodes)
-    bool asm_normals = false;   // normals by the assembly gradient interpreter fh_normals (gen_normals.py): footprints of leaves of <= 32 registers
-    bool split = false;       // 3D tile stage as setup / evaluate+prune / push kernels
-    bool asm_tiles = false;   // ... with the evaluate+prune step in assembly (fh_tiles)
-    bool asm_tiles_t = false; // ... by the *_t variants (transcendental opcodes)
-    uint32_t group_regs = 0, group_choices = 0;  // bounds over the tape's groups
-    size_t lds_tiles_group = 0;
-    bool groups = false;      // ... and level 0 evaluated as the tape's independent groups (tape parallelism)
-    bool prune1 = false;      // ... and, on the first exp_levels levels, the prune as one wave per child (fh_prune1)
-    bool prune2 = false;      // ... by the linked prune (prune2.hip k_prune2: visits only the ops a child keeps) where the tape qualifies
-    const uint64_t* d_links = nullptr;
-    const uint64_t* d_ctab = nullptr;
-    size_t lds_prune2 = 0;
-    uint32_t n_chain = 0;          // ops of the root chain (their table lies behind d_ctab's t.n_choices entries)
-    uint32_t p2_cap_kept = 0;      // kept ops per child the linked prune's LDS areas are sized for (children beyond: the scalar sweep behind it)
-    uint32_t exp_levels = 0;
-    uint32_t col_slots = 0, col_depmask = 0, col_flags = 0;   // 3D: axis slots x | y << 8 | z << 16 (0xFF none), inputs varying along a pixel column, bit 16 projective
-    bool zrep = false;        // ... column-invariant parents are evaluated for one z-layer only (k_tape_flags)
-    bool xy_fixed = false, root_invariant = false;   // 3D, set before prepare(): x and y do not move along a pixel column; the ROOT tape reads nothing that does
-    bool one_level_64 = false;   // 2D, a one-level list: root groups of 64 tiles through the split tile stage (render2d_frame's small-image passes)
-    bool classify_only = false;  // ... and the pass that only classifies its tiles and writes their fills (no prune, no leaves)
-    bool root_zrep = false;   // ... then the root level evaluates ONE layer of root tiles per z-slab and hands the result to the layers stacked on it
-    bool front_only = false;  // ... and only the front slab is rendered (slab_stop = slab_hi - 1)
-    bool alt_pre = false;     // ... and consecutive frames' root levels take the pre-pass and the tail stream in turn (render3d_frame)
-    uint32_t slab_stop = 0;   // the slabs rendered: slab_hi - 1 down to slab_stop (= slab_lo unless front_only)
-    bool big_hbm = false;     // the root-sized register files live in HBM (S.gscratch): hbm_waves workgroups per root-sized launch
-    uint32_t hbm_waves = 0;
-};
 
 static fhip_status bind_inputs(fhip_ctx* ctx, const fhip_tape* tape, const int32_t* axis_slots, const uint64_t* keys,
                                const float* vals, uint32_t n, FhRender& P) {
@@ -70,21 +21,6 @@ static fhip_status bind_inputs(fhip_ctx* ctx, const fhip_tape* tape, const int32
     for (uint32_t s = 0; s < t.n_vars; s++)
         if (!bound[s]) return fail(ctx, FHIP_ERR_MISSING_VAR, "a variable of the shape has no value");
     return FHIP_OK;
-}
-
-// fidget-raster/src/lib.rs:59-66
-static std::vector<uint32_t> trim_tiles(const uint32_t* tiles, uint32_t n, uint32_t max_size) {
-    uint32_t i = n;
-    for (uint32_t k = 0; k < n; k++) if (tiles[k] < max_size) { i = k; break; }
-    i = i ? i - 1 : 0;
-    return std::vector<uint32_t>(tiles + i, tiles + n);
-}
-
-static std::vector<uint32_t> hip_tiles_3d(uint32_t max_size) {
-    std::vector<uint32_t> v = trim_tiles(VM_TILES_3D, 5, max_size);
-    std::vector<uint32_t> out{v[0]};
-    for (uint32_t t = v[0]; t > 8;) { t = std::max<uint32_t>(t / 4, 8); out.push_back(t); }
-    return out;
 }
 
 // 2D hint of the HIP shape: 128 -> 16 with 16 x 16 pixel leaves - what fidget-jit uses (fidget-jit/src/lib.rs:984-986); a fan-out
@@ -155,6 +91,7 @@ static void column_setup(fhip_ctx* ctx, const fhip_tape* tape, const FhRender& P
         }
         R.root_invariant = (reads & R.col_depmask & 0x7FFFFFFFu) == 0;
     }
+    R.column_inv = R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
 }
 
 // A frame before this one ran out of tape arena (k_finish3d / k_latch_arena said so in the pinned host word): wait for what is in flight
@@ -165,7 +102,7 @@ static void column_setup(fhip_ctx* ctx, const fhip_tape* tape, const FhRender& P
 static hipError_t sync_own_streams(fhip_ctx* ctx) {
     hipError_t e = hipSuccess;
     for (hipStream_t s : {ctx->stream, ctx->stream2, ctx->stream3, ctx->stream_pre}) {
-        const hipError_t r = hipStreamSynchronize(s);       // (a null ctx->stream is the device's default stream: the caller chose it)
+        const hipError_t r = hipStreamSynchronize(s);       // (ctx->stream is the caller's stream at all times - no render assigns it -, so the caller's stream is waited for too; null: the device's default stream, the caller chose it)
         if (r != hipSuccess && e == hipSuccess) e = r;
     }
     for (fhip_ctx* L : ctx->lanes)
@@ -305,7 +242,7 @@ static fhip_status prepare(fhip_ctx* ctx, const fhip_tape* tape, bool is3d, cons
     // column of root tiles.  One layer per z-slab is evaluated (the slab's back-most: FhGroup::x = how many layers of the slab it stands
     // for) and the push stage hands the result to the stack - a fill with the nearest copy's depth, ONE queue entry carrying the copies,
     // exactly what the levels below do for column-invariant parents.  prospero.vm at 1024^3: 64 root tiles instead of 512.
-    R.root_zrep = is3d && S.pre_levels > 0 && ctx->use_split && TL == 64 && R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
+    R.root_zrep = is3d && S.pre_levels > 0 && ctx->use_split && TL == 64 && R.column_inv;
     // ... and of such a frame ONLY THE FRONT SLAB is rendered at all.  Nothing the frame evaluates depends on z: every tile, every leaf of
     // a slab further back repeats the front slab's result for its column with a smaller depth - a filled tile is filled in front of it, a
     // leaf's hits are the front leaf's hits, a pixel the front slab left empty is outside the model at every z - and the image takes the
@@ -401,7 +338,7 @@ static fhip_status prepare(fhip_ctx* ctx, const fhip_tape* tape, bool is3d, cons
     }
     S.count_big[0] = (uint32_t)R.roots.size();  // the root tape always takes the large LDS layout
     for (size_t l = 0; l < ts.size(); l++) S.qcap[l] = qcaps[l];
-    R.split = ctx->use_split && R.tl == 64 && true;
+    R.split = ctx->use_split && R.tl == 64;
     // (tapes with sin cos tan asin acos atan exp ln: the *_t variants of the tile kernels, which carry those interval handlers;
     // and, since round 5, those for atan2, mod, mix, rand)
     R.asm_tiles_t = !tape_asm_ok(t) && tape_tiles_t_ok(t) && !ctx->opt.no_asm_tiles_t;
@@ -557,7 +494,7 @@ static fhip_status finish_render(fhip_ctx* ctx) {
 }
 
 struct FrameClear { void* p = nullptr; size_t bytes = 0; uint32_t fill = 0; };   // a buffer the frame starts from cleared (bytes: a multiple of 4)
-static fhip_status upload_frame(fhip_ctx* ctx, const fhip_tape* tape, RenderSetup& R, const FrameClear (&clear)[3]) {
+static fhip_status upload_frame(fhip_ctx* ctx, hipStream_t st, const fhip_tape* tape, RenderSetup& R, const FrameClear (&clear)[3]) {
     // The frame's state and root groups go through pinned staging slots (a ring of eight, each guarded by an event): a copy from
     // pageable memory would make the host wait for everything queued on the stream before it, i.e. for the previous frame.
     const size_t roots_bytes = R.roots.size() * sizeof(FhGroup);
@@ -577,10 +514,10 @@ static fhip_status upload_frame(fhip_ctx* ctx, const fhip_tape* tape, RenderSetu
     // again finds them there (17 small copies, 0.1 ms of a 4 ms frame, otherwise).
     if (ctx->resident_serial != tape->serial || ctx->resident_groups != R.S.n_tgroups) {
         ctx->resident_serial = 0;
-        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena.p, tape->t.ops.data(), tape->t.ops.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        HIP_TRY(ctx, hipMemcpyAsync(ctx->arena.p, tape->t.ops.data(), tape->t.ops.size() * 8, hipMemcpyHostToDevice, st));
         for (uint32_t g = 0; g < R.S.n_tgroups; g++)  // the group tapes follow the root tape
             HIP_TRY(ctx, hipMemcpyAsync((uint64_t*)ctx->arena.p + R.S.tgroup[g].off, tape->tgroups[g].ops.data(),
-                                        tape->tgroups[g].ops.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+                                        tape->tgroups[g].ops.size() * 8, hipMemcpyHostToDevice, st));
         ctx->resident_serial = tape->serial;
         ctx->resident_groups = R.S.n_tgroups;
     }
@@ -600,9 +537,9 @@ static fhip_status upload_frame(fhip_ctx* ctx, const fhip_tape* tape, RenderSetu
         if (clear[k].p) most = std::max(most, clear[k].bytes);
     }
     const unsigned blocks = (unsigned)std::max<size_t>(8, std::min<size_t>((size_t)ctx->n_cu * 32, (most + 64 * 64 - 1) / (64 * 64)));
-    FH_KLAUNCH(k_frame_begin, dim3(blocks), dim3(WAVE), 0, ctx->stream, fb);
+    FH_KLAUNCH(k_frame_begin, dim3(blocks), dim3(WAVE), 0, st, fb);
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(sg.ev, ctx->stream));
+    HIP_TRY(ctx, hipEventRecord(sg.ev, st));
     sg.used = true;
     for (auto& e : ctx->prof_events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
     ctx->prof_events.clear();
@@ -615,209 +552,164 @@ static fhip_status upload_frame(fhip_ctx* ctx, const fhip_tape* tape, RenderSetu
 // root-sized variant for the few large tapes (both always launched; empty queues exit at once).
 #define FH_LAUNCH_TILES(IS3D, FULL, BIG, grid, lds)                                                                  \
     do {                                                                                                            \
-        if (R.tl == 64) FH_KLAUNCH((k_tiles<IS3D, FULL, BIG, 64>), dim3(grid), dim3(WAVE), lds, ctx->stream, dS, level); \
-        else FH_KLAUNCH((k_tiles<IS3D, FULL, BIG, 16>), dim3(grid), dim3(WAVE), lds, ctx->stream, dS, level);            \
+        if (R.tl == 64) FH_KLAUNCH((k_tiles<IS3D, FULL, BIG, 64>), dim3(grid), dim3(WAVE), lds, st, dS, level); \
+        else FH_KLAUNCH((k_tiles<IS3D, FULL, BIG, 16>), dim3(grid), dim3(WAVE), lds, st, dS, level);            \
     } while (0)
-// 3D tile stage of one level as three kernels (see kernels.hip "Split 3D tile stage")
-// Rare mode: blocks per folded launch, and where a slab context's blocks keep their register files (a slab context = one FhRenderState of the set)
-static const uint32_t FH_RARE_BLOCKS = 8;
-static char* rare_file(fhip_ctx* ctx, FhRenderState* dS) {
-    if (!ctx->rare_now) return nullptr;
-    return (char*)ctx->rare_scratch.p + (size_t)(dS - (FhRenderState*)ctx->state.p) * FH_RARE_BLOCKS * ctx->rare_stride;
+// Kernarg blocks of the assembly kernels: one struct per layout, each beside the generator function that reads it
+struct KaTiles { FhRenderState* S; uint32_t level, big, max_regs, max_choices, n_waves, flags, skip_regs, skip_choices; };            // gen_tiles.py gen_tiles, gen_tilesv.py gen_tilesv
+struct KaPrune1 { FhRenderState* S; uint32_t level, big, max_choices, mode; };                                                        // gen_prune.py gen_prune1
+struct KaColumns { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; };    // gen_interp.py gen_columns
+struct KaNormals { FhRenderState* S; uint32_t n_waves, slots, z_lo, z_hi, bucket_cap, mode; };                                        // gen_normals.py gen_normals
+
+// The streams of a context by role (frame_schedule.hpp), and the role the host thread is queueing on
+struct FrameStreams { hipStream_t s[N_ROLES]; Role cur; hipStream_t on() const { return s[cur]; } };
+static FrameStreams frame_streams(const fhip_ctx* ctx, Role at = CALLER) { return FrameStreams{{ctx->stream, ctx->stream_pre, ctx->stream2, ctx->stream3}, at}; }
+// The next stage goes to another stream: that stream waits for what has been queued here so far
+static hipError_t hop(FrameStreams& fs, Role to, hipEvent_t ev) {
+    if (to == fs.cur) return hipSuccess;
+    const hipError_t e = hipEventRecord(ev, fs.on());
+    fs.cur = to;
+    return e != hipSuccess ? e : hipStreamWaitEvent(fs.on(), ev, 0);
 }
-static void launch_tiles_split(fhip_ctx* ctx, const RenderSetup& R, FhRenderState* dS, int level, bool is3d) {
+// The facts of a context the schedule is made from (frame_schedule.hpp; the caller adds what it observes)
+static ScheduleInputs schedule_inputs(const fhip_ctx* ctx, int out_is_device) {
+    ScheduleInputs in;
+    in.no_tiles_v = ctx->opt.no_tiles_v; in.no_zrep = ctx->opt.no_zrep; in.column_walk = ctx->opt.column_walk; in.column_group = ctx->opt.column_group;
+    in.frame_pipeline = ctx->frame_pipeline; in.use_pipeline = ctx->use_pipeline; in.profiling = ctx->profiling; in.slab_contexts = ctx->slab_contexts;
+    in.has_side = ctx->stream2 != nullptr; in.has_tail = ctx->stream3 != nullptr; in.has_flags = ctx->host_flags != nullptr; in.out_is_device = out_is_device != 0;
+    return in;
+}
+// Rare mode: where a slab context's blocks keep their register files (a slab context = one FhRenderState of the set)
+static char* rare_file(const fhip_ctx* ctx, const FhRenderState* dS, uint32_t rare_stride) {
+    if (!rare_stride) return nullptr;
+    return (char*)ctx->rare_scratch.p + (size_t)(dS - (const FhRenderState*)ctx->state.p) * FH_RARE_BLOCKS * rare_stride;
+}
+// 3D tile stage of one level as three kernels (see kernels.hip "Split 3D tile stage"): set-up, evaluate + prune - one of the three below,
+// LevelPlan::path -, push
+// Tape parallelism: the root tree's terms by independent groups, one wave per (block of root
+// tiles, group) -> the tree over the terms (result, marks, arena) -> the root tape's choice words
+// gathered from both -> one wave per ambiguous child prunes the root tape -> push.
+static void tiles_by_groups(fhip_ctx* ctx, const RenderSetup& R, FhRenderState* dS, hipStream_t st) {
+    const int gg = blocks_for(ctx, R.lds_tiles_group, 8);
+    KaTiles ka = {dS, 0, 1, R.group_regs, R.group_choices, (uint32_t)gg, (ctx->probe ? 1u : 0u) | 2u | 4u | 8u, 0, 0};
+    (void)launch_asm(ctx, st, FH_ASM_TILES, (uint32_t)gg, &ka, sizeof(ka), R.lds_tiles_group);
+    const uint32_t blocks = R.S.qcap[0], root_words = (R.S.troot_choices + 15) / 16, group_words = (R.group_choices + 15) / 16;
+    if (R.S.top_chain && R.S.n_top > 64u * FH_CHAIN_SEG) FH_KLAUNCH(k_tchain3d_chunks, dim3(WAVE, blocks), dim3(WAVE), 0, st, dS);
+    else if (R.S.top_chain) FH_KLAUNCH(k_tchain3d, dim3(WAVE, blocks), dim3(WAVE), 0, st, dS);
+    else FH_KLAUNCH(k_ttop3d, dim3(blocks), dim3(WAVE), 0, st, dS);
+    // (the marks and the gather of the root tape's choice words do not depend on each other: one launch, the marks in the blocks
+    // behind the gather's)
+    if (R.classify_only || !root_words) FH_KLAUNCH(k_tmark3d, dim3(blocks), dim3(WAVE), 0, st, dS);
+    if (R.classify_only) return;       // (the fills of the decided tiles follow in the push; nothing is pruned or queued)
+    if (root_words) FH_KLAUNCH(k_tscatter3d, dim3(root_words + 1, blocks), dim3(WAVE), 0, st, dS, group_words, root_words);
+    KaPrune1 kp = {dS, 0, 1, R.S.troot_choices, 2};
+    if (!R.prune2) { (void)launch_asm(ctx, st, FH_ASM_PRUNE1, blocks * 64, &kp, sizeof(kp)); return; }
+    hipEvent_t ea = nullptr, eb = nullptr;      // (timed under the fh_prune1 slot of the per-kernel profile: it replaces that launch)
+    if (ctx->profiling) { (void)hipEventCreate(&ea); (void)hipEventCreate(&eb); (void)hipEventRecord(ea, st); }
+    FH_KLAUNCH(k_prune2, dim3(blocks * FH_P2_PER_SLOT), dim3(FH_P2_WPB * FH_P2_WPC * 64), R.lds_prune2, st, dS, 0u, 1u, root_words,
+                       (const uint2*)R.d_links, (const uint2*)R.d_ctab, 2u, R.S.troot_len, R.S.troot_choices, R.p2_cap_kept,
+                       (const uint32_t*)(R.d_ctab + std::max<uint32_t>(R.S.troot_choices, 1)), R.n_chain);
+    // ... and the scalar sweep behind it for the children it left marked (more than 64 registers or FH_P2_MAX_KEPT kept ops:
+    // none for the models here; a wave whose child is done leaves at once)
+    size_t kp_bytes = sizeof(kp);
+    void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &kp, HIP_LAUNCH_PARAM_BUFFER_SIZE, &kp_bytes, HIP_LAUNCH_PARAM_END};
+    (void)hipModuleLaunchKernel(ctx->asm_fn[FH_ASM_PRUNE1], blocks * 64, 1, 1, WAVE, 1, 1, 0, st, nullptr, extra);
+    if (ctx->profiling) { (void)hipEventRecord(eb, st); ctx->asm_events.push_back({FH_ASM_PRUNE1, {ea, eb}}); }
+}
+// The assembly tile kernels, as the level's plan says (frame_schedule.hpp plan_level: why each launch is there)
+static void tiles_asm(fhip_ctx* ctx, const RenderSetup& R, const LevelPlan& L, FhRenderState* dS, int level, FrameStreams& fs) {
     // Persistent waves with a static round robin over the parents (one short workgroup per parent was measured slower in the
     // pipelined frame: the tile stage then takes more of the machine from the leaf kernel it overlaps with).
-    const int gs = blocks_for(ctx, R.lds_tiles_small, 8);
-    const int gb = blocks_big(ctx, R, R.lds_tiles_big, 8);
-    const int gp = ctx->n_cu * 8;
-    // Rare mode (render3d): at a per-slab level the two launches for parents outside the small slot list are not made; the push kernel's last
-    // blocks evaluate such parents in C++ (none, nearly always)
-    const bool rare_level = ctx->rare_now && is3d && R.asm_tiles && !ctx->opt.no_tiles_v && level > 0 && R.S.pre_levels > 0 && (uint32_t)level >= R.S.pre_levels &&
-                            !(R.prune1 && (uint32_t)level < R.exp_levels);
-    launch(ctx, FHIP_K_TILES, [&] {
-        if (is3d) FH_KLAUNCH(k_tsetup3d, dim3(gp), dim3(WAVE), 0, ctx->stream, dS, level);
-        else FH_KLAUNCH(k_tsetup2d, dim3(gp), dim3(WAVE), 0, ctx->stream, dS, level);
-    });
-    if (R.groups && level == 0) {
-        // Tape parallelism: the root tree's terms by independent groups, one wave per (block of root
-        // tiles, group) -> the tree over the terms (result, marks, arena) -> the root tape's choice words
-        // gathered from both -> one wave per ambiguous child prunes the root tape -> push.
-        launch(ctx, FHIP_K_TILES, [&] {
-            struct { FhRenderState* S; uint32_t level, big, max_regs, max_choices, n_waves, flags, skip_regs, skip_choices; } ka;
-            const int gg = blocks_for(ctx, R.lds_tiles_group, 8);
-            ka.S = dS; ka.level = 0; ka.big = 1; ka.max_regs = R.group_regs; ka.max_choices = R.group_choices;
-            ka.n_waves = (uint32_t)gg; ka.flags = (ctx->probe ? 1u : 0u) | 2u | 4u | 8u; ka.skip_regs = ka.skip_choices = 0;
-            (void)launch_asm(ctx, FH_ASM_TILES, (uint32_t)gg, &ka, sizeof(ka), R.lds_tiles_group);
-            const uint32_t blocks = R.S.qcap[0], root_words = (R.S.troot_choices + 15) / 16, group_words = (R.group_choices + 15) / 16;
-            if (R.S.top_chain && R.S.n_top > 64u * FH_CHAIN_SEG) FH_KLAUNCH(k_tchain3d_chunks, dim3(WAVE, blocks), dim3(WAVE), 0, ctx->stream, dS);
-            else if (R.S.top_chain) FH_KLAUNCH(k_tchain3d, dim3(WAVE, blocks), dim3(WAVE), 0, ctx->stream, dS);
-            else FH_KLAUNCH(k_ttop3d, dim3(blocks), dim3(WAVE), 0, ctx->stream, dS);
-            // (the marks and the gather of the root tape's choice words do not depend on each other: one launch, the marks in the blocks
-            // behind the gather's)
-            if (R.classify_only || !root_words) FH_KLAUNCH(k_tmark3d, dim3(blocks), dim3(WAVE), 0, ctx->stream, dS);
-            if (R.classify_only) return;       // (the fills of the decided tiles follow below; nothing is pruned or queued)
-            if (root_words) FH_KLAUNCH(k_tscatter3d, dim3(root_words + 1, blocks), dim3(WAVE), 0, ctx->stream, dS, group_words, root_words);
-            if (R.prune2) {
-                hipEvent_t ea = nullptr, eb = nullptr;      // (timed under the fh_prune1 slot of the per-kernel profile: it replaces that launch)
-                if (ctx->profiling) { (void)hipEventCreate(&ea); (void)hipEventCreate(&eb); (void)hipEventRecord(ea, ctx->stream); }
-                FH_KLAUNCH(k_prune2, dim3(blocks * FH_P2_PER_SLOT), dim3(FH_P2_WPB * FH_P2_WPC * 64), R.lds_prune2, ctx->stream, dS, 0u, 1u, root_words,
-                                   (const uint2*)R.d_links, (const uint2*)R.d_ctab, 2u, R.S.troot_len, R.S.troot_choices, R.p2_cap_kept,
-                                   (const uint32_t*)(R.d_ctab + std::max<uint32_t>(R.S.troot_choices, 1)), R.n_chain);
-                // ... and the scalar sweep behind it for the children it left marked (more than 64 registers or FH_P2_MAX_KEPT kept ops:
-                // none for the models here; a wave whose child is done leaves at once)
-                struct { FhRenderState* S; uint32_t level, big, max_choices, mode; } kp = {dS, 0, 1, R.S.troot_choices, 2};
-                size_t kp_bytes = sizeof(kp);
-                void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, &kp, HIP_LAUNCH_PARAM_BUFFER_SIZE, &kp_bytes, HIP_LAUNCH_PARAM_END};
-                (void)hipModuleLaunchKernel(ctx->asm_fn[FH_ASM_PRUNE1], blocks * 64, 1, 1, WAVE, 1, 1, 0, ctx->stream, nullptr, extra);
-                if (ctx->profiling) { (void)hipEventRecord(eb, ctx->stream); ctx->asm_events.push_back({FH_ASM_PRUNE1, {ea, eb}}); }
-            } else {
-                struct { FhRenderState* S; uint32_t level, big, max_choices, mode; } kp = {dS, 0, 1, R.S.troot_choices, 2};
-                (void)launch_asm(ctx, FH_ASM_PRUNE1, blocks * 64, &kp, sizeof(kp));
-            }
-        });
-    } else if (R.asm_tiles) {
-        launch(ctx, FHIP_K_TILES, [&] {
-            // pre-pass levels: long tapes, few parents -> the forward pass exports its choices and
-            // the prune runs as one wave per child (fh_prune1)
-            const bool exp = R.prune1 && (uint32_t)level < R.exp_levels;      // level 0 only: 8 parents, 6363-op tape (measured)
-            const int K_TILES = R.asm_tiles_t ? FH_ASM_TILES_T : FH_ASM_TILES;
-            struct { FhRenderState* S; uint32_t level, big, max_regs, max_choices, n_waves, flags, skip_regs, skip_choices; } ka;
-            ka.S = dS; ka.level = (uint32_t)level; ka.flags = (ctx->probe ? 1u : 0u) | (exp ? 2u : 0u);
-            ka.skip_regs = ka.skip_choices = 0;
-            // Pre-pass levels below the root: the small-layout parents and the others are different slot lists;
-            // their launches run side by side (second stream) instead of one after the other.
-            // (Only for a frame alone, whose coarse levels are on the caller's stream: in a pipelined frame they are off the critical
-            // path, and the side stream carries the previous frame's tile chains, where this frame's level-1 kernel sat for 170 us
-            // of every frame - 1.64 -> 1.60 ms without the fork.  Forking to the tail stream instead: 2.0 ms; to streams of their
-            // own, also for the per-slab levels' nearly always empty big-list launches: 3.5 ms - streams beyond four share
-            // hardware queues (GPU_MAX_HW_QUEUES) and serialise against each other.)
-            // (A fifth stream for the per-slab levels' nearly always empty big-list launches, with GPU_MAX_HW_QUEUES=8 in the
-            // environment: 2.3 ms per frame instead of 1.03 - more than four streams in flight cost far more than two kernel
-            // boundaries per slab, whatever the number of hardware queues.)
-            hipStream_t const rest_stream = ctx->stream2;
-            const bool side = level > 0 && (uint32_t)level < R.S.pre_levels && ctx->use_pipeline && !ctx->profiling && rest_stream &&
-                              ctx->stream != rest_stream && ctx->stream != ctx->stream_pre && is3d;
-            hipStream_t const big_stream = side ? rest_stream : nullptr;
-            // Tapes of <= 32 registers / 256 choices (the small slot list: every parent of the leaf level) and, from the other
-            // list, those of <= 64 / 512 go to the kernels that keep the interval file, the choices and the prune's register
-            // map in VGPRs (fh_tiles_v32: 16 waves per CU, fh_tiles_v64: 8; no LDS); what is left takes the LDS layouts.
-            const bool use_v = !ctx->opt.no_tiles_v;
-            const bool vk = use_v && !exp;
-            bool both_lists = false;
-            if (level > 0) {
-                ka.big = 0; ka.max_regs = SMALL_REGS; ka.max_choices = SMALL_CHOICES; ka.n_waves = (uint32_t)gs;
-                if (side) {
-                    (void)hipEventRecord(ctx->ev_rest_fork, ctx->stream);
-                    (void)hipStreamWaitEvent(rest_stream, ctx->ev_rest_fork, 0);
-                }
-                // (a pre-pass level has a few hundred parents in the two lists together: fh_tiles_v64 takes both in ONE launch
-                // below - the level's time is its slowest parent's either way, and a launch of its own for the small list put
-                // another 130 us on the coarse levels' chain)
-                both_lists = vk && (uint32_t)level < R.S.pre_levels && !side;
-                if (vk && !both_lists) {
-                    // (32 waves per compute unit: twice what fits at once - the waves take the slots round robin, and with as many waves as
-                    // fit a launch of 1.5 slots per wave lasted two rounds of its longest parents: 0.213 -> 0.192 ms on the general path)
-                    const int v32_waves = 32;
-                    ka.n_waves = (uint32_t)(ctx->n_cu * v32_waves);
-                    (void)launch_asm(ctx, R.asm_tiles_t ? FH_ASM_TILES_V32_T : FH_ASM_TILES_V32, ka.n_waves, &ka, sizeof(ka));
-                } else if (vk) {
-                } else
-                    (void)launch_asm(ctx, K_TILES, (uint32_t)gs, &ka, sizeof(ka), R.lds_tiles_small);
-            }
-            ka.big = 1;
-            if (exp) ka.flags |= ((R.S.P.max_choices + 15) / 16) << 16;  // one stride in chw[1] for the medium and the large layout
-            bool rest = true;   // anything left for the root-sized LDS layout?
-            // (leaving the per-slab levels' big-list parents to the root-sized LDS launch alone - one launch less on the slab's tile
-            // chain - was measured: 1.02 vs 1.04 ms per frame, within the noise; not done)
-            if (rare_level) return;      // (the parents outside the small list: the blocks behind k_tpush3d's)
-            // (a ROOT tape that fits fh_tiles_v64 - 64 registers, 512 choices - and is not pruned through exported choices takes it too:
-            // bear.vm's 23 registers, 512^3: the root level 255 -> 160 us with the interval file in VGPRs instead of LDS)
-            const bool root_v64 = vk && level == 0 && is3d && !R.groups && R.S.P.max_regs <= V64_REGS && R.S.P.max_choices <= V64_CHOICES;
-            if (vk && (level > 0 || root_v64)) {
-                const int v64_waves = 8;
-                // (per-slab levels: the parents' tapes fit fh_tiles_v32 but for a rare one - an empty launch of 2048 waves of 176
-                // VGPRs each, queued behind the leaf kernel of the slab in front, was measured to hold the tile chain up for
-                // 130 us: a small persistent grid there)
-                const int v64_slab_waves = 128;
-                const bool per_slab = (uint32_t)level >= R.S.pre_levels && R.S.pre_levels > 0;
-                ka.max_regs = V64_REGS; ka.max_choices = V64_CHOICES;
-                ka.n_waves = per_slab ? (uint32_t)v64_slab_waves : (uint32_t)(ctx->n_cu * v64_waves);
-                if (both_lists) ka.flags |= 16u;
-                const uint32_t plain_flags = ka.flags;
-                (void)launch_asm(ctx, R.asm_tiles_t ? FH_ASM_TILES_V64_T : FH_ASM_TILES_V64, ka.n_waves, &ka, sizeof(ka), 0, 1, big_stream);
-                if (ctx->post_v64_stream && !per_slab && !big_stream) {      // (side_only_l1: the level's remaining launches - the LDS layouts' rest, the push - leave the side stream)
-                    (void)hipEventRecord(ctx->ev_l1, ctx->stream);
-                    (void)hipStreamWaitEvent(ctx->post_v64_stream, ctx->ev_l1, 0);
-                    ctx->stream = ctx->post_v64_stream;
-                }
-                ka.flags = plain_flags & ~16u;
-                ka.skip_regs = V64_REGS; ka.skip_choices = V64_CHOICES;
-                rest = R.S.P.max_regs > V64_REGS || R.S.P.max_choices > V64_CHOICES;
-            }
-            // Pre-pass levels below the root: a few hundred parents whose tapes are far smaller than the
-            // root's.  With the root-sized LDS layout only one wave fits a CU (256 at a time); a medium
-            // layout takes those that fit it three to a CU, the root-sized launch takes the rest.
-            const bool mid = !(vk && level > 0) && level > 0 && (uint32_t)level < R.S.pre_levels && R.lds_tiles_mid * 2 <= R.lds_tiles_big;
-            if (mid) {
-                const int gm = blocks_for(ctx, R.lds_tiles_mid, 8);
-                ka.max_regs = MID_REGS; ka.max_choices = MID_CHOICES; ka.n_waves = (uint32_t)gm;
-                (void)launch_asm(ctx, K_TILES, (uint32_t)gm, &ka, sizeof(ka), R.lds_tiles_mid, 1, big_stream);
-                ka.skip_regs = MID_REGS; ka.skip_choices = MID_CHOICES;
-            }
-            ka.max_regs = R.S.P.max_regs; ka.max_choices = R.S.P.max_choices; ka.n_waves = (uint32_t)gb;
-            if (rest) (void)launch_asm(ctx, K_TILES, (uint32_t)gb, &ka, sizeof(ka), R.lds_tiles_big, 1, big_stream);
-            if (side) {
-                (void)hipEventRecord(ctx->ev_rest_join, rest_stream);
-                (void)hipStreamWaitEvent(ctx->stream, ctx->ev_rest_join, 0);
-            }
-            if (exp) {
-                struct { FhRenderState* S; uint32_t level, big, max_choices, pad; } kp = {dS, (uint32_t)level, 0, SMALL_CHOICES, 0};
-                const uint32_t bound = R.S.qcap[level] * 64;  // 64 waves per possible parent; unmarked children exit at once
-                if (level > 0) (void)launch_asm(ctx, FH_ASM_PRUNE1, bound, &kp, sizeof(kp));
-                kp.big = 1; kp.max_choices = R.S.P.max_choices;
-                (void)launch_asm(ctx, FH_ASM_PRUNE1, bound, &kp, sizeof(kp));
-            }
-        });
-    } else
-    launch(ctx, FHIP_K_TILES, [&] {
-        if (level > 0) {
-            if (R.full) FH_KLAUNCH((k_teval3d<true, false>), dim3(gs), dim3(WAVE), R.lds_tiles_small, ctx->stream, dS, level);
-            else FH_KLAUNCH((k_teval3d<false, false>), dim3(gs), dim3(WAVE), R.lds_tiles_small, ctx->stream, dS, level);
-        }
-        if (R.full) FH_KLAUNCH((k_teval3d<true, true>), dim3(gb), dim3(WAVE), R.lds_tiles_big, ctx->stream, dS, level);
-        else FH_KLAUNCH((k_teval3d<false, true>), dim3(gb), dim3(WAVE), R.lds_tiles_big, ctx->stream, dS, level);
-    });
-    // (last level: fewer waves, several parents each - one leaf reservation per wave)
-#ifndef FH_PUSH_MUL
-#define FH_PUSH_MUL 2
-#endif
-    const int push_mul = FH_PUSH_MUL;
-    const int gpush = (level + 1 == (int)R.S.P.n_levels) ? ctx->n_cu * push_mul : gp;
-    launch(ctx, FHIP_K_TILES, [&] {
-        // (above the leaf level: 16 more waves per parent for the fills of its interval-full children - kernels.hip tfill3d_body)
-        const uint32_t rb = rare_level ? FH_RARE_BLOCKS : 0u;
-        if (is3d) FH_KLAUNCH(k_tpush3d, dim3(gpush + rb, (level + 1 == (int)R.S.P.n_levels) ? 1 : 17), dim3(WAVE), 0, ctx->stream, dS, level, rb, rare_file(ctx, dS), ctx->rare_stride);
-        else {
-            if (!R.classify_only) FH_KLAUNCH(k_tpush2d, dim3(gpush), dim3(WAVE), 0, ctx->stream, dS, level);
-            const uint32_t slots_max = R.S.qcap[level] * ((level == 0 && R.groups) ? R.S.n_tgroups : 1u);
-            FH_KLAUNCH(k_tfill2d, dim3(64, slots_max), dim3(256), 0, ctx->stream, dS, level);
-        }
-    });
-}
-
-static void launch_tiles(fhip_ctx* ctx, const RenderSetup& R, FhRenderState* dS, int level, bool is3d) {
-    if (R.split) return launch_tiles_split(ctx, R, dS, level, is3d);
     const int gs = blocks_for(ctx, R.lds_tiles_small, 8), gb = blocks_big(ctx, R, R.lds_tiles_big, 8);
-    launch(ctx, FHIP_K_TILES, [&] {
+    const int K_TILES = R.asm_tiles_t ? FH_ASM_TILES_T : FH_ASM_TILES;
+    auto big_stream = [&] { return L.fork_big ? fs.s[SIDE] : fs.on(); };      // where the launches for the other slot list go
+    KaTiles ka = {dS, (uint32_t)level, 0, SMALL_REGS, SMALL_CHOICES, (uint32_t)gs, (ctx->probe ? 1u : 0u) | (L.exp ? 2u : 0u), 0, 0};
+    if (L.fork_big) { (void)hipEventRecord(ctx->ev_rest_fork, fs.on()); (void)hipStreamWaitEvent(fs.s[SIDE], ctx->ev_rest_fork, 0); }
+    if (L.v32) {
+        // (32 waves per compute unit: twice what fits at once - the waves take the slots round robin, and with as many waves as
+        // fit a launch of 1.5 slots per wave lasted two rounds of its longest parents: 0.213 -> 0.192 ms on the general path)
+        ka.n_waves = (uint32_t)(ctx->n_cu * 32);
+        (void)launch_asm(ctx, fs.on(), R.asm_tiles_t ? FH_ASM_TILES_V32_T : FH_ASM_TILES_V32, ka.n_waves, &ka, sizeof(ka));
+    } else if (L.small_lds)
+        (void)launch_asm(ctx, fs.on(), K_TILES, (uint32_t)gs, &ka, sizeof(ka), R.lds_tiles_small);
+    ka.big = 1;
+    if (L.exp) ka.flags |= ((R.S.P.max_choices + 15) / 16) << 16;  // one stride in chw[1] for the medium and the large layout
+    if (L.rare) return;
+    if (L.v64) {
+        // (per-slab levels: the parents' tapes fit fh_tiles_v32 but for a rare one - an empty launch of 2048 waves of 176
+        // VGPRs each, queued behind the leaf kernel of the slab in front, was measured to hold the tile chain up for
+        // 130 us: a small persistent grid there)
+        ka.max_regs = V64_REGS; ka.max_choices = V64_CHOICES;
+        ka.n_waves = L.per_slab ? 128u : (uint32_t)(ctx->n_cu * 8);
+        if (L.both_lists) ka.flags |= 16u;
+        (void)launch_asm(ctx, big_stream(), R.asm_tiles_t ? FH_ASM_TILES_V64_T : FH_ASM_TILES_V64, ka.n_waves, &ka, sizeof(ka));
+        (void)hop(fs, L.rest_on, ctx->ev_l1);      // (level 1 of a `tiles_first` frame: its remaining launches - the LDS layouts' rest, the push - leave the side stream)
+        ka.flags &= ~16u;
+        ka.skip_regs = V64_REGS; ka.skip_choices = V64_CHOICES;
+    }
+    if (L.mid) {
+        const int gm = blocks_for(ctx, R.lds_tiles_mid, 8);
+        ka.max_regs = MID_REGS; ka.max_choices = MID_CHOICES; ka.n_waves = (uint32_t)gm;
+        (void)launch_asm(ctx, big_stream(), K_TILES, (uint32_t)gm, &ka, sizeof(ka), R.lds_tiles_mid);
+        ka.skip_regs = MID_REGS; ka.skip_choices = MID_CHOICES;
+    }
+    ka.max_regs = R.S.P.max_regs; ka.max_choices = R.S.P.max_choices; ka.n_waves = (uint32_t)gb;
+    if (L.rest) (void)launch_asm(ctx, big_stream(), K_TILES, (uint32_t)gb, &ka, sizeof(ka), R.lds_tiles_big);
+    if (L.fork_big) { (void)hipEventRecord(ctx->ev_rest_join, fs.s[SIDE]); (void)hipStreamWaitEvent(fs.on(), ctx->ev_rest_join, 0); }
+    if (L.exp) {
+        KaPrune1 kp = {dS, (uint32_t)level, 0, SMALL_CHOICES, 0};
+        const uint32_t bound = R.S.qcap[level] * 64;  // 64 waves per possible parent; unmarked children exit at once
+        if (level > 0) (void)launch_asm(ctx, fs.on(), FH_ASM_PRUNE1, bound, &kp, sizeof(kp));
+        kp.big = 1; kp.max_choices = R.S.P.max_choices;
+        (void)launch_asm(ctx, fs.on(), FH_ASM_PRUNE1, bound, &kp, sizeof(kp));
+    }
+}
+static void tiles_hip(fhip_ctx* ctx, const RenderSetup& R, FhRenderState* dS, int level, hipStream_t st) {
+    const int gs = blocks_for(ctx, R.lds_tiles_small, 8), gb = blocks_big(ctx, R, R.lds_tiles_big, 8);
+    if (level > 0 && R.full) FH_KLAUNCH((k_teval3d<true, false>), dim3(gs), dim3(WAVE), R.lds_tiles_small, st, dS, level);
+    else if (level > 0) FH_KLAUNCH((k_teval3d<false, false>), dim3(gs), dim3(WAVE), R.lds_tiles_small, st, dS, level);
+    if (R.full) FH_KLAUNCH((k_teval3d<true, true>), dim3(gb), dim3(WAVE), R.lds_tiles_big, st, dS, level);
+    else FH_KLAUNCH((k_teval3d<false, true>), dim3(gb), dim3(WAVE), R.lds_tiles_big, st, dS, level);
+}
+// The monolithic tile kernel (option no_split)
+static void launch_tiles_mono(fhip_ctx* ctx, const RenderSetup& R, FhRenderState* dS, int level, bool is3d, hipStream_t st) {
+    const int gs = blocks_for(ctx, R.lds_tiles_small, 8), gb = blocks_big(ctx, R, R.lds_tiles_big, 8);
+    launch(ctx, st, FHIP_K_TILES, [&] {
         if (is3d) { if (R.full) FH_LAUNCH_TILES(true, true, true, gb, R.lds_tiles_big); else FH_LAUNCH_TILES(true, false, true, gb, R.lds_tiles_big); }
         else { if (R.full) FH_LAUNCH_TILES(false, true, true, gb, R.lds_tiles_big); else FH_LAUNCH_TILES(false, false, true, gb, R.lds_tiles_big); }
     });
     if (level > 0)
-        launch(ctx, FHIP_K_TILES, [&] {
+        launch(ctx, st, FHIP_K_TILES, [&] {
             if (is3d) { if (R.full) FH_LAUNCH_TILES(true, true, false, gs, R.lds_tiles_small); else FH_LAUNCH_TILES(true, false, false, gs, R.lds_tiles_small); }
             else { if (R.full) FH_LAUNCH_TILES(false, true, false, gs, R.lds_tiles_small); else FH_LAUNCH_TILES(false, false, false, gs, R.lds_tiles_small); }
         });
+}
+// ... on the stream fs is at; fs moves only where the plan says so (LevelPlan::rest_on)
+static void launch_tiles(fhip_ctx* ctx, const RenderSetup& R, const LevelPlan& L, FhRenderState* dS, int level, bool is3d, FrameStreams& fs) {
+    if (L.path == LevelPlan::MONO) return launch_tiles_mono(ctx, R, dS, level, is3d, fs.on());
+    const int gp = ctx->n_cu * 8;
+    launch(ctx, fs.on(), FHIP_K_TILES, [&] {
+        if (is3d) FH_KLAUNCH(k_tsetup3d, dim3(gp), dim3(WAVE), 0, fs.on(), dS, level);
+        else FH_KLAUNCH(k_tsetup2d, dim3(gp), dim3(WAVE), 0, fs.on(), dS, level);
+    });
+    launch(ctx, fs.on(), FHIP_K_TILES, [&] {
+        if (L.path == LevelPlan::GROUPS) tiles_by_groups(ctx, R, dS, fs.on());
+        else if (L.path == LevelPlan::ASM) tiles_asm(ctx, R, L, dS, level, fs);
+        else tiles_hip(ctx, R, dS, level, fs.on());
+    });
+    // (last level: fewer waves, several parents each - one leaf reservation per wave)
+    const bool last = level + 1 == (int)R.S.P.n_levels;
+    const int gpush = last ? ctx->n_cu * L.push_mul : gp;
+    launch(ctx, fs.on(), FHIP_K_TILES, [&] {
+        // (above the leaf level: 16 more waves per parent for the fills of its interval-full children - kernels.hip tfill3d_body)
+        const uint32_t rb = L.rare ? FH_RARE_BLOCKS : 0u;
+        if (is3d) FH_KLAUNCH(k_tpush3d, dim3(gpush + rb, last ? 1 : 17), dim3(WAVE), 0, fs.on(), dS, level, rb, rare_file(ctx, dS, L.rare_stride), L.rare_stride);
+        else {
+            if (!R.classify_only) FH_KLAUNCH(k_tpush2d, dim3(gpush), dim3(WAVE), 0, fs.on(), dS, level);
+            const uint32_t slots_max = R.S.qcap[level] * ((level == 0 && R.groups) ? R.S.n_tgroups : 1u);
+            FH_KLAUNCH(k_tfill2d, dim3(64, slots_max), dim3(256), 0, fs.on(), dS, level);
+        }
+    });
 }
 
 static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render2d_config* cfg, float* out,
@@ -876,24 +768,26 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
         Q.S.image2d = d_out;
         FhRenderState* dS = (FhRenderState*)ctx->state.p;
         const FrameClear no_clear[3] = {};
-        ps = upload_frame(ctx, tape, Q, no_clear);
+        FrameStreams fs = frame_streams(ctx);       // (a 2D frame is one chain on the caller's stream)
+        hipStream_t const st = fs.on();
+        ps = upload_frame(ctx, st, tape, Q, no_clear);
         if (ps) return ps;
         for (uint32_t l = 0; l < Q.S.P.n_levels; l++) {
             if (ctx->is_cancelled()) return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
-            launch_tiles(ctx, Q, dS, (int)l, false);
+            launch_tiles(ctx, Q, plan_level(Q, schedule_inputs(ctx, out_is_device), (int)l, false, 0u, CALLER, CALLER), dS, (int)l, false, fs);
         }
         if (Q.classify_only) return FHIP_OK;
-        launch(ctx, FHIP_K_POINTS, [&] {
-            if (Q.full) FH_KLAUNCH((k_pixels2d<32, true>), dim3(ctx->n_cu * 8), dim3(WAVE), 0, ctx->stream, dS);
-            else FH_KLAUNCH((k_pixels2d<32, false>), dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS);
+        launch(ctx, st, FHIP_K_POINTS, [&] {
+            if (Q.full) FH_KLAUNCH((k_pixels2d<32, true>), dim3(ctx->n_cu * 8), dim3(WAVE), 0, st, dS);
+            else FH_KLAUNCH((k_pixels2d<32, false>), dim3(ctx->n_cu * 16), dim3(WAVE), 0, st, dS);
         });
         if (Q.S.P.max_regs > 32)
-            launch(ctx, FHIP_K_POINTS, [&] {
+            launch(ctx, st, FHIP_K_POINTS, [&] {
                 const int g = blocks_big(ctx, Q, Q.lds_points_big, 16);
-                if (Q.full) FH_KLAUNCH((k_pixels2d<0, true>), dim3(g), dim3(WAVE), Q.lds_points_big, ctx->stream, dS);
-                else FH_KLAUNCH((k_pixels2d<0, false>), dim3(g), dim3(WAVE), Q.lds_points_big, ctx->stream, dS);
+                if (Q.full) FH_KLAUNCH((k_pixels2d<0, true>), dim3(g), dim3(WAVE), Q.lds_points_big, st, dS);
+                else FH_KLAUNCH((k_pixels2d<0, false>), dim3(g), dim3(WAVE), Q.lds_points_big, st, dS);
             });
-        if (ctx->host_flags) FH_KLAUNCH(k_latch_arena, dim3(1), dim3(1), 0, ctx->stream, dS, 1u, ctx->host_flags);    // (an arena that ran out: grown before the next frame)
+        if (ctx->host_flags) FH_KLAUNCH(k_latch_arena, dim3(1), dim3(1), 0, st, dS, 1u, ctx->host_flags);    // (an arena that ran out: grown before the next frame)
         return FHIP_OK;
     };
     // Small images of a large tape (round 5).  With 128 x 128 root tiles a 256 x 256 image is FOUR one-wave chains over a tape that a quarter
@@ -935,11 +829,181 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     return FHIP_OK;
 }
 
+// ---- a 3D frame: the stages of a slab, each on the stream it is given; then the frame in the order of its schedule ---------------------
+// Head of a slab's tile chain: the slab's counters and table reset, the min-depth pyramid rebuilt from the slabs in front
+static void slab_begin(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, int k, hipStream_t st) {
+    const FhRender& P = R.S.P;
+    const uint32_t pre = R.S.pre_levels, n_groups = R.groups_per_slab, n32 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
+    launch(ctx, st, FHIP_K_OTHER, [&] {
+        // the usual pyramid (three levels, 4 x 4 each, 8 x 8 leaf tiles) has a kernel of its own
+        // (up to 1024 x 1024: at 2048 x 2048 it was measured SLOWER than the generic kernel - 11.2 vs 8.2 ms per frame)
+        const bool pyr3 = P.n_levels == 3 && P.tiles[2] == 8 && P.tiles[1] == 32 && P.tiles[0] == 128 && n32 <= 1024;
+        const bool rebuild = k != F.slab_first;  // the first slab sees an empty image (pyramid pre-zeroed)
+        // (32 / 8 with its one pre-pass level: both pyramid levels rebuilt and the slab reset in one launch as well)
+        const bool pyr2 = P.n_levels == 2 && P.tiles[1] == 8 && P.tiles[0] == 32 && pre == 1;
+        if (rebuild && pyr2) { FH_KLAUNCH(k_slab_begin2, dim3(n32 + F.reset_blocks), dim3(256), 0, st, dS, n32, F.table_words, (uint32_t)k, n_groups); return; }
+        if (rebuild && pyr3 && pre == 2) { FH_KLAUNCH(k_slab_begin3, dim3(n32 + F.reset_blocks), dim3(256), 0, st, dS, n32, F.table_words, (uint32_t)k, n_groups); return; }
+        // (workgroups of one wave: they find room beside a leaf kernel that fills the machine - 73 us per launch on the general path with four)
+        FH_KLAUNCH(k_reset_slab, dim3(F.reset_blocks * 4), dim3(WAVE), 0, st, dS, F.table_words, (uint32_t)k, n_groups, (pyr3 && rebuild) ? 1u : 0u);
+        if (rebuild && pyr3) FH_KLAUNCH(k_minpyramid3, dim3(n32), dim3(256), 0, st, dS);
+        else if (rebuild) FH_KLAUNCH(k_minpyramid, dim3(P.roots_x * P.roots_y), dim3(256), 0, st, dS);
+    });
+}
+// The tile chain of slab k (the idx-th slab rendered) on the schedule's tile stream
+static fhip_status tile_step(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, int k, int idx) {
+    fs.cur = F.tiles;
+    if (F.pipe && idx >= (int)F.NC) HIP_TRY(ctx, hipStreamWaitEvent(fs.on(), ctx->ev_leaves[idx - (int)F.NC], 0));  // context free again
+    slab_begin(ctx, R, F, dS, k, fs.on());
+    for (uint32_t l = R.S.pre_levels; l < R.S.P.n_levels; l++) launch_tiles(ctx, R, F.level[l], dS, (int)l, true, fs);
+    if (F.pipe) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles[idx], fs.on()));
+    fs.cur = CALLER;
+    return FHIP_OK;
+}
+// The footprint lists of a slab, and its leaves beyond the leaf kernel's register file
+static void classify_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, hipStream_t st) {
+    const uint32_t class_blocks = (R.n_footprints + FH_CLASSIFY_FP - 1) / FH_CLASSIFY_FP;
+    // (by_list: nothing to classify - what is left of the launch is rare mode's blocks for the leaves beyond the leaf kernel's file)
+    if (F.by_list && F.rare && R.S.P.max_regs > R.S.leaf_asm_regs)
+        launch(ctx, st, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_classify3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, 1, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride); });
+    else if (!F.by_list) launch(ctx, st, FHIP_K_OTHER, [&] {
+        FH_KLAUNCH(k_classify3d, dim3(class_blocks + (F.rare ? FH_RARE_BLOCKS : 0u)), dim3(R.S.P.slab / 8 > 16 ? 256 : WAVE), 0, st, dS, R.asm_points ? 1 : 0, class_blocks,
+                   rare_file(ctx, dS, F.rare_stride), F.rare_stride);
+    });
+    if (R.S.P.max_regs > R.S.leaf_asm_regs && !F.rare)      // (rare mode: in the blocks behind k_classify3d's)
+        launch(ctx, st, FHIP_K_POINTS, [&] {
+            const int g = blocks_big(ctx, R, R.lds_points_big, 16);
+            if (R.full) FH_KLAUNCH((k_leaves3d<2, 0, 1, true>), dim3(g), dim3(WAVE), R.lds_points_big, st, dS);
+            else FH_KLAUNCH((k_leaves3d<2, 0, 1, false>), dim3(g), dim3(WAVE), R.lds_points_big, st, dS);
+        });
+}
+// The leaf kernel of slab context `sk`, by the walk the schedule chose (frame_schedule.hpp leaf_walk: why)
+static void leaf_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, uint32_t sk, hipStream_t st) {
+    launch(ctx, st, FHIP_K_POINTS, [&] {
+        // class 0: <= 16 registers, 4 voxels per lane; class 1: <= 32 registers, 2 per lane; class 2: LDS file
+        if (F.leaf_walk == FrameSchedule::HIP_LEAVES) {
+            const int per_cu = R.full ? 8 : 16;
+            if (R.full) { FH_KLAUNCH((k_leaves3d<0, 16, 4, true>), dim3(ctx->n_cu * per_cu), dim3(WAVE), 0, st, dS); FH_KLAUNCH((k_leaves3d<1, 32, 2, true>), dim3(ctx->n_cu * per_cu), dim3(WAVE), 0, st, dS); }
+            else { FH_KLAUNCH((k_leaves3d<0, 16, 4, false>), dim3(ctx->n_cu * per_cu), dim3(WAVE), 0, st, dS); FH_KLAUNCH((k_leaves3d<1, 32, 2, false>), dim3(ctx->n_cu * per_cu), dim3(WAVE), 0, st, dS); }
+            return;
+        }
+        // one launch for classes 0 and 1: 128 VGPRs -> 4 waves per SIMD
+        // per-frame constants of the leaf kernel (gen_interp.py gen_columns): input slots of the axes, the inputs that change
+        // along a pixel column (a z coefficient in the axis' matrix row, or a projective matrix), projective flag
+        const int which = R.asm_points_t ? FH_ASM_COLUMNS_T : FH_ASM_COLUMNS;
+        const uint32_t layers = R.S.P.slab / 8;
+        // (the slab context's leaf table and leaf records, as k_fork_state lays the contexts out: the kernel takes them - with the table's shape - from its
+        // kernarg, so that a wave whose part of the table is empty leaves after one dependent load)
+        const void* const slab_table = sk == 0 ? (const void*)R.S.leaf_table : (const void*)((const FhLeafRef*)ctx->leaf_table_b.p + (size_t)(sk - 1) * R.S.leaf_cap);
+        const void* const slab_leaves = sk == 0 ? (const void*)R.S.leaves : (const void*)((const FhLeaf*)ctx->leaves_b.p + (size_t)(sk - 1) * R.S.leaf_cap);
+        KaColumns ka = {dS, 0u, R.col_slots, R.col_depmask, R.col_flags, {0, 0}, slab_table, R.n_footprints, layers};
+        if (F.leaf_walk == FrameSchedule::BY_LIST) {      // (flags bit 21: table = the slab context's FhLeaf records, nfpl = their capacity, pad[0] = the launch's waves)
+            ka.flags |= (3u << 20) | (6u << 24); ka.pad[0] = F.list_waves; ka.table = slab_leaves; ka.nfpl = R.S.leaf_cap;
+            (void)launch_asm(ctx, st, which, F.list_waves, &ka, sizeof(ka));
+        } else if (F.leaf_walk == FrameSchedule::BY_COLUMNS) {      // (flags bit 20: a footprint column per wave; bits 24 .. 27: in groups of 2^g layers, grid y = the group)
+            ka.flags |= (1u << 20) | (F.g << 24);
+            (void)launch_asm(ctx, st, which, (R.n_footprints + 63) / 64 * 64, &ka, sizeof(ka), 0, (layers + (1u << F.g) - 1) >> F.g);
+        } else {
+            // one workgroup per block of 4 footprints (gen_interp.py FH_BLKL = 2) of one 8-voxel layer, front layers first
+            // (pad[0]: floor(2^32 / blocks per layer) - the kernel rotates a layer's blocks by a per-layer offset, which is what balances
+            // the launch, and takes the remainder by this reciprocal instead of a subtraction loop)
+            const uint32_t n_blocks = (R.n_footprints + 3) / 4;
+            ka.pad[0] = n_blocks > 1 ? (uint32_t)(((uint64_t)1 << 32) / n_blocks) : 0u;
+            (void)launch_asm(ctx, st, which, n_blocks, &ka, sizeof(ka), 0, layers);
+        }
+    });
+}
+// The normals of slab k's hits
+static void normals_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, int k, hipStream_t st) {
+    const uint32_t z_lo = (uint32_t)k * R.S.P.slab, z_hi = z_lo + R.S.P.slab;
+    launch(ctx, st, FHIP_K_NORMALS, [&] {
+        const int gs = blocks_for(ctx, R.lds_normals_small, 8), gb = blocks_big(ctx, R, R.lds_normals_big, 8);
+        const int which = R.asm_points_t ? FH_ASM_NORMALS_T : FH_ASM_NORMALS;
+        if (F.by_list) {
+            // (the leaf that owns a pixel's hit is its column's leaf or nobody: fh_normals takes the slab's leaves one per wave pass and
+            // looks at the z-buffer itself; k_hits3d: rare mode's blocks for the footprints the push put on list 2)
+            if (F.rare && R.S.P.max_regs > R.S.norm_asm_regs)
+                FH_KLAUNCH(k_hits3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, R.hit_bucket_cap, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride);
+            KaNormals kn = {dS, F.list_waves, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 1u};
+            (void)launch_asm(ctx, st, which, kn.n_waves, &kn, sizeof(kn));
+        }
+        else if (R.asm_normals) {
+            // (lists 0 and 1 of k_classify3d hold every footprint whose leaves need <= 32 registers - the assembly interpreter's file:
+            // k_hits3d turns them into the list of leaves that own a hit, the normals kernel takes one leaf per wave pass)
+            const uint32_t hb = std::min<uint32_t>(R.n_footprints, (uint32_t)ctx->n_cu * 64);
+            FH_KLAUNCH(k_hits3d, dim3(hb + (F.rare ? FH_RARE_BLOCKS : 0u)), dim3(WAVE), 0, st, dS, z_lo, z_hi, R.hit_bucket_cap, hb, rare_file(ctx, dS, F.rare_stride), F.rare_stride);
+            // (wave w walks bucket w % 64 with a stride of n_waves / 64)
+            KaNormals kn = {dS, std::max<uint32_t>((uint32_t)(ctx->n_cu * 8) / FH_HIT_BUCKETS, 1u) * FH_HIT_BUCKETS, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 0};
+            (void)launch_asm(ctx, st, which, kn.n_waves, &kn, sizeof(kn));
+        }
+        else if (R.full) FH_KLAUNCH((k_normals3d<true, false>), dim3(gs), dim3(WAVE), R.lds_normals_small, st, dS, z_lo, z_hi);
+        else FH_KLAUNCH((k_normals3d<false, false>), dim3(gs), dim3(WAVE), R.lds_normals_small, st, dS, z_lo, z_hi);
+        if (R.S.P.max_regs > R.S.norm_asm_regs && !(F.rare && R.asm_normals)) {      // (rare mode: in the blocks behind k_hits3d's)
+            if (R.full) FH_KLAUNCH((k_normals3d<true, true>), dim3(gb), dim3(WAVE), R.lds_normals_big, st, dS, z_lo, z_hi);
+            else FH_KLAUNCH((k_normals3d<false, true>), dim3(gb), dim3(WAVE), R.lds_normals_big, st, dS, z_lo, z_hi);
+        }
+    });
+}
+// The coarse levels of every slab in one go, then what follows them - the flags of the parked parents, the frame mark, the fork of the slab
+// contexts - and the edges to the streams the slabs run on; leaves fs on the caller's stream
+static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS) {
+    const uint32_t pre = R.S.pre_levels;
+    FhFork fork{};
+    fork.n = F.NC; fork.mark = F.coarse ? 1u : 0u;
+    fork.leaves = (FhLeaf*)ctx->leaves_b.p; fork.leaf_table = (FhLeafRef*)ctx->leaf_table_b.p; fork.fp_lists = (uint32_t*)ctx->fp_lists_b.p;
+    fork.leaf_cap = (size_t)R.S.leaf_cap; fork.n_footprints = (size_t)R.n_footprints; fork.hit_words = R.hit_words;
+    const bool forked_here = F.coarse && R.zrep;
+    if (F.coarse) {
+        launch_tiles(ctx, R, F.level[0], dS, 0, true, fs);
+        if (pre > 1) {
+            HIP_TRY(ctx, hop(fs, F.l1_flags, ctx->ev_l0));
+            if (R.zrep) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 4), dim3(WAVE), 0, fs.on(), dS, 1, R.col_depmask, 0, FhFork{}); });
+            HIP_TRY(ctx, hop(fs, F.l1, ctx->ev_l0));
+            launch_tiles(ctx, R, F.level[1], dS, 1, true, fs);
+        }
+        HIP_TRY(ctx, hop(fs, F.fork_on, pre > 1 ? ctx->ev_l1 : ctx->ev_l0));      // (level 1 did not go through fh_tiles_v64; or one coarse level whose tail goes to the side stream)
+        // (the fork of a pipelined frame's slab contexts - or, with ONE context, the frame mark alone - in the same launch)
+        if (R.zrep) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 8 + 1), dim3(WAVE), 0, fs.on(), dS, (int)pre, R.col_depmask, 1, fork); });
+        if (!F.pipe && !forked_here) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_mark_frame, dim3(1), dim3(1), 0, fs.on(), dS); });
+    }
+    if (F.pipe) {
+        if (!forked_here) FH_KLAUNCH(k_fork_state, dim3(1), dim3(1), 0, fs.on(), dS, fork);
+        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, fs.on()));
+        if (F.fork_to_side) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[SIDE], ctx->ev_fork, 0));
+    }
+    if (F.ev_pre) HIP_TRY(ctx, hop(fs, CALLER, ctx->ev_pre));     // (from the stream the last coarse-level kernel went to)
+    fs.cur = CALLER;
+    if (F.fork_to_tail) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[TAIL], ctx->ev_fork, 0));
+    return FHIP_OK;
+}
+// The slabs, front to back (voxel.rs:252-261): tile chain, footprint lists, leaf kernel, normals - each on its role's stream, slab
+// contexts in turn
+static fhip_status render_slabs(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS0) {
+    auto slab_state = [&](int idx) { return dS0 + (F.pipe ? (uint32_t)idx % F.NC : 0u); };
+    for (int idx = 0; F.tiles_first && idx < F.n_rendered; idx++) { const fhip_status st = tile_step(ctx, R, F, fs, slab_state(idx), F.slab_first - idx, idx); if (st) return st; }
+    for (int idx = 0; idx < F.n_rendered; idx++) {
+        if (ctx->is_cancelled()) return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
+        const int k = F.slab_first - idx;
+        FhRenderState* const dS = slab_state(idx);
+        if (!F.tiles_first) { const fhip_status st = tile_step(ctx, R, F, fs, dS, k, idx); if (st) return st; }
+        if (F.pipe) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.leaf], ctx->ev_tiles[idx], 0));
+        if (F.aux_edge) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.lists], ctx->ev_tiles[idx], 0));
+        classify_work(ctx, R, F, dS, fs.s[F.lists]);
+        leaf_work(ctx, R, F, dS, (uint32_t)(dS - dS0), fs.s[F.leaf]);
+        if (F.aux_edge) { HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[idx], fs.s[F.leaf])); HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.normals], ctx->ev_aux[idx], 0)); }     // the slab's leaf kernel is through
+        if (F.normals_on) normals_work(ctx, R, F, dS, k, fs.s[F.normals]);
+        if (F.pipe) HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], fs.s[F.normals]));       // slab context free again; the last one: image complete
+    }
+    // (the tail stream is serial: the last slab's normals)
+    if (F.aux_edge && F.n_rendered > 0) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[CALLER], ctx->ev_leaves[F.n_rendered - 1], 0));
+    return FHIP_OK;
+}
+
 static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_config* cfg, void* out,
                                   int out_is_device, const PartSpec& part) {
     if (ctx->is_cancelled()) return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
     if (ctx->opt.stats & 2) g_spans.start();
     (void)hipSetDevice(ctx->device);
+    // bind and camera
     RenderSetup R;
     memset(&R.S, 0, sizeof(R.S));
     FhRender& P = R.S.P;
@@ -952,431 +1016,60 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     fhip_screen_to_world(size, 3, s2w);
     mat_product(cfg->world_to_model ? cfg->world_to_model : ident, s2w, 4, P.mat);  // voxel.rs:107-109
     column_setup(ctx, tape, P, R);
-    std::vector<uint32_t> ts = cfg->tile_sizes ? trim_tiles(cfg->tile_sizes, cfg->n_tile_sizes, std::max(cfg->width, cfg->height))
-                                               : hip_tiles_3d(std::max(cfg->width, cfg->height));
-    bool own_tiles = !cfg->tile_sizes;
-    if (cfg->tile_sizes) {
-        // Any list the reference accepts (TileSizes::new, fidget-core/src/render/mod.rs:181-251: descending, each a multiple of the next;
-        // fidget-jit's own hint is [64, 16, 8], a caller's [64, 16, 4] is valid there) is accepted here: what the device's kernels cannot
-        // take as given - leaves other than 8^3 (one 8 x 8 footprint per wavefront), a fan-out above 64 children (one per lane) - is
-        // rendered with the library's list instead.  A 3D image does not depend on the tile sizes, so the caller
-        // cannot tell, except by the time; fhip_render_counters out[7] counts such frames.
-        bool valid = cfg->n_tile_sizes >= 1 && cfg->tile_sizes[cfg->n_tile_sizes - 1] >= 1, native = valid;
-        for (uint32_t i = 1; i < cfg->n_tile_sizes && valid; i++)
-            valid = cfg->tile_sizes[i - 1] > cfg->tile_sizes[i] && cfg->tile_sizes[i] > 0 && cfg->tile_sizes[i - 1] % cfg->tile_sizes[i] == 0;
-        if (!valid) return fail(ctx, FHIP_ERR_UNSUPPORTED, "bad tile size list");
-        native = ts.back() == 8 && ts.size() <= FH_MAX_LEVELS;
-        for (size_t i = 1; i < ts.size() && native; i++) { const uint32_t n = ts[i - 1] / ts[i]; native = n * n * n <= 64; }
-        if (!native) { ts = hip_tiles_3d(std::max(cfg->width, cfg->height)); own_tiles = true; ctx->substituted_tiles++; }
-    }
-    // Few tiles, long tape (a small image, a part of a frame on one rank of several, a model without z): root tiles of 32^3 straight
-    // above the leaves.  With 128^3 root tiles such a frame is a handful of one-wave chains over tapes that a 128^3 tile barely prunes
-    // (prospero.vm at 512^3: a root tile keeps up to 1 795 of 6 363 ops - beyond the linked prune's and fh_tiles_v64's limits, so the
-    // LDS-file kernel and the scalar sweep walk them: 3.3 ms for one frame).  The root level's forward pass is parallel over the tape
-    // (term groups) however many tiles there are, and the linked prune handles a thousand children in one round, each a wave: pruning
-    // the ROOT tape per 32^3 tile costs what pruning it per 128^3 tile costs, its tapes are what level 1 would have arrived at, and
-    // level 1 - the longest kernel of the frame - is not run at all: 512^3 3.25 -> 1.45 ms alone.  A 3D image does not depend on the
-    // tile sizes, so this is the library's choice whenever the caller gave none: taken while the root level has at
-    // most `root32_max` children - counting one layer per z-slab when the root tape reads nothing that changes along a pixel column
-    // (root_zrep, prepare) - and the tape is one the groups + linked prune path takes.
-    if (own_tiles && ctx->opt.root32_max > 0 && ts.size() == 3 && ts[0] == 128 && ctx->use_split && ctx->use_asm &&
-        !tape->tgroups.empty() && !ctx->opt.no_tape_groups && ctx->opt.prune2 && tape_asm_ok(tape->t) &&
-        tape->t.ops.size() <= FH_P2_MAX_OPS && tape->t.n_choices <= FH_P2_MAX_CHOICES) {
-        const uint64_t cols = (uint64_t)((P.width + 31) / 32) * ((P.height + 31) / 32) / std::max<uint32_t>(1, part.n_shards * part.nx * part.ny);
-        const bool dedupe = R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
-        const uint64_t layers = dedupe ? (ctx->opt.no_zrep == 0 ? 1u : (uint64_t)std::max<uint32_t>(2, (P.depth + 511) / 512))      // (one layer per slab; the front slab only)
-                                       : (uint64_t)((P.depth + 31) / 32) / std::max<uint32_t>(1, part.nz);
-        // (measured, profiles/r05c: up to two rounds of the linked prune's workgroups - 2 048 children - always; up to root32_max when a
-        // 128^3 root tile is a quarter of the image or more - there the 128^3 tiles' tapes stay long whatever is done: 512^3 with z in
-        // every tape, 4 096 children, 3.65 -> 1.72 ms; an octant of a 1024^3 frame, as many children of a model twice the size: 1.10 -> 1.33)
-        const uint64_t children = cols * std::max<uint64_t>(layers, 1);
-        if ((children <= 2048 || (children <= (uint64_t)ctx->opt.root32_max && std::max(P.width, P.height) <= 512)) && (P.depth + 31) / 32 <= FH_MAX_SLABS)
-            ts = {32, 8};
-    }
-    // Frame pipelining (asynchronous renders): this frame takes the buffer set the previous frame did not use, and everything up
-    // to and including its coarse levels is queued on a stream of its own - it depends on nothing the previous frame does, so it
-    // runs beside that frame's slabs.  The slabs' tile chains follow on the side stream (after the previous frame's), the leaf
-    // chains and the final image on the caller's stream as before.
-    hipStream_t const main_stream = ctx->stream;
+    // choose the tiles
+    const bool root32_tape = ctx->use_split && ctx->use_asm && !tape->tgroups.empty() && !ctx->opt.no_tape_groups && ctx->opt.prune2 && tape_asm_ok(tape->t) &&
+                             tape->t.ops.size() <= FH_P2_MAX_OPS && tape->t.n_choices <= FH_P2_MAX_CHOICES;
+    const TileChoice tiles = choose_tiles_3d(cfg->tile_sizes, cfg->n_tile_sizes, size, part.n_shards * part.nx * part.ny, part.nz, R.column_inv, ctx->opt.root32_max, ctx->opt.no_zrep, root32_tape);
+    if (!tiles.valid) return fail(ctx, FHIP_ERR_UNSUPPORTED, "bad tile size list");
+    if (tiles.substituted) ctx->substituted_tiles++;
+    // pick the buffer set: a pipelined frame takes the set used longest ago
+    ScheduleInputs in = schedule_inputs(ctx, out_is_device);
     // (a tape whose register files live in HBM takes the slow path: one region per workgroup, shared by the launches of a frame, so
     // nothing of the frame runs beside anything else)
-    const bool huge = (size_t)std::max<uint32_t>(tape->t.n_regs, 1) * WAVE * 16 > FH_LDS_MAX || tiles_lds(std::max<uint32_t>(tape->t.n_regs, 1), tape->t.n_choices, 64) > FH_LDS_MAX;
-    const bool fpipe = ctx->frame_pipeline && ctx->use_pipeline && !ctx->profiling && out_is_device && !huge;
-    struct StreamGuard { fhip_ctx* c; hipStream_t s; ~StreamGuard() { c->stream = s; } } stream_guard{ctx, main_stream};
-    bool frames_queued = false;     // the frame before this one is still under way (the caller queues frames back to back)
-    bool lone = false;              // ... a pipelined context's frame with nothing under way before it
-    if (fpipe) {
+    in.huge = (size_t)std::max<uint32_t>(tape->t.n_regs, 1) * WAVE * 16 > FH_LDS_MAX || tiles_lds(std::max<uint32_t>(tape->t.n_regs, 1), tape->t.n_choices, 64) > FH_LDS_MAX;
+    in.whole = part.n_shards == 1 && part.nx * part.ny * part.nz == 1;
+    if (frame_pipelined(in)) {
         // (rotate: the current set goes to the back of the ring, the set used longest ago comes forward)
         for (uint32_t i = 0; i < ctx->extra_sets; i++) std::swap(static_cast<FrameBufs&>(*ctx), ctx->others[i]);
-        frames_queued = ctx->extra_sets > 0 && ctx->others[0].ev_done_valid && hipEventQuery(ctx->others[0].ev_done) == hipErrorNotReady;
+        // the frame before this one is still under way (the caller queues frames back to back)
+        in.frames_queued = ctx->extra_sets > 0 && ctx->others[0].ev_done_valid && hipEventQuery(ctx->others[0].ev_done) == hipErrorNotReady;
         (void)hipGetLastError();
-        // Two root levels side by side.  A frame of one coarse level whose tapes read no z (front slab only: one light tile chain, a leaf
-        // stage of 5 k leaves) is its root level and little else: 165 us of kernels in one dependent chain on the pre-pass stream against
-        // 100 on the side stream and 100 for lists + leaves + normals together - and that chain set the rate of queued frames.  Such frames
-        // take the pre-pass stream and the tail stream IN TURN for their root level, and keep what the tail stream carried (lists, normals)
-        // on the caller's stream around the leaf kernel: still four streams (a fifth shares a hardware queue with one of them and
-        // serialises against it, measured in round 2), two frames' root levels in flight.
-        R.alt_pre = ts.size() == 2 && R.xy_fixed && R.root_invariant && ctx->opt.no_zrep == 0 && ctx->stream3 &&
-                    part.n_shards == 1 && part.nx * part.ny * part.nz == 1;
-        // A frame ALONE - nothing of the frame before it is under way - keeps its coarse levels on the caller's stream: there is nothing to run
-        // beside, and every change of stream is an event's latency (prospero.vm 1024^3, one frame alone: 0.388 -> 0.33 ms).  The frame queued
-        // behind it takes the pre-pass stream as before and overlaps with it.
-        lone = !frames_queued;
-#ifdef FH_EXP_NO_LONE      // experiment (tools/build_lib_variant.py): every frame's coarse levels on the pre-pass stream, as until round 6
-        lone = false;
-#endif
-        hipStream_t const pre_stream = lone ? main_stream : (R.alt_pre && (ctx->pre_turn++ & 1u) ? ctx->stream3 : ctx->stream_pre);
-        ctx->stream = pre_stream;
-        if (ctx->ev_done_valid) HIP_TRY(ctx, hipStreamWaitEvent(pre_stream, ctx->ev_done, 0));   // the set's previous frame has left it
     }
     FH_SPAN(0);
-    st = prepare(ctx, tape, true, ts, part, R);
+    st = prepare(ctx, tape, true, tiles.ts, part, R);
     if (st) return st;
     FH_SPAN(1);
     R.zrep = R.split && R.S.pre_levels > 0 && R.xy_fixed && !ctx->opt.no_column_inv && ctx->opt.no_zrep != 1;
+    // schedule: every decision about streams, launches and slabs of this frame (frame_schedule.hpp)
+    in.pre_turn = ctx->pre_turn;
+    if (ctx->host_flags) { in.rare_seen = ctx->host_flags[2]; in.last_leaves = ctx->host_flags[3]; }
+    const FrameSchedule F = schedule_frame(R, in);
+    if (F.takes_turn) ctx->pre_turn++;
+    if (F.rare) { HIP_TRY(ctx, ctx->rare_scratch.ensure((size_t)F.rare_stride * FH_RARE_BLOCKS * 4)); ctx->rare_frames++; }      // (a set's state buffer holds four slab contexts)
+    R.S.leaf_list = F.by_list ? 1u : 0u; ctx->forked = F.pipe ? F.NC : 0;      // (what the device and the set are told of it)
+    FrameStreams fs = frame_streams(ctx, F.root);
+    if (F.fpipe && ctx->ev_done_valid) HIP_TRY(ctx, hipStreamWaitEvent(fs.on(), ctx->ev_done, 0));   // the set's previous frame has left it
+    // upload
     const size_t npix = (size_t)cfg->width * cfg->height;
     FhGeometryPixel* d_out = (FhGeometryPixel*)out;
     if (!out_is_device) { HIP_TRY(ctx, ctx->tmp_out.ensure(npix * sizeof(FhGeometryPixel))); d_out = (FhGeometryPixel*)ctx->tmp_out.p; }
-    FhRenderState* dS = (FhRenderState*)ctx->state.p;
-    // Sparse columns (option column_walk, see the leaf kernel's launch below): the frames whose tapes guarantee at most one leaf per pixel
-    // column and slab.  `by_list` (column_walk 1): their leaf stage is driven by the slab's FhLeaf records themselves - wave i of fh_columns
-    // and of fh_normals takes leaf i - instead of by the [layer][footprint] table, which for 5.5 k leaves in 1 M entries was cleared, scanned
-    // whole by k_classify3d, scanned whole again by fh_columns and walked per footprint by k_hits3d in every frame.  The push then writes no
-    // table (render_state.h leaf_list), k_classify3d and k_hits3d shrink to their rare-mode blocks, and both kernels' grids follow the leaf
-    // count the last finished frame of this context reported (host_flags[3]: a hint - waves loop over the list, any grid is right).
-    const bool sparse_columns = R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
-    const bool by_list = ctx->opt.column_walk == 1 && sparse_columns && R.split && R.zrep && R.asm_points && R.asm_normals && P.slab / 8 <= 64 && ctx->host_flags;
-    R.S.leaf_list = by_list ? 1u : 0u;
-    const uint32_t table_words = by_list ? 0u : R.table_words;
-    uint32_t list_waves = (R.n_footprints + 63) / 64 * 64;      // (no frame has reported yet: what the column walk launches)
-    if (by_list && ctx->host_flags[3]) list_waves = std::min(list_waves, (ctx->host_flags[3] + ctx->host_flags[3] / 8 + 63) / 64 * 64);
-    // (FHIP_DEBUG_ZFILL, diagnostics: every pixel already at the far depth - the front slab's leaf kernel then finds all its
-    // leaves but nothing pending, which times its per-workgroup and per-leaf set-up without the interpretation)
-    const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u},
-                                  {ctx->mind.p, R.mind_words * 4, 0u}};
-    st = upload_frame(ctx, tape, R, clear3);
+    FhRenderState* const dS0 = (FhRenderState*)ctx->state.p;
+    const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u}, {ctx->mind.p, R.mind_words * 4, 0u}};
+    st = upload_frame(ctx, fs.on(), tape, R, clear3);
     if (st) return st;
     FH_SPAN(2);
-    const uint32_t n_groups = R.groups_per_slab;
-    const uint32_t pre = R.S.pre_levels;
-    const int reset_blocks = (int)std::max<uint32_t>(1, std::min<uint32_t>(1024, (std::max(table_words, n_groups) + 255) / 256));
-    const int class_blocks = (int)((R.n_footprints + FH_CLASSIFY_FP - 1) / FH_CLASSIFY_FP);
-    // Pipelined frames: the root level stays on the pre-pass stream, the level below it moves to the head of this frame's tile
-    // chains on the side stream.  The two coarse levels of a frame are one dependent chain of ~0.9 ms that, on one stream, set
-    // the frame rate; split, the root level of frame n + 1 runs beside level 1 and the slabs of frame n, and the side stream
-    // carries level 1 + the (now few) slab steps of its own frame.  (A frame alone sees no difference: the same chain.)
-    const bool l1_side = fpipe && !lone && pre > 1 && ctx->stream2 &&
-                         ctx->use_pipeline && R.slab_hi - R.slab_lo > 1 && n_groups > 0;
-    // (option side_only_l1, on: the side stream - the busiest one of a pipelined frame, 0.43 ms of the 0.526 - carries level 1's evaluate + prune
-    // launches and nothing else: the flags of level 1's tapes are set at the end of the root level on the pre-pass stream, and what follows
-    // level 1 - the flags of its children, the frame mark, the fork of the slab contexts - goes to the stream the tile chains run on)
-    // (only for frames whose tile chains will run on the tail stream - `tiles_first` below, the same conditions: a frame with heavy leaf
-    // kernels keeps its tile chains on the side stream, and its fork must not queue behind the previous frame's tail work)
-    // Rare mode.  Four launches of a slab exist for tapes too large for the assembly kernels' register files - a leaf of more than 32
-    // registers (its points, then its normals, in the C++ kernels with an LDS file), a parent of a per-slab tile level outside the small
-    // slot list (fh_tiles_v64, then fh_tiles) - and find nothing to do in nearly every frame: prospero.vm 1024^3 0.138 -> 0.126 ms per
-    // frame without them.  While the last finished frame of this context met no such tape (k_finish3d: host_flags[2]) the slab does not
-    // make them: the last FH_RARE_BLOCKS blocks of k_classify3d, k_hits3d and k_tpush3d do their work - correct for any number of such
-    // tapes, slow for many (a wave per block, the register files in HBM), and the first frame that meets one puts the launches back.
-    {
-        const size_t need = std::max(std::max(R.lds_tiles_big, R.lds_points_big), R.lds_normals_big);
-        const size_t stride = (need + 255) / 256 * 256;
-        // (a root tape of <= 32 registers has no large leaves, but its per-slab levels still launch fh_tiles_v64 for the other slot list)
-        ctx->rare_now = R.split && R.asm_tiles && R.asm_points && R.asm_normals && !R.big_hbm && ctx->host_flags && ctx->host_flags[2] == 0 &&
-                        stride * FH_RARE_BLOCKS * 4 <= ((size_t)256 << 20);
-        if (ctx->rare_now) {
-            HIP_TRY(ctx, ctx->rare_scratch.ensure(stride * FH_RARE_BLOCKS * 4));      // (a set's state buffer holds four slab contexts)
-            ctx->rare_stride = (uint32_t)stride;
-            ctx->rare_frames++;
-        }
-    }
-    const bool rare = ctx->rare_now;
-    bool l1_only = false;
-    if (l1_side && pre == 2 && ctx->stream3 && R.asm_points) {
-        const bool pipe_plan = ctx->use_pipeline && !ctx->profiling && R.slab_hi - R.slab_lo > 1 && n_groups > 0 && !R.big_hbm;
-        const uint32_t nc_plan = pipe_plan ? std::min<uint32_t>(ctx->slab_contexts, R.slab_hi - R.slab_lo) : 1;
-        l1_only = pipe_plan && R.root_invariant && R.slab_hi - R.slab_lo <= nc_plan;      // (column_setup: no tape of the frame reads an input that changes along a pixel column)
-    }
-    if (pre && n_groups) {  // coarse levels of every slab in one go
-        for (uint32_t l = 0; l < pre; l++) {
-            const bool flags_here = R.zrep && l > 0;
-            if (l == 1 && l1_side) {
-                if (flags_here && l1_only) launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 4), dim3(WAVE), 0, ctx->stream, dS, (int)l, R.col_depmask, 0, FhFork{}); });
-                HIP_TRY(ctx, hipEventRecord(ctx->ev_l0, ctx->stream_pre));
-                HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream2, ctx->ev_l0, 0));
-                ctx->stream = ctx->stream2;
-            }
-            if (flags_here && !(l == 1 && l1_only)) launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 4), dim3(WAVE), 0, ctx->stream, dS, (int)l, R.col_depmask, 0, FhFork{}); });
-            ctx->post_v64_stream = (l == 1 && l1_only) ? ctx->stream3 : nullptr;
-            launch_tiles(ctx, R, dS, (int)l, true);
-            ctx->post_v64_stream = nullptr;
-        }
-        if (l1_only && ctx->stream != ctx->stream3) {      // (level 1 did not go through fh_tiles_v64: switch here)
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_l1, ctx->stream2));
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream3, ctx->ev_l1, 0));
-            ctx->stream = ctx->stream3;
-        }
-    }
-    // Two-stream pipeline over the z-slabs: the tile stage of a slab runs on the side stream while
-    // the leaves of the slab in front of it are evaluated on the caller's stream.  The occlusion
-    // pyramid is then one slab stale, which is still exact (depths only grow).  Two slab contexts
-    // (dS, dS + 1) alternate; each owns its leaves, leaf table, footprint lists and arena half.
-    FhRenderState* const dS0 = dS;
-    const bool pipe = ctx->use_pipeline && !ctx->profiling && R.slab_hi - R.slab_lo > 1 && n_groups > 0 && !R.big_hbm;
-    hipStream_t const side_stream = ctx->stream2;
-    const uint32_t NC = pipe ? std::min<uint32_t>(ctx->slab_contexts, R.slab_hi - R.slab_lo) : 1;     // (no more contexts than slabs: each takes its share of the arena)
-    ctx->forked = pipe ? NC : 0;
-    FhFork fork{};
-    fork.n = NC; fork.mark = (pre && n_groups) ? 1u : 0u;
-    fork.leaves = (FhLeaf*)ctx->leaves_b.p; fork.leaf_table = (FhLeafRef*)ctx->leaf_table_b.p; fork.fp_lists = (uint32_t*)ctx->fp_lists_b.p;
-    fork.leaf_cap = (size_t)R.S.leaf_cap; fork.n_footprints = (size_t)R.n_footprints; fork.hit_words = R.hit_words;
-    bool forked_here = false;
-    if (pre && n_groups) {
-        // (one coarse level - root tiles of 32^3 - in a pipelined frame: that level IS the frame's longest chain and the pre-pass stream the
-        // pacemaker of the pipeline, so what follows its push - the flags of the parked parents, the frame mark, the fork of the slab
-        // contexts - goes to the head of the tile chains on the side stream, which has no level 1 to carry in such a frame)
-        if (fpipe && !lone && pipe && pre == 1 && side_stream && side_stream != ctx->stream) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_l0, ctx->stream));
-            HIP_TRY(ctx, hipStreamWaitEvent(side_stream, ctx->ev_l0, 0));
-            ctx->stream = side_stream;
-        }
-        if (R.zrep) launch(ctx, FHIP_K_OTHER, [&] {
-            // (the fork of a pipelined frame's slab contexts - or, with ONE context, the frame mark alone - in the same launch)
-            FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 8 + 1), dim3(WAVE), 0, ctx->stream, dS, (int)pre, R.col_depmask, 1, fork);
-            forked_here = true;
-        });
-        if (!pipe && !forked_here) launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_mark_frame, dim3(1), dim3(1), 0, ctx->stream, dS); });
-    }
-    if (pipe) {
-        if (!forked_here) FH_KLAUNCH(k_fork_state, dim3(1), dim3(1), 0, ctx->stream, dS0, fork);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, ctx->stream));
-        if (ctx->stream != side_stream) HIP_TRY(ctx, hipStreamWaitEvent(side_stream, ctx->ev_fork, 0));
-    }
-    if (fpipe && ctx->stream != main_stream) {      // the rest of the frame is the caller's stream's (and the side stream's, which waits for the fork above)
-        // (one coarse level, its tail on the side stream, and tile chains to follow there: the caller's stream waits for the first tile
-        // chain's event, which lies behind everything queued so far - no event of its own for that)
-        const bool implied = pipe && pre == 1 && n_groups > 0 && side_stream && ctx->stream == side_stream;
-        if (!implied) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_pre, ctx->stream));     // (the stream the last coarse-level kernel went to)
-            HIP_TRY(ctx, hipStreamWaitEvent(main_stream, ctx->ev_pre, 0));
-        }
-        ctx->stream = main_stream;
-    }
+    st = coarse_levels(ctx, R, F, fs, dS0);
+    if (st) return st;
     FH_SPAN(3);
-    int last_tail_idx = -1;
-    // Where a slab's tile chain goes: the side stream, or (option tiles_stream = 1, pipelined frames of at most as many slabs
-    // as there are slab contexts) the tail stream, every slab's chain queued there BEFORE the tail work of the first slab - the
-    // side stream then carries level 1 of the coarse levels alone, the pre-pass stream the root level, and the three chains
-    // of consecutive frames run beside each other.
-    // (2, the default: there when the ROOT tape reads no input that changes along a pixel column - then no tape of the frame does,
-    // the leaf stage is light and the tail stream has room; a frame whose leaf kernels fill the machine wants its tile chains on
-    // the high-priority side stream: prospero.vm 1024^3 0.77 -> 0.64 ms per frame there, the same frames with the column-invariance
-    // short cuts off 1.86 -> 2.01)
-    const bool root_invariant = R.root_invariant;
-    const bool tiles_first = pipe && l1_side && root_invariant && ctx->stream3 && R.asm_points && R.slab_hi - R.slab_lo <= NC;
-    hipStream_t const tile_stream = tiles_first ? ctx->stream3 : side_stream;
-    if (tiles_first) HIP_TRY(ctx, hipStreamWaitEvent(tile_stream, ctx->ev_fork, 0));
-    auto tile_step = [&](int k, int idx) -> fhip_status {
-        dS = dS0 + (pipe ? (uint32_t)idx % NC : 0u);
-        if (pipe) {
-            ctx->stream = tile_stream;
-            if (idx >= (int)NC) HIP_TRY(ctx, hipStreamWaitEvent(tile_stream, ctx->ev_leaves[idx - (int)NC], 0));  // context free again
-        }
-        launch(ctx, FHIP_K_OTHER, [&] {
-            // the usual pyramid (three levels, 4 x 4 each, 8 x 8 leaf tiles) has a kernel of its own
-            // (up to 1024 x 1024: at 2048 x 2048 it was measured SLOWER than the generic kernel - 11.2 vs 8.2 ms per frame)
-            const bool pyr3 = P.n_levels == 3 && P.tiles[2] == 8 && P.tiles[1] == 32 && P.tiles[0] == 128 &&
-                              ((P.width + 31) / 32) * ((P.height + 31) / 32) <= 1024;
-            const bool rebuild = k != (int)R.slab_hi - 1;  // the first slab sees an empty image (pyramid pre-zeroed)
-            // (32 / 8 with its one pre-pass level: both pyramid levels rebuilt and the slab reset in one launch as well)
-            const bool pyr2 = P.n_levels == 2 && P.tiles[1] == 8 && P.tiles[0] == 32 && pre == 1;
-            if (rebuild && pyr2) {
-                const uint32_t n0 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
-                FH_KLAUNCH(k_slab_begin2, dim3(n0 + reset_blocks), dim3(256), 0, ctx->stream, dS, n0, table_words, (uint32_t)k, n_groups);
-                return;
-            }
-            if (rebuild && pyr3 && pre == 2) {
-                const uint32_t n1 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
-                FH_KLAUNCH(k_slab_begin3, dim3(n1 + reset_blocks), dim3(256), 0, ctx->stream, dS, n1, table_words, (uint32_t)k, n_groups);
-                return;
-            }
-            // (workgroups of one wave: they find room beside a leaf kernel that fills the machine - 73 us per launch on the general path with four)
-            FH_KLAUNCH(k_reset_slab, dim3(reset_blocks * 4), dim3(WAVE), 0, ctx->stream, dS, table_words, (uint32_t)k, n_groups,
-                               (pyr3 && rebuild) ? 1u : 0u);
-            if (rebuild && pyr3) {
-                const uint32_t n1 = ((P.width + 31) / 32) * ((P.height + 31) / 32);
-                FH_KLAUNCH(k_minpyramid3, dim3(n1), dim3(256), 0, ctx->stream, dS);
-            } else if (rebuild)
-                FH_KLAUNCH(k_minpyramid, dim3(P.roots_x * P.roots_y), dim3(256), 0, ctx->stream, dS);
-        });
-        for (uint32_t l = pre; l < P.n_levels; l++) launch_tiles(ctx, R, dS, (int)l, true);
-        if (pipe) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles[idx], tile_stream));
-            ctx->stream = main_stream;
-        }
-        return FHIP_OK;
-    };
-    if (tiles_first)
-        for (int k = (int)R.slab_hi - 1; k >= (int)R.slab_stop && n_groups; k--) {
-            const fhip_status ts_ = tile_step(k, (int)R.slab_hi - 1 - k);
-            if (ts_) { ctx->stream = main_stream; return ts_; }
-        }
-    for (int k = (int)R.slab_hi - 1; k >= (int)R.slab_stop && n_groups; k--) {  // front to back (voxel.rs:252-261)
-        if (ctx->is_cancelled()) { ctx->stream = main_stream; return fail(ctx, FHIP_ERR_CANCELLED, "cancelled"); }
-        const int idx = (int)R.slab_hi - 1 - k;
-        if (!tiles_first) {
-            const fhip_status ts_ = tile_step(k, idx);
-            if (ts_) { ctx->stream = main_stream; return ts_; }
-        }
-        dS = dS0 + (pipe ? (uint32_t)idx % NC : 0u);
-        hipStream_t const leaf_stream = main_stream;
-        if (pipe) HIP_TRY(ctx, hipStreamWaitEvent(leaf_stream, ctx->ev_tiles[idx], 0));
-        // The leaf kernel is the slab's critical chain.  What surrounds it - the footprint lists (needed by the normals and the
-        // LDS-class leaves only), those leaves (any order with the others: atomic-max z-buffer) and the normals of the slab's
-        // hits - are small launches that leave the machine mostly idle, so in the pipelined frame they run on a third stream
-        // beside the leaf kernel of the NEXT slab: the normals kernel only takes hits of its own slab's depth range, and a hit
-        // behind them can never replace them.  (Measured with three slab contexts, ms per frame: everything on the caller's stream 2.44, the normals only on the third stream 2.30, lists + normals 2.16 - once the min-depth pyramid kernel of the tile chain ran in blocks of four waves: its 16-wave blocks found no room beside a leaf kernel that is never interrupted, 166 us instead of 10.  FHIP_TAIL_STREAM=0 / 2 / 1.)
-        const int tail_mode = 1;   // (lists + normals on the tail stream; normals only - 2 - and off - 0 - were measured slower: DESIGN_HISTORY.md)
-        // (option tail_on_main - 0 never, 1 always, 2 when frames are queued back to back: when the tile chains run on the tail stream, the
-        // slab's small kernels stay on the caller's stream around its leaf kernel - otherwise the tail stream, serial, waits for every leaf
-        // kernel with the NEXT frame's tile chains queued behind: 0.45 ms of it per frame for 0.40 of work.  A frame alone is 70 us
-        // quicker with them beside its leaf kernels, hence the test)
-        const bool on_main = tiles_first && frames_queued;
-        const bool tail = pipe && ctx->stream3 && tail_mode > 0 && R.asm_points && !on_main && !R.alt_pre;   // (the HIP leaf kernels walk the footprint lists)
-        const uint32_t z_lo = (uint32_t)k * P.slab, z_hi = z_lo + P.slab;
-        auto classify_work = [&] {
-            // (by_list: nothing to classify - what is left of the launch is rare mode's blocks for the leaves beyond the leaf kernel's file)
-            if (by_list && rare && P.max_regs > R.S.leaf_asm_regs)
-                launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_classify3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, ctx->stream, dS, 1, 0u, rare_file(ctx, dS), ctx->rare_stride); });
-            else if (!by_list) launch(ctx, FHIP_K_OTHER, [&] {
-                FH_KLAUNCH(k_classify3d, dim3(class_blocks + (rare ? FH_RARE_BLOCKS : 0u)), dim3(P.slab / 8 > 16 ? 256 : WAVE), 0, ctx->stream, dS, R.asm_points ? 1 : 0, (uint32_t)class_blocks,
-                           rare_file(ctx, dS), ctx->rare_stride);
-            });
-            if (P.max_regs > R.S.leaf_asm_regs && !rare)      // (rare mode: in the blocks behind k_classify3d's)
-                launch(ctx, FHIP_K_POINTS, [&] {
-                    const int g = blocks_big(ctx, R, R.lds_points_big, 16);
-                    if (R.full) FH_KLAUNCH((k_leaves3d<2, 0, 1, true>), dim3(g), dim3(WAVE), R.lds_points_big, ctx->stream, dS);
-                    else FH_KLAUNCH((k_leaves3d<2, 0, 1, false>), dim3(g), dim3(WAVE), R.lds_points_big, ctx->stream, dS);
-                });
-        };
-        auto normals_work = [&] {
-#ifdef FH_EXP_SKIP_NORMALS      // experiment (tools/build_lib_variant.py): a frame without its normals kernels - what they cost beside the leaf kernels
-            return;
-#endif
-            launch(ctx, FHIP_K_NORMALS, [&] {
-                const int gs = blocks_for(ctx, R.lds_normals_small, 8), gb = blocks_big(ctx, R, R.lds_normals_big, 8);
-                if (by_list) {
-                    // (the leaf that owns a pixel's hit is its column's leaf or nobody: fh_normals takes the slab's leaves one per wave pass and
-                    // looks at the z-buffer itself; k_hits3d: rare mode's blocks for the footprints the push put on list 2)
-                    if (rare && P.max_regs > R.S.norm_asm_regs)
-                        FH_KLAUNCH(k_hits3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, ctx->stream, dS, z_lo, z_hi, R.hit_bucket_cap, 0u, rare_file(ctx, dS), ctx->rare_stride);
-                    struct { FhRenderState* S; uint32_t n_waves, slots, z_lo, z_hi, bucket_cap, mode; } kn = {dS, list_waves, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 1u};
-                    (void)launch_asm(ctx, R.asm_points_t ? FH_ASM_NORMALS_T : FH_ASM_NORMALS, kn.n_waves, &kn, sizeof(kn));
-                }
-                else if (R.asm_normals) {
-                    // (lists 0 and 1 of k_classify3d hold every footprint whose leaves need <= 32 registers - the assembly interpreter's file:
-                    // k_hits3d turns them into the list of leaves that own a hit, the normals kernel takes one leaf per wave pass)
-                    const uint32_t hb = std::min<uint32_t>(R.n_footprints, (uint32_t)ctx->n_cu * 64);
-                    FH_KLAUNCH(k_hits3d, dim3(hb + (rare ? FH_RARE_BLOCKS : 0u)), dim3(WAVE), 0, ctx->stream, dS, z_lo, z_hi, R.hit_bucket_cap, hb, rare_file(ctx, dS), ctx->rare_stride);
-                    // (wave w walks bucket w % 64 with a stride of n_waves / 64)
-                    struct { FhRenderState* S; uint32_t n_waves, slots, z_lo, z_hi, bucket_cap, pad; } kn = {dS, std::max<uint32_t>((uint32_t)(ctx->n_cu * 8) / FH_HIT_BUCKETS, 1u) * FH_HIT_BUCKETS, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 0};
-                    (void)launch_asm(ctx, R.asm_points_t ? FH_ASM_NORMALS_T : FH_ASM_NORMALS, kn.n_waves, &kn, sizeof(kn));
-                }
-                else if (R.full) FH_KLAUNCH((k_normals3d<true, false>), dim3(gs), dim3(WAVE), R.lds_normals_small, ctx->stream, dS, z_lo, z_hi);
-                else FH_KLAUNCH((k_normals3d<false, false>), dim3(gs), dim3(WAVE), R.lds_normals_small, ctx->stream, dS, z_lo, z_hi);
-                if (P.max_regs > R.S.norm_asm_regs && !(rare && R.asm_normals)) {      // (rare mode: in the blocks behind k_hits3d's)
-                    if (R.full) FH_KLAUNCH((k_normals3d<true, true>), dim3(gb), dim3(WAVE), R.lds_normals_big, ctx->stream, dS, z_lo, z_hi);
-                    else FH_KLAUNCH((k_normals3d<false, true>), dim3(gb), dim3(WAVE), R.lds_normals_big, ctx->stream, dS, z_lo, z_hi);
-                }
-            });
-        };
-        if (tail && tail_mode == 1) {
-            ctx->stream = ctx->stream3;
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream3, ctx->ev_tiles[idx], 0));
-            classify_work();
-            ctx->stream = main_stream;
-        } else classify_work();
-        launch(ctx, FHIP_K_POINTS, [&] {
-            // class 0: <= 16 registers, 4 voxels per lane; class 1: <= 32 registers, 2 per lane; class 2: LDS file
-            if (R.asm_points) {
-                // one launch for classes 0 and 1: 128 VGPRs -> 4 waves per SIMD
-                // one workgroup per block of 4 footprints of one 8-voxel layer, front layers first
-                // per-frame constants of the leaf kernel (gen_interp.py gen_columns): input slots of the axes, the inputs that change
-                // along a pixel column (a z coefficient in the axis' matrix row, or a projective matrix), projective flag
-                const uint32_t blk = 4;   // footprints per workgroup: gen_interp.py FH_BLKL = 2
-                const uint32_t n_blocks = (R.n_footprints + blk - 1) / blk;
-                // Column walk (flags bit 20): one footprint COLUMN of the slab's leaf table per wave instead of one block of four footprints
-                // of one layer.  A frame whose tapes read nothing that changes along a pixel column queues at most one leaf per column
-                // and slab (the nearest of a stack), so its table is nearly empty - prospero 1024^3: 5.5 k leaves in 1 M entries - and
-                // the (blocks, layers) grid is 262 144 workgroups of which 98 % load four empty entries and leave: 66 of the launch's
-                // 71 us.  By columns it is 16 384 waves, each with its column's 64 entries in one load.  Leaves of a column are then
-                // taken one after the other by one wave, front to back, which is wrong for frames with a leaf in most layers (the
-                // launch would last as long as its fullest column: measured in round 3, bear.vm 2.40 -> 4.07 ms): option column_walk
-                // 1 = only where the tapes guarantee sparse columns - and then by the list of leaves, `by_list` above -, 3 = the same frames
-                // by the table (parity runs), 0 never, 2 always (tests).
-                const bool by_columns = ctx->opt.column_walk == 2 || ((ctx->opt.column_walk == 1 || ctx->opt.column_walk == 3) && sparse_columns);
-                const uint32_t layers = P.slab / 8;
-                // (the slab context's leaf table, as k_fork_state lays the contexts out: the kernel takes it - with the table's shape - from its
-                // kernarg, so that a wave whose part of the table is empty leaves after one dependent load)
-                const uint32_t sk = (uint32_t)(dS - dS0);
-                const void* const slab_table = sk == 0 ? (const void*)R.S.leaf_table : (const void*)((const FhLeafRef*)ctx->leaf_table_b.p + (size_t)(sk - 1) * R.S.leaf_cap);
-                // ... and for every other frame, round 6: the column walk by GROUPS of 2^g layers (flags bits 24 .. 27, grid y = the group,
-                // front group first; option column_group = g, 0: the block walk below).  A wave keeps its footprint: the pixels' set-up,
-                // their matrix products and their z-buffer words are loaded once per wave instead of once per leaf (the z-buffer words
-                // were two thirds of the launch's HBM traffic), hits stay in registers from leaf to leaf and leave in one atomic.
-                // (a blend - few min / max, nothing to prune: bear.vm's leaves keep 350 of the root's 650 ops - wants half the group: a wave's
-                // leaves are taken one after the other, and the launch lasts as long as its fullest waves - 512^3, ms per frame by g = 0 / 1 /
-                // 2 / 3: 1.24 / 0.97 / 1.09 / 1.33; prospero.vm's 22-op leaves on the general path: 0.433 / 0.424 ms per launch by g = 1 / 2)
-                const uint32_t g_opt = (uint32_t)std::min(std::max(ctx->opt.column_group, 0), 6);
-                const uint32_t g = by_columns ? 6u : (R.smooth_tape && g_opt > 1 ? g_opt - 1 : g_opt);
-                if (by_list) {      // (flags bit 21: table = the slab context's FhLeaf records, nfpl = their capacity, pad[0] = the launch's waves)
-                    const void* const slab_leaves = sk == 0 ? (const void*)R.S.leaves : (const void*)((const FhLeaf*)ctx->leaves_b.p + (size_t)(sk - 1) * R.S.leaf_cap);
-                    struct { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; } ka =
-                        {dS, 0u, R.col_slots, R.col_depmask, R.col_flags | (3u << 20) | (6u << 24), {list_waves, 0}, slab_leaves, R.S.leaf_cap, layers};
-                    (void)launch_asm(ctx, R.asm_points_t ? FH_ASM_COLUMNS_T : FH_ASM_COLUMNS, list_waves, &ka, sizeof(ka), 0, 1, leaf_stream);
-                    return;
-                }
-                if ((by_columns && layers <= 64) || (!by_columns && g > 0)) {
-                    struct { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; } ka =
-                        {dS, 0u, R.col_slots, R.col_depmask, R.col_flags | (1u << 20) | (g << 24), {0, 0}, slab_table, R.n_footprints, layers};
-                    const int which = R.asm_points_t ? FH_ASM_COLUMNS_T : FH_ASM_COLUMNS;
-                    (void)launch_asm(ctx, which, (R.n_footprints + 63) / 64 * 64, &ka, sizeof(ka), 0, (layers + (1u << g) - 1) >> g, leaf_stream);
-                    return;
-                }
-                // (pad[0]: floor(2^32 / blocks per layer) - the kernel rotates a layer's blocks by a per-layer offset, which is what balances
-                // the launch, and takes the remainder by this reciprocal instead of a subtraction loop)
-                struct { FhRenderState* S; uint32_t n_waves, slots, depmask, flags, pad[2]; const void* table; uint32_t nfpl, layers; } ka =
-                    {dS, 0u, R.col_slots, R.col_depmask, R.col_flags, {n_blocks > 1 ? (uint32_t)(((uint64_t)1 << 32) / n_blocks) : 0u, 0}, slab_table, R.n_footprints, layers};
-                const int which = R.asm_points_t ? FH_ASM_COLUMNS_T : FH_ASM_COLUMNS;
-                (void)launch_asm(ctx, which, n_blocks, &ka, sizeof(ka), 0, P.slab / 8, leaf_stream);
-            } else if (R.full) {
-                FH_KLAUNCH((k_leaves3d<0, 16, 4, true>), dim3(ctx->n_cu * 8), dim3(WAVE), 0, ctx->stream, dS);
-                FH_KLAUNCH((k_leaves3d<1, 32, 2, true>), dim3(ctx->n_cu * 8), dim3(WAVE), 0, ctx->stream, dS);
-            } else {
-                FH_KLAUNCH((k_leaves3d<0, 16, 4, false>), dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS);
-                FH_KLAUNCH((k_leaves3d<1, 32, 2, false>), dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS);
-            }
-        });
-        if (tail) {
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[idx], leaf_stream));          // the slab's leaf kernel is through
-            ctx->stream = ctx->stream3;
-            HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream3, ctx->ev_aux[idx], 0));
-            normals_work();
-            HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], ctx->stream3));       // slab context free again; the last one: image complete
-            ctx->stream = main_stream;
-            last_tail_idx = idx;
-            continue;
-        }
-        normals_work();
-        if (pipe) HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], main_stream));
-    }
+    st = render_slabs(ctx, R, F, fs, dS0);
+    if (st) return st;
     FH_SPAN(4);
-    if (last_tail_idx >= 0) HIP_TRY(ctx, hipStreamWaitEvent(main_stream, ctx->ev_leaves[last_tail_idx], 0));   // the third stream is serial: the last slab's normals
-    launch(ctx, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_finish3d, dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS0, d_out, std::max<uint32_t>(ctx->forked, 1u), (uint32_t*)ctx->sticky.p, ctx->host_flags); });
+    // finish: the image, the overflow latches and the pinned host words, on the caller's stream
+    launch(ctx, ctx->stream, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_finish3d, dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS0, d_out, std::max<uint32_t>(ctx->forked, 1u), (uint32_t*)ctx->sticky.p, ctx->host_flags); });
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->launch_failed) { ctx->launch_failed = false; return FHIP_ERR_HIP; }   // (message in fhip_last_error)
     ctx->async_pending = out_is_device != 0;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_done, main_stream));     // (a later pipelined frame that takes this set waits for it)
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_done, ctx->stream));     // (a later pipelined frame that takes this set waits for it)
     ctx->ev_done_valid = true;
     if (ctx->opt.stats & 2) { g_spans.mark(5); g_spans.frame(); }
     if (!out_is_device) {

@@ -65,10 +65,8 @@ uint32_t fhip_tape_term_plan(const fhip_tape* tape, uint32_t info[4]) {
     return (uint32_t)tape->tgroups.size();
 }
 // Launch one of the assembly kernels: `waves` single-wave workgroups, raw kernarg block
-static hipError_t launch_asm(fhip_ctx* ctx, int which, uint32_t waves, void* args, size_t bytes, size_t lds = 0, uint32_t grid_y = 1,
-                             hipStream_t stream = nullptr) {
+static hipError_t launch_asm(fhip_ctx* ctx, hipStream_t st, int which, uint32_t waves, void* args, size_t bytes, size_t lds = 0, uint32_t grid_y = 1) {
     void* extra[] = {HIP_LAUNCH_PARAM_BUFFER_POINTER, args, HIP_LAUNCH_PARAM_BUFFER_SIZE, &bytes, HIP_LAUNCH_PARAM_END};
-    hipStream_t const st = stream ? stream : ctx->stream;
     hipEvent_t ea = nullptr, eb = nullptr;
     if (ctx->profiling) { (void)hipEventCreate(&ea); (void)hipEventCreate(&eb); (void)hipEventRecord(ea, st); }
     const hipError_t e = hipModuleLaunchKernel(ctx->asm_fn[which], waves, grid_y, 1, WAVE, 1, 1, (unsigned)lds, st, nullptr, extra);
