@@ -275,3 +275,130 @@ def test_normals_with_transcendental_opcodes(which, mat):
     got_z, got_n = run_normals(tapes, ik, mat, hits, kernel="fh_normals_t", corners=corners)
     want_z, want_n = expect(tapes, ik, mat, hits, 16)
     assert (got_z == want_z).all() and same(got_n, want_n), f"{(got_n.view(U32) != want_n.view(U32)).any(axis=1).sum()} normals differ"
+
+
+# ---- every handler of the interpreter on its own, against the float64 duals of grad_f64.py (an independent statement of the rules) ------
+import grad_f64 as G64
+import test_grad_f64 as TG
+import test_kat_bulk as KB
+
+IDENTITY = [1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1]
+TRANS_OPS = {"sin", "cos", "tan", "asin", "acos", "atan", "exp", "ln", "rand", "atan2", "mix"}    # fh_normals_t's handlers
+# modulo has no handler in the assembly (a tape with one keeps the C++ kernel, held to the same reference by tests/test_grad_f64.py and
+# tests/test_kat_bulk.py on the device): every other opcode, in every operand form the Context produces
+ASM_CASES = [(n, f) for n, f in TG.ONE_OP_CASES if n != "mod"]
+KAT_NAME = {"not": "not_", "and": "and_", "or": "or_"}
+
+
+def one_op_tape(name, form):
+    import fidget_amd as F
+    c = F.Context()
+    sh = F.Shape(c, TG.one_op_build(c, name, form))
+    tape = U.shape_tape(sh)
+    want = name.upper() if form == "r" else f"{name.upper()}_{form.upper()}"
+    assert want in [U.OPS[U.decode(w)[0]] for w in tape], f"{name} {form}: no {want} in the tape"
+    ik = [3, 3]
+    for a in range(2):
+        if sh.axis_index(a) >= 0:
+            ik[sh.axis_index(a)] = a
+    return tape, sh.slot_count(), tuple(ik)
+
+
+def run_one_ops(cases, mat):
+    """the cases' tapes as the leaves of launches of at most six tapes (the hit lists of run_normals hold that many leaves), the pixels
+    of the 16 x 16 image dealt out among them: {case: (pixel indices, normals [n, 3])}"""
+    px, py, pz, depth = TG.one_op_points()
+    out = {}
+    made = {c: one_op_tape(*c) for c in cases}
+    for trans, ik in sorted({(c[0] in TRANS_OPS, made[c][2]) for c in cases}):       # a launch has one kernel and one assignment of the input slots
+        group = [c for c in cases if (c[0] in TRANS_OPS, made[c][2]) == (trans, ik)]
+        for at in range(0, len(group), 6):
+            part = group[at:at + 6]
+            tapes, corners = leaves_of([made[c][:2] for c in part])
+            which = (np.arange(256) // 3) % len(part)                  # (runs of three pixels: every tape sees every column and row)
+            hits = {(int(px[i]), int(py[i])): (leaf_at(int(px[i]), int(py[i]), int(which[i]), len(part)), int(depth[i])) for i in range(256)}
+            got_z, got_n = run_normals(tapes, list(ik), mat, hits, kernel="fh_normals_t" if trans else "fh_normals", corners=corners)
+            assert (got_z & 0xFFFFFFFF == 0).all() and (got_z >> 32 == depth.astype(np.uint64)).all(), "not every hit was taken"
+            for k, c in enumerate(part):
+                idx = np.nonzero(which == k)[0]
+                out[c] = (idx, got_n[idx])
+    return out
+
+
+_one_ops = {}
+
+
+def one_ops(mat_name):
+    if mat_name not in _one_ops:
+        _one_ops[mat_name] = run_one_ops(ASM_CASES, {"identity": IDENTITY, "perspective": PERSPECTIVE}[mat_name])
+    return _one_ops[mat_name]
+
+
+@pytest.mark.parametrize("name,form", ASM_CASES)
+def test_one_op_identity(name, form):
+    """under the identity matrix the operands are the pixel's integer coordinates with unit seeds: the partials within K ulp of the f64
+    duals (the table of tests/test_kat_bulk.py), at every point the reference does not call discontinuous"""
+    idx, normals = one_ops("identity")[(name, form)]
+    px, py, pz, _ = TG.one_op_points()
+    x, y = [float(v) for v in px[idx]], [float(v) for v in py[idx]]
+    imm = [TG.ONE_OP_IMM] * len(idx)
+    kat = KAT_NAME.get(name, name)
+    if form == "r":
+        ref = G64._unary(name, G64.D.seed(x, 0), None)
+        keep = [p for p, a in enumerate(x) if not (kat == "rand" or (kat == "not_" and a == 0.0))]
+        kd = KB.K_UNARY[kat][1]
+        kd_of = (lambda p: kd) if kd is not None else (lambda p: KB.k_asin(x[keep[p]]))
+    else:
+        lhs, rhs, i, j = {"rr": (x, y, 0, 1), "ri": (x, imm, 0, None), "ir": (imm, x, None, 0)}[form]
+        if name in ("min", "max") and form == "ir":
+            lhs, rhs, i, j = rhs, lhs, j, i
+        ref = G64._binary(name, G64.D.seed(lhs, i), G64.D.seed(rhs, j), None)
+        keep = [p for p, (a, b) in enumerate(zip(lhs, rhs)) if not KB.discontinuous_at(kat, a, b)]
+        kd = KB.k_binary(kat, form)[1]
+        kd_of = lambda p: kd
+    # the kernel writes no value: the reference's own stands in for it
+    rows = [(float(np.float32(ref.v[p])), *(float(v) for v in normals[p])) for p in keep]
+    sub = G64.D(ref.v[keep], ref.d[keep])
+    assert len(keep) >= 10 or name in ("rand", "mix")
+    KB.tight(f"{name} {form}", rows, sub, 1, kd_of)       # (the stand-in value is the reference rounded: within half an ulp)
+
+
+@pytest.mark.parametrize("name,form", ASM_CASES)
+def test_one_op_perspective(name, form):
+    """under PERSPECTIVE the operands go through the kernel's xf_grad and its division by w: against the f64 xf and the f64 rule, within
+    the bound tests/test_grad_f64.py keeps for this opcode (4 x what the CPU oracle shows for the same expression)"""
+    idx, normals = one_ops("perspective")[(name, form)]
+    px, py, pz, _ = TG.one_op_points()
+    ref, skip = TG.one_op_reference(name, form, PERSPECTIVE, px[idx], py[idx], pz[idx])
+    keep = ~skip & np.isfinite(ref.v) & np.isfinite(ref.d).all(axis=1)
+    assert keep.sum() >= 10
+    worst = float(G64.measure(normals[keep], ref.d[keep]).max())
+    assert worst <= TG.one_op_bound(name, form), f"{name} {form}: {worst:.3e} > {TG.one_op_bound(name, form):.3e}"
+
+
+@pytest.mark.parametrize("mat", [AFFINE, ROTATED, PERSPECTIVE], ids=["affine", "rotated", "perspective"])
+@pytest.mark.parametrize("seed", [0, 1, 2, 3, 5, 6])
+def test_ref_grad_model_against_f64(seed, mat):
+    """the numpy model the kernel is held to bit for bit (ref_grad, xf_grad above), itself against the f64 duals on the random shapes of
+    test_normals_of_random_shapes, under the bound of the same shape's composed test"""
+    import fidget_amd as F
+    from test_render_random import build
+    rec = G64.Rec(F.Context())
+    root = build(rec, seed)
+    sh = F.Shape(rec.ctx, root.be)
+    tape = U.shape_tape(sh)
+    ik = [3] * 16
+    for a in range(3):
+        if sh.axis_index(a) >= 0:
+            ik[sh.axis_index(a)] = a
+    px, py, pz, _ = TG.one_op_points()
+    gx, gy, gz = xf_grad(np.asarray(mat, F32), px, py, pz)
+    n = len(px)
+    g = ref_grad(tape, {s: (gx, gy, gz)[k] if k < 3 else G.one(F32(0.25 + s), n) for s, k in enumerate(ik)}, n)
+    ax = G64.xf(mat, px, py, pz)
+    ref, near = G64.evaluate(rec, root, {0: ax[0], 1: ax[1], 2: ax[2]}, tol=TG.TOL)
+    keep = ~near & np.isfinite(ref.d).all(axis=1)
+    assert keep.mean() > 0.9
+    worst = float(G64.measure(np.stack(g.c[1:], axis=1)[keep], ref.d[keep]).max())
+    bound = 4 * max(v["measure"] for k, v in TG.bounds().items() if k.startswith("random"))
+    assert worst <= bound, f"{worst:.3e} > {bound:.3e}"

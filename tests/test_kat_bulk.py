@@ -4,12 +4,16 @@ reference's conformance suite:
   /root/reference/fidget-core/src/eval/test/float_slice.rs
   /root/reference/fidget-core/src/eval/test/grad_slice.rs
 Each test names the lines it restates.  Oracle on CPU; HIP backend with -m gpu.
+
+The gradient sweeps (test_g_unary, test_g_binary) hold every opcode to two independent criteria: the reference's own finite-difference
+check, unchanged, and value and partials within K ulp of the float64 duals of grad_f64.py (K derived below from the roundings of each rule).
 """
 import math
 
 import numpy as np
 import pytest
 
+import grad_f64 as G64
 from kat_util import (BINARY_DEFS, NAN, UNARY_DEFS, build_stress_fn, f32, f_mix, f_rand, libm, same, spicy_args)
 
 L, R, B = 1, 2, 3
@@ -431,22 +435,247 @@ def test_g_stress(be, oracle_mod, n):  # grad_slice.rs:447-493
     assert np.abs(out - ref).max() < 1e-6 * max(1.0, float(n))  # compare_eq, scaled by the gradient magnitude
 
 
-@pytest.mark.parametrize("name", [n for n in UNARY_DEFS if n not in ("rand",)])
-def test_g_unary(be, name):  # grad_slice.rs:495-644: exact value + finite-difference gradient
-    args = [a for a in spicy_args()[::3] if not math.isnan(a)]
-    ctx = be.Context()
-    s = be.Shape(ctx, getattr(ctx, name)(ctx.x()))
-    out = g(s, args)
-    fn = UNARY_DEFS[name]
-    for a, o in zip(args, out):
-        assert value_ok(be, name, o[0], fn(a)), f"{name} value at {a}"
-        if name in ("floor", "ceil", "round", "not_"):
-            assert o[1:] == (0, 0, 0)
+# ---- g_unary / g_binary: grad_slice.rs:495-778 -------------------------------
+# K: how many float32 ulp the value and a partial may lie from the float64 reference, per opcode and operand form.
+#
+# Each float32 operation rounds once: a relative error of at most 2^-24, which is less than one ulp of whatever the result later becomes.
+# A libm routine counts one more (glibc's float routines are within 1 ulp).  So K = the number of float32 roundings on the way to the
+# number, + 1 per libm call - counting every operation of the rule as the reference writes it, also those that happen to be exact here.
+# With unit seeds at most one term of a rule's numerator is non-zero (or, when both operands are the same axis, the two cancel or add
+# exactly), so no cancellation slack is part of any K.  Two rules square or difference an already-rounded number and are conditioned:
+#   tan        d / cos(v)^2: cosf (1), squared (its error twice) + the product (1) + the quotient (1)            -> 4
+#   asin, acos d / sqrt(1 - v*v): the product's rounding (1) is magnified by c = v^2 / (1 - v^2) in the difference, which rounds (1);
+#              the root halves both and rounds (1); the quotient (1)                                             -> 2.5 + c/2, rounded up
+K_UNARY = {  # name: (value, partial)
+    "neg": (0, 0), "abs": (0, 0),              # sign changes and selection: exact
+    "recip": (1, 5),                           # 1/v; (v*0 - 1*1) / (v*v): two products, a difference, a product, a quotient (vm/mod.rs:1127-1132)
+    "sqrt": (1, 3),                            # sqrtf; d / (2 * s): the root, a product, a quotient
+    "square": (1, 3),                          # v*v; v*d + v*d: two products and a sum (vm/mod.rs:1138-1143)
+    "sin": (1, 2), "cos": (1, 2),              # libm; d * cosf(v), d * -sinf(v): libm and a product
+    "tan": (1, 4),
+    "asin": (1, None), "acos": (1, None),      # None: k_asin(v) below
+    "atan": (1, 3),                            # libm; d / (v*v + 1): a product, a sum, a quotient
+    "exp": (1, 2),                             # libm; expf(v) * d
+    "ln": (1, 1),                              # libm; d / v
+    "floor": (0, 0), "ceil": (0, 0), "round": (0, 0), "not_": (0, 0), "rand": (0, 0),   # exact values, partials 0
+}
+K_BINARY = {  # name: {form: (value, partial)}; forms "rr", "ri" (reg, imm), "ir" (imm, reg)
+    "add": (1, 1), "sub": (1, 1),              # one sum / difference each
+    "mul": {"rr": (1, 3), "ri": (1, 1), "ir": (1, 1)},   # a*b' + b*a': two products and a sum; by an immediate: d * imm (vm/mod.rs:1219-1223)
+    "div": (1, 5),                             # (b*a' - a*b') / (b*b): two products, a difference, a product, a quotient
+    "atan2": (1, 7),                           # libm; (x*y' - y*x') / (x*x + y*y): 2 + 1 in the numerator, 2 + 1 in the denominator, a quotient
+    "modulo": (1, 2),                          # fmodf is exact, + |b| rounds; a' - b' * e: a product and a difference
+    "min": (0, 0), "max": (0, 0), "and_": (0, 0), "or_": (0, 0),   # selection: exact
+    "compare": (0, 0), "mix": (0, 0),          # exact values, partials 0
+}
+G64_NAME = {"not_": "not", "and_": "and", "or_": "or", "modulo": "mod"}
+
+
+def k_asin(v):
+    c = v * v / (1.0 - v * v) if abs(v) < 1 else 0.0
+    return math.ceil(2.5 + 0.5 * c)
+
+
+def k_binary(name, form):
+    k = K_BINARY[name]
+    return k[form] if isinstance(k, dict) else k
+
+
+def ulps(got, want64):
+    """|got - want| in float32 ulp of want (float64 arithmetic)"""
+    return abs(float(got) - want64) / float(np.spacing(np.float32(abs(want64))))
+
+
+def tight(label, out, ref, kv, kd_of):
+    """value and the three partials of every point within K ulp of the float64 duals `ref`.  A point where the reference's value is NaN
+    (outside the domain) asks for a NaN value and nothing else; where a component of the reference is infinite or NaN (a pole), the same
+    component of the result must not be finite either, and the point's other components - 0 * inf on the axes not seeded - are left alone.
+    Returns the largest (value, partial) distance seen, in ulp."""
+    worst_v = worst_d = 0.0
+    for p in range(len(out)):
+        o, rv, rd = out[p], float(ref.v[p]), ref.d[p]
+        if math.isnan(rv):
+            assert math.isnan(o[0]), f"{label} point {p}: value {o[0]}, the reference is NaN"
             continue
-        eps = 1e-3
-        d = (fn(f32(a + eps)) - fn(f32(a - eps))) / (f32(a + eps) - f32(a - eps))
-        if math.isfinite(d) and math.isfinite(o[1]) and abs(d) < 1e3 and not (name == "abs" and abs(a) < 2 * eps):
-            if name in ("tan", "recip", "ln", "sqrt", "asin", "acos") and (abs(o[1]) > 50 or abs(a) < 0.05):
-                continue  # near a pole: the reference skips these via its error scaling
-            assert abs(o[1] - d) < 1e-2 * max(1.0, abs(d)), f"{name} d/dx at {a}: {o[1]} vs {d}"
-        assert all(v == 0 or math.isnan(v) for v in o[2:])  # 0/NaN outside a function's domain
+        want32 = np.array([rv, *rd], np.float64).astype(np.float32)   # (a finite float64 beyond float32's range counts as infinite)
+        pole = ~np.isfinite(want32)
+        if pole.any():
+            for c in np.nonzero(pole)[0]:
+                assert not math.isfinite(o[c]), f"{label} point {p}: component {c} is {o[c]}, the reference {want32[c]}"
+            continue
+        u = ulps(o[0], rv)
+        assert u <= kv, f"{label} point {p}: value {o[0]} is {u:.2f} ulp from {rv!r} (K = {kv})"
+        worst_v = max(worst_v, u)
+        kd = kd_of(p)
+        for c in range(3):
+            u = ulps(o[1 + c], float(rd[c]))
+            assert u <= kd, f"{label} point {p}: d/d{'xyz'[c]} {o[1 + c]} is {u:.2f} ulp from {float(rd[c])!r} (K = {kd})"
+            worst_d = max(worst_d, u)
+    return worst_v, worst_d
+
+
+def est_ok(err, grad):
+    """`err.min(err / grad.abs()) < 1e-2` (f32::min / f64::min ignore a NaN operand)"""
+    rel = err / abs(grad) if grad != 0 else (math.inf if err != 0 else math.nan)
+    m = err if math.isnan(rel) else min(err, rel)
+    return m < 1e-2
+
+
+def xyz(i, v, zero, j=None, w=None):
+    """three argument lists with `v` on axis i (and `w` on axis j)"""
+    a = [zero, zero, zero]
+    a[i] = v
+    if j is not None and j != i:
+        a[j] = w
+    return a
+
+
+@pytest.mark.parametrize("name", [n for n in UNARY_DEFS if n not in ("rand",)])
+def test_g_unary(be, name):  # grad_slice.rs:495-553, as the reference runs it: EPSILON 1e-4, every argument, every seed axis
+    EPS = np.float32(1e-4)
+    args = spicy_args()
+    zero = [0.0] * len(args)
+    fn = UNARY_DEFS[name]
+    kv, kd = K_UNARY[name]
+    for i in range(3):
+        ctx = be.Context()
+        s = be.Shape(ctx, getattr(ctx, name)((ctx.x, ctx.y, ctx.z)[i]()))
+        out = g(s, *xyz(i, args, zero))
+        for a, o in zip(args, out):
+            v = fn(a)
+            assert value_ok(be, name, o[0], v), f"{name} value at {a}"
+            rest = [o[1 + k] for k in range(3) if k != i]
+            assert all(r == 0 or math.isnan(r) for r in rest)  # 0/NaN outside a function's domain
+            if name in ("floor", "ceil", "round", "not_"):
+                assert o[1:] == (0, 0, 0)
+            if name == "not_" and a == 0.0:   # discontinuous_at (eval/test/mod.rs:207)
+                continue
+            grad = float(o[1 + i])
+            if not math.isnan(v) and grad < 1e9 and not math.isinf(grad):
+                d = fn(f32(np.float32(a) + EPS))
+                err = abs((float(d) - float(v)) / float(EPS) - grad)
+                d = fn(f32(np.float32(a) - EPS))
+                err = min(err, abs((float(v) - float(d)) / float(EPS) - grad))
+                assert est_ok(err, grad), f"{name} d/d{'xyz'[i]} at {a}: {grad}, estimated within {err}"
+        # ... and the tight criterion, against the float64 duals
+        ref = G64._unary(G64_NAME.get(name, name), G64.D.seed(args, i), None)
+        kd_of = (lambda p: kd) if kd is not None else (lambda p: k_asin(args[p]))
+        wv, wd = tight(f"{name} seeded on {'xyz'[i]}", out, ref, kv, kd_of)
+        print(f"{name} axis {i}: value within {wv:.2f} ulp (K {kv}), partials within {wd:.2f} ulp (K {kd if kd is not None else 'k_asin'})")
+
+
+def discontinuous_at(name, a, b):
+    """eval/test/mod.rs:220-245"""
+    if name == "compare":
+        return a == b
+    if name == "modulo":
+        v = np.float32(a) / np.float32(b)
+        return abs(np.float32(libm("roundf", float(v))) - v) < 1e-9
+    if name in ("and_", "or_"):
+        return a == 0.0
+    return name == "mix"
+
+
+def compare_grad_results(name, i, j, lhs, rhs, out, constant_folded, label):
+    """grad_slice.rs:555-644, arithmetic widths included: the estimate of d/d(lhs) is taken in f64, those of d/d(rhs) and of the
+    shared axis in f32.  i, j: the seeded axis of each operand, 3 for an immediate."""
+    EPS = np.float32(1e-3)
+    fn = BINARY_DEFS[name]
+    F = np.float32
+
+    def ev(a, b):
+        return fn(f32(a), f32(b))
+
+    for a, b, o in zip(lhs, rhs, out):
+        v = fn(a, b)
+        assert same(o[0], v) or (math.isnan(v) and constant_folded), f"value mismatch in {label} at ({a}, {b}): {v} != {o[0]}"
+        if math.isnan(v) or discontinuous_at(name, a, b):
+            continue
+        if i == j:
+            grad = F(o[1 + i])
+            if grad < 1e9 and not np.isinf(grad):
+                err = abs((F(ev(F(a) + EPS, F(b) + EPS)) - F(v)) / EPS - grad)
+                err = min(err, abs((F(v) - F(ev(F(a) - EPS, b))) / EPS - grad))
+                assert est_ok(float(err), float(grad)), f"gradient estimate mismatch in {label} at ({a} + epsilon, {b}): {grad} ({err})"
+            continue
+        if i < 3:
+            grad = float(o[1 + i])
+            if grad < 1e9 and not math.isinf(grad):
+                err = abs((float(ev(F(a) + EPS, b)) - float(v)) / float(EPS) - grad)
+                err = min(err, abs((float(v) - float(ev(F(a) - EPS, b))) / float(EPS) - grad))
+                assert est_ok(err, grad), f"gradient estimate mismatch in {label} at ({a} + epsilon, {b}): {grad} ({err})"
+        if j < 3:
+            grad = float(o[1 + j])
+            if grad < 1e9 and not math.isinf(grad):
+                err = abs(float((F(ev(a, F(b) + EPS)) - F(v)) / EPS) - grad)
+                err = min(err, abs(float((F(v) - F(ev(a, F(b) - EPS))) / EPS) - grad))
+                assert est_ok(err, grad), f"gradient estimate mismatch in {label} at ({a}, {b} + epsilon): {grad} ({err})"
+
+
+def tight_binary(name, form, i, j, lhs, rhs, out, label):
+    """the K-ulp criterion at the points the reference does not call discontinuous (and at those alone)"""
+    keep = [p for p, (a, b) in enumerate(zip(lhs, rhs)) if not discontinuous_at(name, a, b)]
+    if not keep:
+        return 0.0, 0.0
+    a = G64.D.seed([lhs[p] for p in keep], i if i < 3 else None)
+    b = G64.D.seed([rhs[p] for p in keep], j if j < 3 else None)
+    if name in ("min", "max") and i > j:
+        # the Context orders the operands of a commutative node by handle (context/mod.rs:215-224; x, y, z, then constants, as they are made
+        # here), and a tie takes the right-hand one (grad.rs:173-195): the expression that was built is min(b, a)
+        a, b = b, a
+    ref = G64._binary(G64_NAME.get(name, name), a, b, None)
+    kv, kd = k_binary(name, form)
+    return tight(label, [out[p] for p in keep], ref, kv, lambda p: kd)
+
+
+# Strides of the sweep (the reference takes every rotation and every immediate; test_f_binary above subsamples the same way):
+#   reg,reg   every fifth rotation of the argument list against itself, all nine axis pairs
+#   immediate every fifth argument as the immediate, three axes, against the whole argument list.  (The reference also rotates the list
+#             here, which only reorders the same (argument, immediate) pairs.)
+ROT_STRIDE, IMM_STRIDE = 5, 5
+
+
+@pytest.mark.parametrize("name", list(BINARY_DEFS))
+def test_g_binary(be, name):  # grad_slice.rs:646-778
+    args = spicy_args()
+    zero = [0.0] * len(args)
+    worst = {}
+
+    def note(form, w):
+        worst[form] = tuple(max(p, q) for p, q in zip(worst.get(form, (0.0, 0.0)), w))
+
+    for rot in range(0, len(args), ROT_STRIDE):
+        rgsa = args[rot:] + args[:rot]
+        for i in range(3):
+            for j in range(3):
+                ctx = be.Context()
+                ax = (ctx.x(), ctx.y(), ctx.z())
+                s = be.Shape(ctx, getattr(ctx, name)(ax[i], ax[j]))
+                folded = s.var_count() == 0
+                out = g(s, *xyz(i, args, zero, j, rgsa))
+                rhs = args if i == j else rgsa
+                label = f"{name}(reg {'xyz'[i]}, reg {'xyz'[j]}) rotation {rot}"
+                compare_grad_results(name, i, j, args, rhs, out, folded, label)
+                if not folded:
+                    note("rr", tight_binary(name, "rr", i, j, args, rhs, out, label))
+    for imm in args[::IMM_STRIDE]:
+        for imm_first in (False, True):
+            for i in range(3):
+                ctx = be.Context()
+                v = (ctx.x, ctx.y, ctx.z)[i]()
+                s = be.Shape(ctx, getattr(ctx, name)(imm, v) if imm_first else getattr(ctx, name)(v, imm))
+                folded = s.var_count() == 0 or s.ssa_len() <= 2
+                out = g(s, *xyz(i, args, zero))
+                imms = [imm] * len(args)
+                form = "ir" if imm_first else "ri"
+                label = f"{name}({'imm, reg' if imm_first else 'reg, imm'}) on {'xyz'[i]}, imm {imm}"
+                if imm_first:
+                    compare_grad_results(name, 3, i, imms, args, out, folded, label)
+                    if not (folded and math.isnan(imm)):
+                        note(form, tight_binary(name, form, 3, i, imms, args, out, label))
+                else:
+                    compare_grad_results(name, i, 3, args, imms, out, folded, label)
+                    if not (folded and math.isnan(imm)):
+                        note(form, tight_binary(name, form, i, 3, args, imms, out, label))
+    for form, (wv, wd) in sorted(worst.items()):
+        print(f"{name} {form}: value within {wv:.2f} ulp, partials within {wd:.2f} ulp (K {k_binary(name, form)})")
