@@ -52,11 +52,11 @@ EXPORTS = [
     "fhip_ctx_create", "fhip_ctx_destroy", "fhip_ctx_trim", "fhip_ctx_reserve_arena", "fhip_libm_probe", "fhip_last_error", "fhip_ctx_sync", "fhip_cancel", "fhip_cancel_reset", "fhip_cancel_watch", "fhip_ctx_set_option", "fhip_ctx_get_option",
     "fhip_tape_from_bytecode", "fhip_tape_free", "fhip_tape_len", "fhip_tape_reg_tape", "fhip_tape_choice_count", "fhip_tape_reg_count",
     "fhip_tape_var_count", "fhip_tape_output_count", "fhip_tape_ops", "fhip_simplify", "fhip_interval_eval",
-    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge",
+    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
-    "fhip_screen_to_world", "fhip_debug_groups", "fhip_debug_ubench", "fhip_debug_math_sweep", "fhip_debug_stats", "fhip_debug_leaf_stats", "fhip_debug_tape_links", "fhip_debug_tape_chain", "fhip_debug_bench", "fhip_debug_leaves", "fhip_debug_arena", "fhip_debug_probe", "fhip_debug_trans_probe", "fhip_debug_bound_tape", "fhip_debug_lane_frames", "fhip_debug_rare_frames", "fhip_debug_lane_tune", "fhip_debug_walk_dual", "fhip_tape_group_count", "fhip_tape_group_op",
+    "fhip_screen_to_world", "fhip_debug_groups", "fhip_debug_ubench", "fhip_debug_math_sweep", "fhip_debug_stats", "fhip_debug_leaf_stats", "fhip_debug_tape_links", "fhip_debug_tape_chain", "fhip_debug_bench", "fhip_debug_leaves", "fhip_debug_arena", "fhip_debug_probe", "fhip_debug_trans_probe", "fhip_debug_bound_tape", "fhip_debug_lane_frames", "fhip_debug_rare_frames", "fhip_debug_lane_tune", "fhip_debug_walk_dual", "fhip_debug_stl_pack", "fhip_tape_group_count", "fhip_tape_group_op",
     "fhip_tape_group", "fhip_tape_term_plan", "fhip_tape_term_group", "fhip_tape_term_tree", "fhip_tape_term_choice_src",
 ]
 
@@ -175,6 +175,10 @@ def lib():
             "fhip_mesh_sample_part": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, u32, u32, C.POINTER(vp)]),
             "fhip_mesh_part_bytes": (C.c_uint64, [vp]), "fhip_mesh_part_export": (None, [vp, vp]),
             "fhip_mesh_merge": (i32, [vp, vp, vp, u32, vp, C.POINTER(vp)]),
+            "fhip_mesh_vertices_dev": (vp, [vp]), "fhip_mesh_triangles_dev": (vp, [vp]),
+            "fhip_mesh_stl_bytes": (u64, [vp]), "fhip_mesh_stl": (i32, [vp, vp, vp, i32]),
+            "fhip_mesh_vertex_grads": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, i32]),
+            "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
             "fhip_debug_stats": (i32, [vp, vp]), "fhip_debug_leaf_stats": (i32, [vp, vp]), "fhip_debug_tape_links": (u32, [vp, vp, u32]), "fhip_debug_tape_chain": (u32, [vp, vp, u32]),
@@ -1060,6 +1064,83 @@ def mesh(shape, depth, world_to_model=None, vars=None):
     return mesh_sample(shape, depth, world_to_model, vars, _build=True)
 
 
+class _DeviceArray:
+    """An array of a mesh in device memory, as `__cuda_array_interface__` (version 2) describes it; keeps the mesh's handle alive.
+    The interface's read-only flag is False - torch refuses a read-only one - but the array is the mesh's: a consumer reads it."""
+    def __init__(self, owner, ptr, shape, typestr):
+        self._owner = owner
+        self.ptr, self.shape = int(ptr), tuple(shape)
+        self.__cuda_array_interface__ = {"shape": self.shape, "typestr": typestr, "data": (self.ptr, False), "version": 2, "strides": None}
+
+
+class Mesh:
+    """A mesh of `build_mesh`: fidget_mesh::Mesh { vertices, triangles } (fidget-mesh/src/lib.rs:64-69), with what a caller does with
+    one on the device.  `.triangles` [n, 3] uint64, `.vertices` [m, 3] float32, `.counts`: the views `mesh()` returns, borrowed from the handle."""
+    def __init__(self, owner, hip, triangles, vertices, counts):
+        self._owner, self._hip = owner, hip
+        self.triangles, self.vertices, self.counts = triangles, vertices, counts
+
+    def stl(self, out=None):
+        """Mesh::write_stl's bytes (fhip_mesh_stl) as a numpy uint8 array; with `out` (a torch CUDA uint8 tensor of at least that many
+        bytes) the call is asynchronous on the context's stream and returns `out`."""
+        n = int(lib().fhip_mesh_stl_bytes(self._owner.h))
+        if out is not None:
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 1 and out.numel() >= n
+            self._hip.check(lib().fhip_mesh_stl(self._hip._h, self._owner.h, _dev_ptr(out), 1))
+            return out
+        buf = np.zeros(n, np.uint8)
+        self._hip.check(lib().fhip_mesh_stl(self._hip._h, self._owner.h, _p(buf), 0))
+        return buf
+
+    def write_stl(self, path):
+        """Mesh::write_stl (fidget-mesh/src/output.rs:5-38) to a file"""
+        with open(path, "wb") as f:
+            f.write(self.stl().tobytes())
+
+    def vertex_grads(self, shape, vars=None, out=None):
+        """fhip_mesh_vertex_grads: [m, 4] float32 {v, dx, dy, dz} of `shape` at the mesh's vertices (model space, unnormalised); with
+        `out` (a torch CUDA float32 tensor [m, 4]) the result stays on the device and `out` is returned."""
+        n = len(self.vertices)
+        vk, vv = _var_arrays(shape, vars)
+        ax = None
+        if shape._vars is not None:
+            ax = np.array(shape._vars, dtype=np.int32)
+            vk = np.array([shape._named_slot(k) for k in (vars or {})], dtype=np.uint64)
+        if out is not None:
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() == 4 * n
+            ptr, dev, res = _dev_ptr(out), 1, out
+        else:
+            res = np.zeros((n, 4), np.float32)
+            ptr, dev = _p(res), 0
+        st = lib().fhip_mesh_vertex_grads(self._hip._h, shape._h, self._owner.h, _p(ax), _p(vk), _p(vv), len(vk), ptr, dev)
+        if st == 4:
+            raise ValueError("MissingVar")
+        self._hip.check(st)
+        return res
+
+    def vertices_device(self):
+        """The vertices where the dual walk left them in device memory ([m, 3] float32), as an object carrying
+        `__cuda_array_interface__` that keeps the mesh alive - `torch.as_tensor(obj, device="cuda")` views it; None when the
+        arrays are not resident (built with keep_device off, by the host's walk, or empty)."""
+        ptr = lib().fhip_mesh_vertices_dev(self._owner.h)
+        return _DeviceArray(self._owner, ptr, (len(self.vertices), 3), "<f4") if ptr else None
+
+    def triangles_device(self):
+        """... and the triangles ([n, 3] vertex indices; "<u8", which torch takes from version 2.3 on - older ones want
+        `torch.as_tensor(obj, device="cuda")` of a copy of the interface with typestr "<i8": the indices are below 2^63)"""
+        ptr = lib().fhip_mesh_triangles_dev(self._owner.h)
+        return _DeviceArray(self._owner, ptr, (len(self.triangles), 3), "<u8") if ptr else None
+
+
+def build_mesh(shape, depth, world_to_model=None, vars=None, keep_device=True):
+    """fidget_mesh::Octree::build(...).walk_dual() as a `Mesh` object.  keep_device: context option mesh_keep_device for this build (the
+    option is restored afterwards) - the device walk's arrays stay resident for .stl(), .vertex_grads() and the *_device() views."""
+    hip = shape.hip
+    with hip.options(mesh_keep_device=1 if keep_device else 0):
+        owner, tris, verts, counts = mesh_sample(shape, depth, world_to_model, vars, _build=True, _owner=True)
+    return Mesh(owner, hip, tris, verts, counts)
+
+
 def mesh_part(shape, depth, part, n_parts, world_to_model=None, vars=None, alloc=None):
     """The device side of a mesh build for part `part` of `n_parts` (the root's octants o with o * n_parts // 8 == part;
     fhip_mesh_sample_part), as the flat uint8 buffer fhip_mesh_part_export writes: what a rank sends to the merging rank.
@@ -1113,7 +1194,7 @@ def mesh_merge(parts, world_to_model=None, hip=None):
     return tris, verts, {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
 
 
-def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False):
+def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False, _owner=False):
     """The evaluation side of fidget_mesh::Octree::build on the device (fhip_mesh_sample): returns (leaf records as a
     MESH_LEAF array, counts dict)."""
     hip = shape.hip
@@ -1140,7 +1221,7 @@ def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False):
             h = None
             verts = owner.view(lib().fhip_mesh_vertices_ptr(owner.h), (int(c[6]), 3), np.float32)
             tris = owner.view(lib().fhip_mesh_triangles_ptr(owner.h), (int(c[7]), 3), np.uint64)
-            return tris, verts, counts
+            return (owner, tris, verts, counts) if _owner else (tris, verts, counts)
         leaves = np.zeros(int(c[3]), MESH_LEAF)
         if len(leaves):
             lib().fhip_mesh_leaves(h, _p(leaves))

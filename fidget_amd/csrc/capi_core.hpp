@@ -81,9 +81,9 @@ static const char* const FH_ASM_NAMES[FH_ASM_COUNT] = {"fh_columns", "fh_float_e
        column_walk: the leaf kernel by footprint columns - 1 in frames whose tapes read no z, and then by the slab's list of leaves (no leaf table, k_classify3d, k_hits3d), 3 the same frames by the table, 0 never, 2 always; column_group: every other frame by groups of 2^g layers of a column (0: by blocks of four footprints of a layer) */                  \
     X(no_column_inv, 0) X(no_zrep, 0) X(root32_max, 4096) X(column_walk, 1) X(column_group, 2)                                                    \
     /* pipelining and resources */                                                                                             \
-    X(no_pipeline, 0) X(frame_lanes, 4) X(lanes_tune, 1) X(lanes_fail, 0) X(slab_layers, 4) X(arena_mb, 4096)  \
-    /* mesher */                                                                                                               \
-    X(mesh_device_assembly, 1) X(mesh_device_walk, 1) X(mesh_simplify_min_ops, 256)                                             \
+    X(no_pipeline, 0) X(frame_lanes, 4) X(lanes_fail, 0) X(slab_layers, 4) X(arena_mb, 4096)  \
+    /* mesher (mesh_keep_device: a mesh of the device walk keeps its vertices and triangles in HBM, fhip_mesh_vertices_dev) */      \
+    X(mesh_device_assembly, 1) X(mesh_device_walk, 1) X(mesh_simplify_min_ops, 256) X(mesh_keep_device, 0)                      \
     /* diagnostics (stats: bit 0 device counters and clocks, bit 1 the host thread's time per frame to stderr) */                                                                                                          \
     X(probe, 0) X(stats, 0)
 struct FhOptions {
@@ -213,7 +213,7 @@ struct fhip_ctx : FrameBufs {
     bool ev_last_valid = false;
     // Which of the two arrangements a queued 3D frame takes is MEASURED, per (tape, image size): consecutive queued frames of one kind
     // run a window under the stage pipeline, then one on the lanes, each timed between two events on the caller's stream, and the
-    // faster arrangement is kept (capi_render.hpp lane_mode; option lanes_tune)
+    // faster arrangement is kept (capi_render.hpp lane_mode)
     struct LaneTune {
         uint64_t key = 0, used = 0;
         int phase = 0;               // 0 / 1 / 2: windows under the stage pipeline, on the lanes, under the stage pipeline again; 3 waiting for the last window's end; 4 decided

@@ -84,6 +84,11 @@ struct fhip_mesh {
     uint64_t sub_skipped = 0;                            // ... or how many there would have been, when they were not worth using
     uint64_t sub_tapes = 0, sub_ops = 0;                 // tapes simplified at the split level and their ops together (0: the root tape everywhere)
     uint32_t depth = 0, part = 0, n_parts = 1;           // fhip_mesh_sample_part: which of the root's octants this one covers
+    // option mesh_keep_device: `vertices` and `triangles` where the device walk left them in HBM - taken out of the walk's allocator
+    // (WalkDevX::forget), not copied - and owned by the mesh from then on; null: not resident (the host's walk, a merged mesh, an empty one)
+    fhmesh::V3* d_vertices = nullptr;
+    uint64_t* d_triangles = nullptr;
+    ~fhip_mesh() { if (d_vertices) (void)hipFree(d_vertices); if (d_triangles) (void)hipFree(d_triangles); }
 };
 // Assembly of the octree from the device's results, as Octree::recurse unwinds (octree.rs:556-583), then Octree::walk_dual
 struct MeshAssembler {
@@ -884,6 +889,10 @@ static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t dep
                         if (i < nv_ch) memcpy((char*)M->vertices.data() + i * CH, pv + i * CH, std::min(CH, vbytes - i * CH));
                         else { const size_t j = i - nv_ch; memcpy((char*)M->triangles.data() + j * CH, pt + j * CH, std::min(CH, tbytes - j * CH)); }
                     });
+                    if (ctx->opt.mesh_keep_device) {     // the mesh keeps the two arrays (fhip_mesh_vertices_dev): everything else of the walk goes
+                        w.forget(wo.verts); w.forget(wo.tris);
+                        M->d_vertices = wo.verts; M->d_triangles = wo.tris;
+                    }
                     w.release();
                     x.release();
                     M->octree_cells = oo.n_blocks; M->octree_verts = oo.n_verts;
@@ -1159,3 +1168,135 @@ void fhip_mesh_counts(const fhip_mesh* m, uint64_t out[8]) {
     out[5] = m->per_level.size(); out[6] = m->vertices.size(); out[7] = m->triangles.size();
 }
 void fhip_mesh_leaves(const fhip_mesh* m, void* out) { memcpy(out, m->leaves.data(), m->leaves.size() * sizeof(FhMeshLeaf)); }
+
+// ---- what a caller does with a finished mesh, on the device: Mesh::write_stl (fidget-mesh/src/output.rs:5-38) and gradients at its vertices ----
+const float* fhip_mesh_vertices_dev(const fhip_mesh* m) { return m ? (const float*)m->d_vertices : nullptr; }
+const uint64_t* fhip_mesh_triangles_dev(const fhip_mesh* m) { return m ? m->d_triangles : nullptr; }
+uint64_t fhip_mesh_stl_bytes(const fhip_mesh* m) { return fhm::FH_STL_HEADER + (uint64_t)fhm::FH_STL_RECORD * (m ? m->triangles.size() : 0); }
+// `bytes` from device memory to a host buffer of the caller's through the context's pinned landing area, as a built mesh travels
+static fhip_status mesh_to_host(fhip_ctx* ctx, void* dst, const void* d_src, size_t bytes) {
+    if (!bytes) return FHIP_OK;
+    if (ctx->mesh_pinned_cap < bytes) {
+        if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
+        ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
+        HIP_TRY(ctx, hipHostMalloc(&ctx->mesh_pinned, bytes + bytes / 8, hipHostMallocDefault));
+        ctx->mesh_pinned_cap = bytes + bytes / 8;
+    }
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->mesh_pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    const size_t CH = (size_t)4 << 20;
+    fhmesh::parallel_for((bytes + CH - 1) / CH, [&](size_t i) { memcpy((char*)dst + i * CH, (const char*)ctx->mesh_pinned + i * CH, std::min(CH, bytes - i * CH)); });
+    return FHIP_OK;
+}
+// host arrays to the context's buffer `b`; waits, so that the caller's arrays are free again when the call returns
+static fhip_status mesh_upload(fhip_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
+    HIP_TRY(ctx, b.ensure(std::max<size_t>(bytes, 4)));
+    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
+    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
+    return FHIP_OK;
+}
+// k_mesh_stl over device arrays; `out`: the caller's device buffer (asynchronous), or a host buffer (filled when the call returns)
+static fhip_status stl_pack(fhip_ctx* ctx, const fhmesh::V3* d_verts, const uint64_t* d_tris, uint64_t n_tris, void* out, int out_is_device) {
+    const size_t bytes = fhm::FH_STL_HEADER + (size_t)fhm::FH_STL_RECORD * n_tris;
+    void* d_out = out;
+    if (out_is_device) {
+        if ((uintptr_t)out & 3u) return fail(ctx, FHIP_ERR_UNSUPPORTED, "STL to the device: the buffer must be 4-byte aligned");
+    } else {
+        HIP_TRY(ctx, ctx->io_d.ensure(bytes));
+        d_out = ctx->io_d.p;
+    }
+    static const char text[] = "This is a binary STL file exported by Fidget";       // output.rs:14
+    fhm::FhStlHeader H;
+    memset(&H, 0, sizeof(H));
+    memcpy(H.w, text, sizeof(text) - 1);
+    H.w[fhm::FH_STL_HEADER / 4 - 1] = (uint32_t)n_tris;
+    const uint32_t grid = std::max<uint32_t>(1, (uint32_t)((n_tris + fhm::FH_STL_TRIS - 1) / fhm::FH_STL_TRIS));
+    hipLaunchKernelGGL(fhm::k_mesh_stl, dim3(grid), dim3(256), 0, ctx->stream, d_verts, d_tris, (uint32_t)n_tris, H, (uint32_t*)d_out);
+    HIP_TRY(ctx, hipGetLastError());
+    return out_is_device ? FHIP_OK : mesh_to_host(ctx, out, d_out, bytes);
+}
+fhip_status fhip_mesh_stl(fhip_ctx* ctx, const fhip_mesh* m, void* out, int out_is_device) {
+    if (!ctx || !m || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_mesh_stl: context, mesh and output buffer");
+    if (m->triangles.size() >= (1ull << 32)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "binary STL counts its triangles in 32 bits");
+    (void)hipSetDevice(ctx->device);
+    const fhmesh::V3* dv = m->d_vertices;
+    const uint64_t* dt = m->d_triangles;
+    if (!dv || !dt) {       // not resident (the host's walk, a merged mesh): the host arrays go up first
+        fhip_status st = mesh_upload(ctx, ctx->io_a, m->vertices.data(), m->vertices.size() * sizeof(fhmesh::V3));
+        if (!st) st = mesh_upload(ctx, ctx->io_b, m->triangles.data(), m->triangles.size() * 24);
+        if (st) return st;
+        dv = (const fhmesh::V3*)ctx->io_a.p; dt = (const uint64_t*)ctx->io_b.p;
+    }
+    return stl_pack(ctx, dv, dt, m->triangles.size(), out, out_is_device);
+}
+// (tests: the packing on counts a real mesh does not give - the walk emits triangles in pairs)
+fhip_status fhip_debug_stl_pack(fhip_ctx* ctx, const float* verts, uint64_t n_verts, const uint64_t* tris, uint64_t n_tris, void* out) {
+    if (!ctx || !out || (n_tris && (!verts || !tris))) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_debug_stl_pack: context, arrays and output buffer");
+    if (n_tris >= (1ull << 32)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "binary STL counts its triangles in 32 bits");
+    for (uint64_t i = 0; i < n_tris * 3; i++) if (tris[i] >= n_verts) return fail(ctx, FHIP_ERR_BAD_TAPE, "a triangle names a vertex the array does not have");
+    (void)hipSetDevice(ctx->device);
+    fhip_status st = mesh_upload(ctx, ctx->io_a, verts, (size_t)n_verts * sizeof(fhmesh::V3));
+    if (!st) st = mesh_upload(ctx, ctx->io_b, tris, (size_t)n_tris * 24);
+    if (st) return st;
+    return stl_pack(ctx, (const fhmesh::V3*)ctx->io_a.p, (const uint64_t*)ctx->io_b.p, n_tris, out, 0);
+}
+// VmGradSliceEval::eval (vm/mod.rs:1091-1397) at the mesh's vertices.  The binding is fhip_mesh_build's (bind_inputs), for any number of
+// input slots: the axes' slots go to the kernel as they are, every other slot's value through a table of one float per slot.
+fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const fhip_mesh* m, const int32_t* axis_slots, const uint64_t* var_keys,
+                                   const float* var_values, uint32_t n_vars, float* out, int out_is_device) {
+    if (!ctx || !tape || !m) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_mesh_vertex_grads: context, tape and mesh");
+    const fh::HostTape& t = tape->t;
+    if (t.n_outputs != 1) return fail(ctx, FHIP_ERR_BAD_TAPE, "shape tapes have exactly one output");
+    const uint32_t n_slots = std::max<uint32_t>(t.n_vars, 1);
+    std::vector<float> values(n_slots, 0.0f);
+    std::vector<char> bound(n_slots, 0);
+    int ax[3];
+    for (int a = 0; a < 3; a++) {
+        ax[a] = axis_slots ? axis_slots[a] : t.vars.axis[a];
+        if (ax[a] >= 0 && (uint32_t)ax[a] < n_slots) bound[ax[a]] = 1;
+    }
+    for (uint32_t i = 0; i < n_vars; i++) {
+        const int s = axis_slots ? (int)var_keys[i] : t.vars.slot_of(3, var_keys[i]);
+        if (s >= 0 && (uint32_t)s < n_slots) { values[s] = var_values[i]; bound[s] = 1; }
+    }
+    for (uint32_t s = 0; s < t.n_vars; s++)
+        if (!bound[s]) return fail(ctx, FHIP_ERR_MISSING_VAR, "a variable of the shape has no value");
+    const uint64_t n = m->vertices.size();
+    if (n == 0) return FHIP_OK;
+    if (!out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_mesh_vertex_grads: no output buffer");
+    if (out_is_device && ((uintptr_t)out & 15u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "gradients to the device: the buffer must be 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    { fhip_status ts_ = tape_to_device(ctx, tape); if (ts_) return ts_; }
+    const fhmesh::V3* dv = m->d_vertices;
+    if (!dv) {
+        const fhip_status st = mesh_upload(ctx, ctx->io_a, m->vertices.data(), (size_t)n * sizeof(fhmesh::V3));
+        if (st) return st;
+        dv = (const fhmesh::V3*)ctx->io_a.p;
+    }
+    HIP_TRY(ctx, ctx->io_c.ensure((size_t)n_slots * 4));
+    HIP_TRY(ctx, hipMemcpyAsync(ctx->io_c.p, values.data(), (size_t)n_slots * 4, hipMemcpyHostToDevice, ctx->stream));     // (pageable memory: read before the copy call returns)
+    float4* d_out = (float4*)out;
+    if (!out_is_device) { HIP_TRY(ctx, ctx->io_d.ensure((size_t)n * 16)); d_out = (float4*)ctx->io_d.p; }
+    const uint32_t nr = std::max<uint32_t>(t.n_regs, 1);
+    const size_t file = (size_t)nr * WAVE * sizeof(GR);
+    const bool g = file > FH_LDS_MAX;        // register file too large for LDS: a global slab, at most 1 GiB of it
+    const uint64_t blocks = (n + WAVE - 1) / WAVE;
+    const uint32_t grid = (uint32_t)std::min<uint64_t>(blocks, g ? std::max<size_t>(1, ((size_t)1 << 30) / file) : (uint64_t)1 << 30);
+    if (g) {
+        HIP_TRY(ctx, ctx->io_e.ensure(file * grid));
+        hipLaunchKernelGGL(fhm::k_mesh_vertex_grads<true>, dim3(grid), dim3(WAVE), 0, ctx->stream, tape->d_ops, (uint32_t)t.ops.size(), nr, dv, n, ax[0], ax[1], ax[2],
+                           (const float*)ctx->io_c.p, d_out, (GR*)ctx->io_e.p);
+    } else {
+        {   // (function attributes are per device)
+            static std::mutex attr_lock;
+            static bool attr_done[64] = {};
+            std::lock_guard<std::mutex> guard(attr_lock);
+            const int d = ctx->device & 63;
+            if (!attr_done[d]) { (void)hipFuncSetAttribute((const void*)fhm::k_mesh_vertex_grads<false>, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX); attr_done[d] = true; }
+        }
+        hipLaunchKernelGGL(fhm::k_mesh_vertex_grads<false>, dim3(grid), dim3(WAVE), file, ctx->stream, tape->d_ops, (uint32_t)t.ops.size(), nr, dv, n, ax[0], ax[1], ax[2],
+                           (const float*)ctx->io_c.p, d_out, (GR*)nullptr);
+    }
+    HIP_TRY(ctx, hipGetLastError());
+    return out_is_device ? FHIP_OK : mesh_to_host(ctx, out, d_out, (size_t)n * 16);
+}

@@ -1207,7 +1207,6 @@ static bool lane_mode(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_
     const bool possible = lanes_possible(ctx, out_is_device) && ctx->use_pipeline && ctx->frame_pipeline;
     const bool prior = ctx->use_asm && !ctx->opt.no_columns_t && !tape_asm_ok(tape->t);
     if (!possible) { ctx->tune_last_key = 0; return false; }       // (a frame alone, a profiled frame, ...: the stage pipeline; the sequence is broken)
-    if (!ctx->opt.lanes_tune) return prior;
     uint64_t key = (tape->parent_serial ? tape->parent_serial : tape->serial) * 0x9E3779B97F4A7C15ull;   // (a bound tape: its parent's entry)
     key ^= ((uint64_t)cfg->width << 42) ^ ((uint64_t)cfg->height << 21) ^ (uint64_t)cfg->depth;
     key ^= (((uint64_t)part.shard * 64 + part.n_shards) * 0xD6E8FEB86659FD93ull) ^ ((((uint64_t)part.ix * 16 + part.iy) * 16 + part.iz) * 4096 + (part.nx * 16 + part.ny) * 16 + part.nz) * 0xA24BAED4963EE407ull;

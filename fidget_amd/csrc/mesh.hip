@@ -19,6 +19,10 @@
 //                 bottom-up what every ambiguous cell becomes, top-down where its vertices and its block of eight cells go.
 //   k_walk_* / k_scan_*   Octree::walk_dual (dc.rs, builder.rs) on that octree: the recursion's calls as level arrays in call order, the
 //                 mesh's vertices numbered by first use through atomic minima and prefix sums (mesh_walk.hpp).
+//   k_mesh_stl    Mesh::write_stl (fidget-mesh/src/output.rs:14-36): the binary STL file of a mesh, 256 triangles per block, the records
+//                 put together in LDS and stored as whole dwords;
+//   k_mesh_vertex_grads   the tape's value and gradient at every vertex of a mesh (VmGradSliceEval::eval, vm/mod.rs:1091-1397): one
+//                 vertex per lane, read from the V3 array where the dual walk left it.
 #pragma once
 #include <hip/hip_runtime.h>
 
@@ -516,6 +520,74 @@ __global__ void __launch_bounds__(WAVE) k_mesh_leaf_qef(const FhMdcTable* T, FhM
         if (!forced) q.solve(pos, &err);
         for (int a = 0; a < 3; a++) o->vert[vtx][a] = pos[a];
         o->qef_err[vtx] = err;
+    }
+}
+
+// ---- Mesh::write_stl (fidget-mesh/src/output.rs:14-36) ----------------------------------------------------------------------------------
+// The file: 80 bytes of header (44 of text, zeros), the triangle count as a little-endian u32, then 50 bytes per triangle: normal =
+// (b - a) x (c - a) in f32, the corners a, b, c, two zero bytes.  The cross product is nalgebra's, which is not vendored here: the operand
+// order below - x = u.y v.z - u.z v.y, y = u.z v.x - u.x v.z, z = u.x v.y - u.y v.x, every product and every difference rounded to f32
+// (the library is built with -ffp-contract=off) - is RECALLED from its source and could not be verified against it; another order of the
+// same products can only change the sign of a zero.  The normal is not normalised (output.rs:20).
+// A block packs 256 triangles: every thread gathers its three vertices and writes its record into LDS (12 800 bytes), the block then
+// stores its span as coalesced dwords - 84 and 12 800 are multiples of 4, so every block starts on a dword of `out` (which must be
+// 4-byte aligned).  A last block with an odd number of triangles ends with a 16-bit store; nothing is written at or beyond
+// 84 + 50 n_tris.  Block 0 writes the header and the count (the 21 dwords of H).
+constexpr uint32_t FH_STL_TRIS = 256, FH_STL_HEADER = 84, FH_STL_RECORD = 50;
+struct FhStlHeader { uint32_t w[FH_STL_HEADER / 4]; };
+__global__ void __launch_bounds__(256) k_mesh_stl(const fhmesh::V3* __restrict__ verts, const uint64_t* __restrict__ tris, uint32_t n_tris, FhStlHeader H,
+                                                   uint32_t* __restrict__ out) {
+    __shared__ uint32_t rec32[FH_STL_TRIS * FH_STL_RECORD / 4];
+    uint16_t* const rec = (uint16_t*)rec32;
+    const uint32_t tid = threadIdx.x, first = blockIdx.x * FH_STL_TRIS;        // (first <= n_tris: the grid is ceil(n_tris / 256), one block for none)
+    const uint32_t cnt = min(FH_STL_TRIS, n_tris - first);
+    if (blockIdx.x == 0 && tid < FH_STL_HEADER / 4) out[tid] = H.w[tid];
+    if (tid < cnt) {
+        const uint64_t* q = tris + (size_t)(first + tid) * 3;
+        const fhmesh::V3 a = verts[q[0]], b = verts[q[1]], c = verts[q[2]];
+        const float ux = b.x - a.x, uy = b.y - a.y, uz = b.z - a.z;
+        const float vx = c.x - a.x, vy = c.y - a.y, vz = c.z - a.z;
+        const float f[12] = {uy * vz - uz * vy, uz * vx - ux * vz, ux * vy - uy * vx, a.x, a.y, a.z, b.x, b.y, b.z, c.x, c.y, c.z};
+        uint16_t* r = rec + tid * (FH_STL_RECORD / 2);      // (a record starts on an even byte, every second one not on a dword: halves)
+#pragma unroll
+        for (int k = 0; k < 12; k++) {
+            const uint32_t bits = __float_as_uint(f[k]);
+            r[2 * k] = (uint16_t)(bits & 0xFFFFu); r[2 * k + 1] = (uint16_t)(bits >> 16);
+        }
+        r[24] = 0;      // the attribute byte count
+    }
+    __syncthreads();
+    const uint32_t bytes = cnt * FH_STL_RECORD, n_dw = bytes >> 2;
+    uint32_t* const dst = out + FH_STL_HEADER / 4 + (size_t)blockIdx.x * (FH_STL_TRIS * FH_STL_RECORD / 4);
+    for (uint32_t i = tid; i < n_dw; i += 256) dst[i] = rec32[i];
+    if ((bytes & 2u) && tid == 0) *(uint16_t*)(dst + n_dw) = rec[2 * n_dw];
+}
+
+// ---- gradients at a mesh's vertices -----------------------------------------------------------------------------------------------------
+// out[i] = {v, dx, dy, dz} of the tape at vertex i (model space: octree.rs:58-65 has already taken the vertices there), x / y / z seeded
+// (1,0,0) / (0,1,0) / (0,0,1) in registers, every other input slot the constant values[slot] with a zero gradient.  The interpreter is
+// k_eval_grad's (step<GRAD>), the register file in LDS, or - GREGS - this block's region of a global slab when n_regs x 64 x 16 bytes
+// exceed LDS; a block takes 64 vertices at a time, as many times as the grid needs to cover them (the slab bounds the grid).
+template <bool GREGS>
+__global__ void __launch_bounds__(WAVE) k_mesh_vertex_grads(const uint64_t* __restrict__ tape_g, uint32_t len, uint32_t n_regs, const fhmesh::V3* __restrict__ verts, uint64_t n,
+                                                             int sx, int sy, int sz, const float* __restrict__ values, float4* __restrict__ out, GR* gregs) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const ctape_t tape = (ctape_t)tape_g;
+    const int lane = threadIdx.x;
+    Regs<GR, WAVE> R{GREGS ? gregs + (size_t)blockIdx.x * n_regs * WAVE : (GR*)smem, lane};
+    for (uint64_t base = (uint64_t)blockIdx.x * WAVE; base < n; base += (uint64_t)gridDim.x * WAVE) {
+        const uint64_t i = base + (uint64_t)lane;
+        const bool act = i < n;
+        const fhmesh::V3 p = verts[act ? i : n - 1];
+        const GR gx = gr(p.x, 1.0f, 0.0f, 0.0f), gy = gr(p.y, 0.0f, 1.0f, 0.0f), gz = gr(p.z, 0.0f, 0.0f, 1.0f);
+        for (uint32_t k = 0; k < len; k++) {
+            const uint64_t w = tape[k];
+            step<GRAD, WAVE, true>(
+                w, R,
+                [&](uint32_t slot) { return (int)slot == sz ? gz : ((int)slot == sy ? gy : ((int)slot == sx ? gx : gr(values[slot], 0.0f, 0.0f, 0.0f))); },     // (bind_inputs: a slot two axes share is the later axis')
+                [&](uint32_t, GR v) { if (act) out[i] = make_float4(v.v, v.dx, v.dy, v.dz); },
+                [&](int) {});
+        }
     }
 }
 

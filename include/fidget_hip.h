@@ -309,6 +309,33 @@ uint64_t fhip_mesh_part_bytes(const fhip_mesh* mesh);
 void fhip_mesh_part_export(const fhip_mesh* mesh, void* out);
 fhip_status fhip_mesh_merge(fhip_ctx* ctx, const void* const* parts, const uint64_t* part_bytes, uint32_t n_parts, const float* world_to_model,
                             fhip_mesh** out);
+/* The mesh where the device left it.  Context option "mesh_keep_device" (default 0) = 1: a mesh that fhip_mesh_build makes with the
+ * device walk keeps `Mesh { vertices, triangles }` (fidget-mesh/src/lib.rs:64-69) in device memory as well - n x 3 f32 and n x 3 u64,
+ * the arrays of fhip_mesh_vertices_ptr / fhip_mesh_triangles_ptr - for a consumer on the device.  They belong to the mesh:
+ * fhip_mesh_free frees them, fhip_ctx_trim does not touch them.  NULL when the arrays are not resident: the option was off, the walk
+ * ran on the host ("mesh_device_walk" 0, an octree beyond the device walk's limits), the mesh came from fhip_mesh_merge, or it is empty. */
+const float* fhip_mesh_vertices_dev(const fhip_mesh* mesh);
+const uint64_t* fhip_mesh_triangles_dev(const fhip_mesh* mesh);
+/* Mesh::write_stl (fidget-mesh/src/output.rs:5-38) on the device: the binary STL file of the mesh, byte for byte - the 44 bytes of header
+ * text zero-padded to 80, the triangle count as a little-endian u32, then 50 bytes per triangle: normal = (b - a) x (c - a) in f32, not
+ * normalised (output.rs:20-26), the corners a, b, c, two zero bytes (output.rs:27-35).  The cross product is nalgebra's, which is not
+ * vendored with the reference: x = u.y v.z - u.z v.y, y = u.z v.x - u.x v.z, z = u.x v.y - u.y v.x, each product and each difference
+ * rounded to f32, is recalled from its source and could not be verified against it; another order of the same operands can only change
+ * the sign of a zero.  fhip_mesh_stl_bytes = 84 + 50 x triangles is the size of `out`.  Resident arrays (above) are read in place; a mesh
+ * without them has its host arrays uploaded first.  out_is_device != 0: `out` is a device pointer (4-byte aligned) and the call is
+ * asynchronous on the context's stream; otherwise the bytes arrive in the host buffer through the context's pinned landing area.
+ * FHIP_ERR_UNSUPPORTED before any launch: 2^32 triangles or more (the format's count is 32 bits wide). */
+uint64_t fhip_mesh_stl_bytes(const fhip_mesh* mesh);
+fhip_status fhip_mesh_stl(fhip_ctx* ctx, const fhip_mesh* mesh, void* out, int out_is_device);
+/* BulkEvaluator<Data = Grad>::eval (VmGradSliceEval::eval, vm/mod.rs:1091-1397) at the mesh's vertices, without the round trip through
+ * the host that fhip_grad_eval needs: out = n_vertices x Grad {v, dx, dy, dz} (types/grad.rs:4-13) of `tape` at vertex i, x / y / z
+ * seeded (1,0,0) / (0,1,0) / (0,0,1), every Var::V bound to its value with a zero gradient.  The vertices are in model space already
+ * (octree.rs:58-65), so no transform is applied: the gradient is the model-space one, unnormalised as GeometryPixel::normal
+ * (voxel.rs:122-134), and v says how far the vertex sits from the surface.  `tape`: any one-output tape (FHIP_ERR_BAD_TAPE otherwise), of
+ * any number of input slots; the variable arguments are fhip_mesh_build's (FHIP_ERR_MISSING_VAR likewise).  The whole tape runs at every
+ * vertex.  out_is_device != 0: a device pointer (16-byte aligned), asynchronous on the context's stream when the arrays are resident. */
+fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const fhip_mesh* mesh, const int32_t* axis_slots,
+                                   const uint64_t* var_keys, const float* var_values, uint32_t n_vars, float* out, int out_is_device);
 
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's

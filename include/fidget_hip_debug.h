@@ -66,6 +66,10 @@ uint32_t fhip_debug_groups(fhip_ctx* ctx, int kind, uint32_t index, void* out, u
  * then again with buffers of 3 u64 per triangle and 3 floats per vertex. */
 void fhip_debug_walk_dual(const uint32_t* cells, uint64_t n_cells, const uint32_t* root, const float* verts, uint64_t n_verts, int parallel,
                           uint64_t counts[2], uint64_t* tris, float* verts_out);
+/* The kernel of fhip_mesh_stl on arrays given by the caller (host buffers: verts [n_verts][3] floats, tris [n_tris][3] vertex indices,
+ * out 84 + 50 n_tris bytes): the packing on triangle counts a real mesh does not produce (the dual walk emits triangles in pairs).
+ * FHIP_ERR_BAD_TAPE: an index beyond n_verts. */
+fhip_status fhip_debug_stl_pack(fhip_ctx* ctx, const float* verts, uint64_t n_verts, const uint64_t* tris, uint64_t n_tris, void* out);
 
 #ifdef __cplusplus
 }

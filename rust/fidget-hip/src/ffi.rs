@@ -102,6 +102,13 @@ extern "C" {
     pub fn fhip_mesh_vertices_ptr(mesh: *const fhip_mesh) -> *const f32;       // the arrays where the mesh holds them (valid until fhip_mesh_free)
     pub fn fhip_mesh_triangles_ptr(mesh: *const fhip_mesh) -> *const u64;
     pub fn fhip_mesh_free(mesh: *mut fhip_mesh);
+    // the mesh where the device left it (context option "mesh_keep_device"), Mesh::write_stl and gradients at the vertices, on the device
+    pub fn fhip_mesh_vertices_dev(mesh: *const fhip_mesh) -> *const f32;
+    pub fn fhip_mesh_triangles_dev(mesh: *const fhip_mesh) -> *const u64;
+    pub fn fhip_mesh_stl_bytes(mesh: *const fhip_mesh) -> u64;
+    pub fn fhip_mesh_stl(ctx: *mut fhip_ctx, mesh: *const fhip_mesh, out: *mut c_void, out_is_device: c_int) -> fhip_status;
+    pub fn fhip_mesh_vertex_grads(ctx: *mut fhip_ctx, tape: *const fhip_tape, mesh: *const fhip_mesh, axis_slots: *const i32,
+                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, out: *mut f32, out_is_device: c_int) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,
