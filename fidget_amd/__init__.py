@@ -52,7 +52,7 @@ EXPORTS = [
     "fhip_ctx_create", "fhip_ctx_destroy", "fhip_ctx_trim", "fhip_ctx_reserve_arena", "fhip_libm_probe", "fhip_last_error", "fhip_ctx_sync", "fhip_cancel", "fhip_cancel_reset", "fhip_cancel_watch", "fhip_ctx_set_option", "fhip_ctx_get_option",
     "fhip_tape_from_bytecode", "fhip_tape_free", "fhip_tape_len", "fhip_tape_reg_tape", "fhip_tape_choice_count", "fhip_tape_reg_count",
     "fhip_tape_var_count", "fhip_tape_output_count", "fhip_tape_ops", "fhip_simplify", "fhip_interval_eval",
-    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads",
+    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads", "fhip_shape_occupancy",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -178,6 +178,7 @@ def lib():
             "fhip_mesh_vertices_dev": (vp, [vp]), "fhip_mesh_triangles_dev": (vp, [vp]),
             "fhip_mesh_stl_bytes": (u64, [vp]), "fhip_mesh_stl": (i32, [vp, vp, vp, i32]),
             "fhip_mesh_vertex_grads": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, i32]),
+            "fhip_shape_occupancy": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1228,6 +1229,87 @@ def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False, _own
     finally:
         lib().fhip_mesh_free(h)
     return leaves, {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
+
+
+# ---- shape occupancy: volume, centroid, second moments, bounds (fhip_shape_occupancy) ------------------------------------
+class OccupancyStruct(C.Structure):
+    """fhip_occupancy (include/fidget_hip.h)"""
+    _fields_ = [("n", C.c_uint64), ("s1", C.c_uint64 * 3), ("s2", C.c_uint64 * 6), ("lo", C.c_uint32 * 3), ("hi", C.c_uint32 * 3),
+                ("grid", C.c_uint32), ("pad", C.c_uint32), ("cells", C.c_uint64 * 4)]
+
+
+class Occupancy:
+    """The inside voxels of the grid of N = 4 << depth per axis over [-1, 1]^3, as the integers fhip_shape_occupancy returns (Python
+    ints: n, s1 (sum of i, j, k), s2 (sum of i^2, j^2, k^2, ij, ik, jk), lo / hi (inclusive, lo = N and hi = 0 when empty), grid,
+    cells = {"cells", "full", "empty", "leaf_cells"} as mesh_sample counts them) and what follows from them in float64, in the region's
+    own coordinates, with h = 2 / N."""
+
+    def __init__(self, raw):
+        self.n = int(raw.n)
+        self.s1 = tuple(int(v) for v in raw.s1)
+        self.s2 = tuple(int(v) for v in raw.s2)
+        self.lo = tuple(int(v) for v in raw.lo)
+        self.hi = tuple(int(v) for v in raw.hi)
+        self.grid = int(raw.grid)
+        self.cells = dict(zip(("cells", "full", "empty", "leaf_cells"), (int(v) for v in raw.cells)))
+
+    @property
+    def h(self):
+        return 2.0 / self.grid
+
+    @property
+    def volume(self):
+        return self.n * self.h ** 3
+
+    @property
+    def centroid(self):
+        """mean of the inside voxels' centres, -1 + (i + 1/2) h per axis; NaN for an empty shape"""
+        if self.n == 0:
+            return np.full(3, np.nan)
+        # (the quotient of the integers first: exact to the last place)
+        return np.array([-1.0 + (s / self.n + 0.5) * self.h for s in self.s1], np.float64)
+
+    @property
+    def covariance(self):
+        """second moments of the inside voxels' centres about the centroid, [3, 3]: h^2 (sum ab / n - (sum a / n)(sum b / n)), the
+        numerator n sum ab - sum a sum b taken in integers, so nothing cancels in floating point"""
+        if self.n == 0:
+            return np.full((3, 3), np.nan)
+        pair = {(0, 0): 0, (1, 1): 1, (2, 2): 2, (0, 1): 3, (0, 2): 4, (1, 2): 5}
+        out = np.zeros((3, 3), np.float64)
+        for a in range(3):
+            for b in range(3):
+                num = self.n * self.s2[pair[(min(a, b), max(a, b))]] - self.s1[a] * self.s1[b]
+                out[a, b] = num / (self.n * self.n) * self.h * self.h
+        return out
+
+    @property
+    def bounds(self):
+        """the faces of the outermost inside voxels: ([x0, y0, z0], [x1, y1, z1]); NaN for an empty shape"""
+        if self.n == 0:
+            return np.full(3, np.nan), np.full(3, np.nan)
+        return (np.array([-1.0 + l * self.h for l in self.lo], np.float64), np.array([-1.0 + (u + 1) * self.h for u in self.hi], np.float64))
+
+    def __repr__(self):
+        return f"Occupancy(grid={self.grid}, n={self.n}, s1={self.s1}, s2={self.s2}, lo={self.lo}, hi={self.hi}, cells={self.cells})"
+
+
+def occupancy(shape, depth, world_to_model=None, vars=None):
+    """fhip_shape_occupancy: the solid `shape < 0` on the grid of 4 << depth voxels per axis over [-1, 1]^3 (world_to_model as for
+    `mesh`), counted down the mesher's octree -> Occupancy"""
+    hip = shape.hip
+    w2m = None if world_to_model is None else np.ascontiguousarray(world_to_model, np.float32)
+    vk, vv = _var_arrays(shape, vars)
+    ax = None
+    if shape._vars is not None:
+        ax = np.array(shape._vars, dtype=np.int32)
+        vk = np.array([shape._named_slot(k) for k in (vars or {})], dtype=np.uint64)
+    raw = OccupancyStruct()
+    st = lib().fhip_shape_occupancy(hip._h, shape._h, depth, _p(w2m), _p(ax), _p(vk), _p(vv), len(vk), C.byref(raw))
+    if st == 4:
+        raise ValueError("MissingVar")
+    hip.check(st)
+    return Occupancy(raw)
 
 
 # ---- constraint solver (fidget::solver, fidget-solver/src/lib.rs) ---------------------------------------------------------

@@ -387,16 +387,22 @@ static const fhmesh::WalkTable& walk_table() {       // CELL_TO_EDGE_TO_VERT out
 }
 static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t depth, std::vector<fhmesh::OctLevel>& lv, const FhMeshLeaf* rec, uint32_t n_rec, const FhMdcTable* table,
                                        bool has_mat, const float* mat, MeshTimes& T, std::string& why);
-enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART };
+// MESH_OCC (fhip_shape_occupancy): the level loop alone, with k_occ_full after every level that has Full cells and k_occ_leaves over the
+// ambiguous cells of the last one - no leaf records, no mesh; the other modes make the launches they made without it, in the same order
+enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART, MESH_OCC };
 static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
-                            const uint64_t* var_keys, const float* var_values, uint32_t n_vars, MeshMode mode, uint32_t part, uint32_t n_parts, fhip_mesh** out) {
+                            const uint64_t* var_keys, const float* var_values, uint32_t n_vars, MeshMode mode, uint32_t part, uint32_t n_parts, fhip_mesh** out,
+                            fhip_occupancy* occ = nullptr) {
     if (!out) return FHIP_ERR_BAD_TAPE;
     *out = nullptr;
+    const bool occ_mode = mode == MESH_OCC;
+    if (occ_mode && !occ) return FHIP_ERR_BAD_TAPE;
+    if (occ_mode && depth > 10) return fail(ctx, FHIP_ERR_UNSUPPORTED, "occupancy depth above 10: the second moments of a grid of more than 4096^3 voxels overflow 64 bits");
     const bool assemble = mode == MESH_BUILD;
     // fhip_mesh_build assembles the octree on the device: the levels' arrays and the leaf records stay in HBM, the host gets the finished
     // octree for the dual walk.  (Option mesh_device_assembly 0: on the host's threads from copies of both, as fhip_mesh_merge does.)
     const bool dev_asm = assemble && n_parts == 1 && ctx->opt.mesh_device_assembly;
-    const bool keep = mode != MESH_SAMPLE && !dev_asm;
+    const bool keep = (mode == MESH_BUILD || mode == MESH_PART) && !dev_asm;      // host copies of every level's classes and slots: for the host's assembly alone
     if (depth > 20) return fail(ctx, FHIP_ERR_UNSUPPORTED, "octree depth above 20");
     if (n_parts < 1 || n_parts > 8 || part >= n_parts) return fail(ctx, FHIP_ERR_UNSUPPORTED, "mesh parts: 1..8, part < n_parts");
     std::shared_ptr<const fhip_tape> bound;     // (more input slots than a mesh binds: its bound tape, capi_bound.hpp; held for the call, which waits for its work)
@@ -435,6 +441,7 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
             (void)hipFuncSetAttribute((const void*)fhm::k_mesh_corners, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
             (void)hipFuncSetAttribute((const void*)fhm::k_mesh_edges, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
             (void)hipFuncSetAttribute((const void*)fhm::k_mesh_grads, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
+            (void)hipFuncSetAttribute((const void*)fhm::k_occ_leaves, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
             attr_done[d] = true;
         }
     }
@@ -445,18 +452,20 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
     const double t_start = now();
     double t_cells = 0, t_leaf = 0, t_copy = 0;
     DevBuf& leaves = ctx->mesh_leaves;      // (kept with the context between builds)
-    DevBuf bufs[2], counters, table, d_cls, d_slot, edge_list, edge_count, edge_br, edge_vars, edge_vals, sub_ops, sub_tab, sub_choices, sub_ops2, sub_tab2;
+    DevBuf bufs[2], counters, table, d_cls, d_slot, edge_list, edge_count, edge_br, edge_vars, edge_vals, sub_ops, sub_tab, sub_choices, sub_ops2, sub_tab2, occ_parts;
     std::vector<DevBuf> lv_cls, lv_slot, lv_amb;        // dev_asm: every level's classes, slots and ambiguous cells stay
     if (dev_asm) { lv_cls.resize(depth + 1); lv_slot.resize(depth + 1); lv_amb.resize(depth + 1); }
     std::vector<uint32_t> lv_n_amb;
     auto cleanup = [&] {
         bufs[0].release(); bufs[1].release(); counters.release(); table.release(); d_cls.release(); d_slot.release();
         edge_list.release(); edge_count.release(); edge_br.release(); edge_vars.release(); edge_vals.release();
-        sub_ops.release(); sub_tab.release(); sub_choices.release(); sub_ops2.release(); sub_tab2.release();
+        sub_ops.release(); sub_tab.release(); sub_choices.release(); sub_ops2.release(); sub_tab2.release(); occ_parts.release();
         for (auto* v : {&lv_cls, &lv_slot, &lv_amb}) for (DevBuf& b : *v) b.release();
     };
 #define MESH_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); delete M; return fail(ctx, FHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
     MESH_TRY(counters.ensure(16));
+    uint32_t occ_used = 0;       // partial records written so far: every launch of the two occupancy kernels its own span, one record per block
+    if (occ_mode) MESH_TRY(occ_parts.ensure(((size_t)(depth + 1) * FH_OCC_FULL_BLOCKS + FH_OCC_LEAF_BLOCKS) * sizeof(FhOccPart)));
     FhMeshCell root;
     for (int k = 0; k < 3; k++) { root.b[2 * k] = -1.0f; root.b[2 * k + 1] = 1.0f; }     // CellBounds::new (cell.rs:171-176)
     root.path = 1;
@@ -483,10 +492,11 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
         const void* in_cells = (dev_asm && d > 0) ? lv_amb[d - 1].p : bufs[cur].p;
         MESH_TRY(out_cells.ensure((size_t)n * sizeof(FhMeshCell)));
         MESH_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-        if (keep) { MESH_TRY(d_cls.ensure(n)); MESH_TRY(d_slot.ensure((size_t)n * 4)); }
+        // (occupancy reads the classes alone, on the device; k_mesh_cells writes slots wherever it writes classes, so it gets both arrays)
+        if (keep || occ_mode) { MESH_TRY(d_cls.ensure(n)); MESH_TRY(d_slot.ensure((size_t)n * 4)); }
         if (dev_asm) { MESH_TRY(lv_cls[d].ensure(n)); MESH_TRY(lv_slot[d].ensure((size_t)n * 4)); }
-        uint8_t* const cls_p = dev_asm ? (uint8_t*)lv_cls[d].p : (keep ? (uint8_t*)d_cls.p : nullptr);
-        uint32_t* const slot_p = dev_asm ? (uint32_t*)lv_slot[d].p : (keep ? (uint32_t*)d_slot.p : nullptr);
+        uint8_t* const cls_p = dev_asm ? (uint8_t*)lv_cls[d].p : ((keep || occ_mode) ? (uint8_t*)d_cls.p : nullptr);
+        uint32_t* const slot_p = dev_asm ? (uint32_t*)lv_slot[d].p : ((keep || occ_mode) ? (uint32_t*)d_slot.p : nullptr);
         const uint32_t child_mask = (d == 1 && n_parts > 1) ? mesh_part_mask(part, n_parts) : 0xFFu;      // (level 1 = the root's 8 children)
         hipLaunchKernelGGL(fhm::k_mesh_cells, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, (const FhMeshCell*)in_cells, n, d == 0 ? 0 : 1,
                            (FhMeshCell*)out_cells.p, (uint32_t*)counters.p, n, cls_p, slot_p, child_mask);
@@ -502,6 +512,13 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
         const uint32_t n_here = child_mask == 0xFFu ? n : (uint32_t)__builtin_popcount(child_mask);
         M->cells_evaluated += n_here; M->full += c[1]; M->empty += c[2];
         M->per_level.push_back(n_here);
+        if (occ_mode && c[1]) {      // this level's Full cells: their closed forms (the parents' paths are still in in_cells)
+            const uint32_t nb = std::min<uint32_t>((n + 255) / 256, FH_OCC_FULL_BLOCKS);
+            hipLaunchKernelGGL(fhm::k_occ_full, dim3(nb), dim3(256), 0, ctx->stream, (const FhMeshCell*)in_cells, (const uint8_t*)cls_p, n, d == 0 ? 0 : 1, d, depth,
+                               (FhOccPart*)occ_parts.p + occ_used);
+            MESH_TRY(hipGetLastError());
+            occ_used += nb;
+        }
         cur ^= 1;
         n_in = c[0];
         lv_n_amb.push_back(c[0]);
@@ -609,6 +626,34 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
         fprintf(stderr, "fhip mesh: tape simplified at level %u: %llu cells with tapes of their own, %.1f ops on average (root tape: %zu)%s\n", split_level,
                 (unsigned long long)(M->sub_tapes + M->sub_skipped), (double)M->sub_ops / (double)(M->sub_tapes + M->sub_skipped), t.ops.size(),
                 M->sub_skipped ? " - not used: too little gained" : "");
+    if (occ_mode) {
+        if (n_leaf_cells) {
+            const uint32_t nb = std::min<uint32_t>(n_leaf_cells, FH_OCC_LEAF_BLOCKS);
+            hipLaunchKernelGGL(fhm::k_occ_leaves, dim3(nb), dim3(WAVE), (size_t)P.n_regs * WAVE * 4, ctx->stream, P, (const FhMeshCell*)bufs[cur].p, n_leaf_cells, depth,
+                               (FhOccPart*)occ_parts.p + occ_used);
+            MESH_TRY(hipGetLastError());
+            occ_used += nb;
+        }
+        std::vector<FhOccPart> parts(occ_used);
+        if (occ_used) MESH_TRY(hipMemcpyAsync(parts.data(), occ_parts.p, (size_t)occ_used * sizeof(FhOccPart), hipMemcpyDeviceToHost, ctx->stream));
+        MESH_TRY(hipStreamSynchronize(ctx->stream));
+        const uint32_t N = 4u << depth;
+        memset(occ, 0, sizeof(*occ));
+        occ->grid = N;
+        for (int k = 0; k < 3; k++) occ->lo[k] = N;
+        for (const FhOccPart& q : parts) {
+            if (!q.n) continue;
+            occ->n += q.n;
+            for (int k = 0; k < 3; k++) { occ->s1[k] += q.s1[k]; occ->lo[k] = std::min(occ->lo[k], q.lo[k]); occ->hi[k] = std::max(occ->hi[k], q.hi[k]); }
+            for (int k = 0; k < 6; k++) occ->s2[k] += q.s2[k];
+        }
+        occ->cells[0] = M->cells_evaluated; occ->cells[1] = M->full; occ->cells[2] = M->empty; occ->cells[3] = M->ambiguous_leaves;
+        if (times) fprintf(stderr, "fhip occupancy depth %u: %.4f s (%llu cells evaluated, %u leaf cells, %u partial records)\n", depth, now() - t_start,
+                           (unsigned long long)M->cells_evaluated, n_leaf_cells, occ_used);
+        cleanup();
+        *out = M;
+        return FHIP_OK;
+    }
     FhMdcTable mdc;
     if (n_leaf_cells || dev_asm) {
         build_mdc_table(mdc);
@@ -951,6 +996,15 @@ static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t dep
                         "dual walk + the mesh's vertices gathered %.4f s, total %.4f s\n",
                 depth, T.t_cells, (unsigned long long)M->cells_evaluated, T.t_leaf, T.n_leaf_cells, t_asm, oo.n_blocks, oo.n_verts, t_walk, now() - T.t_start);
     return hipSuccess;
+}
+// Shape occupancy (fidget_hip.h): the octree's level loop with the occupancy kernels of mesh.hip, the partial records added up on the host
+fhip_status fhip_shape_occupancy(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
+                                 const uint64_t* var_keys, const float* var_values, uint32_t n_vars, void* out) {
+    if (!out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_shape_occupancy: no result struct");
+    fhip_mesh* m = nullptr;
+    const fhip_status st = mesh_run(ctx, tape, depth, world_to_model, axis_slots, var_keys, var_values, n_vars, MESH_OCC, 0, 1, &m, (fhip_occupancy*)out);
+    delete m;
+    return st;
 }
 fhip_status fhip_mesh_sample(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
                              const uint64_t* var_keys, const float* var_values, uint32_t n_vars, fhip_mesh** out) {

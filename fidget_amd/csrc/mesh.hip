@@ -55,6 +55,12 @@ struct FhMeshParams {
     const uint2* sub_tab2;
     uint32_t split_level2, pad2_;
 };
+// shape occupancy (k_occ_full, k_occ_leaves): one block's partial sums
+struct FhOccPart {
+    uint64_t n, s1[3], s2[6];       // inside voxels; sum i, j, k; sum i^2, j^2, k^2, ij, ik, jk
+    uint32_t lo[3], hi[3];          // inclusive bounds of the inside voxels per axis (n == 0: lo = 0xFFFFFFFF, hi = 0)
+};
+constexpr uint32_t FH_OCC_FULL_BLOCKS = 256, FH_OCC_LEAF_BLOCKS = 4096;      // the grids' upper bounds: blocks stride over their cells
 
 namespace fhm {
 using namespace fhd;
@@ -672,5 +678,137 @@ __global__ void __launch_bounds__(256) k_scan_block(const uint32_t* in, uint32_t
 __global__ void __launch_bounds__(256) k_scan_add(uint32_t* out, uint32_t n, const uint32_t* block_off) {
     const uint32_t i = blockIdx.x * blockDim.x + threadIdx.x;
     if (i <= n) out[i] += block_off[i / FH_SCAN_PER_BLOCK];
+}
+
+// ---- shape occupancy: the inside voxels of the regular grid of N = 4 << depth per axis, as integer sums -------------------------------
+// The octree of k_mesh_cells with another leaf: a Full cell counts all its voxels (closed forms, k_occ_full), an Empty one none, an
+// ambiguous cell of the last level is sampled at the centres of its 4 x 4 x 4 voxels (k_occ_leaves).  Voxel (i, j, k) is inside iff the
+// tape is < 0 at c(i) = float(2 i + 1 - N) * (1.0f / N) (both factors and the product exact in f32), likewise j, k.  Every block writes
+// one partial record; the host adds them up - integers, so the result does not depend on the order.
+FH_DEV void occ_zero(FhOccPart& a) {
+    a.n = 0;
+    for (int k = 0; k < 3; k++) { a.s1[k] = 0; a.lo[k] = 0xFFFFFFFFu; a.hi[k] = 0; }
+    for (int k = 0; k < 6; k++) a.s2[k] = 0;
+}
+// the origin (in cells of its level) of the cell with this path: 3 bits per level below a leading 1, bit 0 x, 1 y, 2 z, the last level lowest
+FH_DEV void occ_origin(uint64_t path, uint32_t level, uint32_t o[3]) {
+    o[0] = o[1] = o[2] = 0;
+    for (uint32_t l = 0; l < level; l++) {
+        const uint32_t b = (uint32_t)(path >> (3 * l)) & 7u;
+        o[0] |= (b & 1u) << l; o[1] |= ((b >> 1) & 1u) << l; o[2] |= ((b >> 2) & 1u) << l;
+    }
+}
+// all the voxels of the box [X, X + w) x [Y, Y + w) x [Z, Z + w): with S1(X) = sum of a over [X, X + w) = w X + w (w - 1) / 2 and
+// S2(X) = sum of a^2 = w X^2 + X w (w - 1) + (w - 1) w (2 w - 1) / 6:  n = w^3, sum i = w^2 S1(X), sum i^2 = w^2 S2(X), sum ij = w S1(X) S1(Y).
+// (N <= 4096: the largest, sum i^2 of the whole grid, is below N^5 = 2^60)
+FH_DEV void occ_add_box(FhOccPart& a, const uint32_t org[3], uint32_t w32) {
+    const uint64_t w = w32, t1 = w * (w - 1) / 2, t2 = (w - 1) * w * (2 * w - 1) / 6;
+    uint64_t S1[3], S2[3];
+    for (int k = 0; k < 3; k++) {
+        const uint64_t X = org[k];
+        S1[k] = w * X + t1;
+        S2[k] = w * X * X + X * w * (w - 1) + t2;
+        a.lo[k] = min(a.lo[k], org[k]);
+        a.hi[k] = max(a.hi[k], org[k] + w32 - 1);
+    }
+    a.n += w * w * w;
+    for (int k = 0; k < 3; k++) { a.s1[k] += w * w * S1[k]; a.s2[k] += w * w * S2[k]; }
+    a.s2[3] += w * S1[0] * S1[1]; a.s2[4] += w * S1[0] * S1[2]; a.s2[5] += w * S1[1] * S1[2];
+}
+FH_DEV uint64_t occ_shfl_down(uint64_t v, int d) { return (uint64_t)__shfl_down((unsigned long long)v, d); }
+// the sum of the lanes' records, valid in lane 0
+FH_DEV void occ_wave_reduce(FhOccPart& a) {
+    for (int d = WAVE / 2; d > 0; d >>= 1) {
+        a.n += occ_shfl_down(a.n, d);
+        for (int k = 0; k < 3; k++) {
+            a.s1[k] += occ_shfl_down(a.s1[k], d);
+            a.lo[k] = min(a.lo[k], (uint32_t)__shfl_down((int)a.lo[k], d));
+            a.hi[k] = max(a.hi[k], (uint32_t)__shfl_down((int)a.hi[k], d));
+        }
+        for (int k = 0; k < 6; k++) a.s2[k] += occ_shfl_down(a.s2[k], d);
+    }
+}
+
+// The Full cells of one level (cls as k_mesh_cells left it: cell i is child (i & 7) of in[i >> 3] when expand): one lane per cell, the
+// closed forms of a cell of edge w = N >> level voxels; one partial record per block.  The grid is bounded: a block strides over the cells.
+__global__ void __launch_bounds__(256) k_occ_full(const FhMeshCell* in, const uint8_t* cls, uint32_t n, int expand, uint32_t level, uint32_t depth, FhOccPart* out) {
+    __shared__ FhOccPart part[256 / WAVE];
+    FhOccPart a;
+    occ_zero(a);
+    const uint32_t w = (4u << depth) >> level;
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < n; i += (uint64_t)gridDim.x * 256) {
+        if (cls[i] != 2) continue;
+        const uint64_t path = expand ? ((in[i >> 3].path << 3) | (i & 7)) : in[i].path;
+        uint32_t o[3];
+        occ_origin(path, level, o);
+        for (int k = 0; k < 3; k++) o[k] *= w;
+        occ_add_box(a, o, w);
+    }
+    occ_wave_reduce(a);
+    if ((threadIdx.x & (WAVE - 1)) == 0) part[threadIdx.x / WAVE] = a;
+    __syncthreads();
+    if (threadIdx.x == 0) {
+        for (int v = 1; v < 256 / WAVE; v++) {
+            const FhOccPart b = part[v];
+            a.n += b.n;
+            for (int k = 0; k < 3; k++) { a.s1[k] += b.s1[k]; a.lo[k] = min(a.lo[k], b.lo[k]); a.hi[k] = max(a.hi[k], b.hi[k]); }
+            for (int k = 0; k < 6; k++) a.s2[k] += b.s2[k];
+        }
+        out[blockIdx.x] = a;
+    }
+}
+
+// The ambiguous cells of the last level: one wave takes one cell at a time, lane (lx, ly, lz) = (lane & 3, (lane >> 2) & 3, lane >> 4)
+// the voxel (4 ox + lx, 4 oy + ly, 4 oz + lz) of the cell at origin (ox, oy, oz), evaluated as k_mesh_leaf's samples are (eval_point: the
+// f32 point transform, the cell's own tape, the register file in LDS - a lane only ever touches its own column, so cells need no barrier
+// between them).  The inside mask is one ballot; what the cell adds follows from it with X = 4 ox:
+//   sum i = n X + sum lx,   sum i^2 = n X^2 + 2 X sum lx + sum lx^2,   sum ij = n X Y + X sum ly + Y sum lx + sum lx ly,
+// the local sums being popcounts of the mask against constant lane masks - wave-uniform, scalar work.  The block's sums stay in
+// registers across its cells; one store of the record at the end, no atomics.
+__global__ void __launch_bounds__(WAVE) k_occ_leaves(FhMeshParams P, const FhMeshCell* cells, uint32_t n, uint32_t depth, FhOccPart* out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const uint32_t lx = lane & 3, ly = (lane >> 2) & 3, lz = lane >> 4;
+    const int32_t N = (int32_t)(4u << depth);
+    const float inv = 1.0f / (float)N;
+    Regs<float, WAVE> R{(float*)smem, lane};
+    FhOccPart a;
+    occ_zero(a);
+    constexpr uint64_t MX = 0x1111111111111111ull, MY = 0x000F000F000F000Full, MZ = 0xFFFFull;
+    for (uint32_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+        const uint64_t pv = cells[ci].path;
+        const uint64_t path = ((uint64_t)uni((uint32_t)(pv >> 32)) << 32) | (uint64_t)uni((uint32_t)pv);      // (wave-uniform, and known to be)
+        uint32_t o[3];
+        occ_origin(path, depth, o);
+        const uint32_t X = 4 * o[0], Y = 4 * o[1], Z = 4 * o[2];
+        const float x = (float)(2 * (int32_t)(X + lx) + 1 - N) * inv, y = (float)(2 * (int32_t)(Y + ly) + 1 - N) * inv, z = (float)(2 * (int32_t)(Z + lz) + 1 - N) * inv;
+        const float v = eval_point(P, R, x, y, z, path);
+        const uint64_t m = ballot(v < 0.0f);       // (NaN: not inside)
+        if (m == 0) continue;
+        const uint64_t cnt = (uint64_t)__popcll(m);
+        const uint32_t org[3] = {X, Y, Z};
+        uint64_t M[3][4];                           // the inside voxels with local coordinate v along axis k
+        for (int q = 0; q < 4; q++) { M[0][q] = m & (MX << q); M[1][q] = m & (MY << (4 * q)); M[2][q] = m & (MZ << (16 * q)); }
+        uint64_t S[3];
+        for (int k = 0; k < 3; k++) {
+            const uint64_t c1 = (uint64_t)__popcll(M[k][1]), c2 = (uint64_t)__popcll(M[k][2]), c3 = (uint64_t)__popcll(M[k][3]);
+            const uint64_t s = c1 + 2 * c2 + 3 * c3, ss = c1 + 4 * c2 + 9 * c3, O = org[k];
+            S[k] = s;
+            a.s1[k] += cnt * O + s;
+            a.s2[k] += cnt * O * O + 2 * O * s + ss;
+            const uint32_t first = M[k][0] ? 0u : (M[k][1] ? 1u : (M[k][2] ? 2u : 3u)), last = M[k][3] ? 3u : (M[k][2] ? 2u : (M[k][1] ? 1u : 0u));
+            a.lo[k] = min(a.lo[k], org[k] + first);
+            a.hi[k] = max(a.hi[k], org[k] + last);
+        }
+        int pi = 3;
+        for (int k = 0; k < 3; k++)
+            for (int j = k + 1; j < 3; j++, pi++) {
+                uint64_t cross = 0;
+                for (int p = 1; p < 4; p++) for (int q = 1; q < 4; q++) cross += (uint64_t)(p * q) * (uint64_t)__popcll(M[k][p] & M[j][q]);
+                a.s2[pi] += cnt * org[k] * org[j] + (uint64_t)org[k] * S[j] + (uint64_t)org[j] * S[k] + cross;
+            }
+        a.n += cnt;
+    }
+    if (lane == 0) out[blockIdx.x] = a;
 }
 }  // namespace fhm

@@ -337,6 +337,27 @@ fhip_status fhip_mesh_stl(fhip_ctx* ctx, const fhip_mesh* mesh, void* out, int o
 fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const fhip_mesh* mesh, const int32_t* axis_slots,
                                    const uint64_t* var_keys, const float* var_values, uint32_t n_vars, float* out, int out_is_device);
 
+/* ---- shape occupancy: volume, centroid, second moments and bounds of a solid, as exact integer sums ----------
+ * The region is the mesher's cube [-1, 1]^3 (carried into model space by world_to_model as fhip_mesh_build does), divided into a
+ * regular grid of N = 4 << depth voxels per axis.  Voxel (i, j, k) is inside iff the tape's value is < 0 (NaN: not inside) at its
+ * centre, c(i) = float(2 i + 1 - N) * (1.0f / N) - both factors and the product are exact in f32 - taken through the f32 point
+ * transform of the mesher's leaf samples.  The grid is not visited voxel by voxel: the octree of fhip_mesh_sample is descended (the
+ * same interval evaluations, the same tape simplification on the way down), a Full cell (interval result hi < 0) counts as entirely
+ * inside by closed forms, an Empty one (lo > 0) as entirely outside, and only the ambiguous cells of level `depth` are sampled, at
+ * their 4 x 4 x 4 voxels.  The result is what this recursion gives; it is the count over all N^3 centres whenever interval
+ * inclusion holds for the tape.  All sums are integers: exact, independent of summation order and of "mesh_simplify_min_ops",
+ * identical from run to run.
+ *   n: inside voxels;  s1: sum of i, j, k over them;  s2: sum of i^2, j^2, k^2, ij, ik, jk;  lo / hi: the smallest and largest inside
+ *   index per axis, inclusive (n == 0: lo = N, hi = 0);  grid: N;  cells: {cells interval-evaluated, Full, Empty, ambiguous cells of
+ *   the last level}, what fhip_mesh_counts reports after fhip_mesh_sample at the same depth.
+ * With h = 2 / N: volume = n h^3, centroid_x = -1 + (s1[0] / n + 0.5) h, and so on.  Arguments, variable binding and statuses are
+ * fhip_mesh_build's (tapes of more than 16 input slots run their bound tape; one output; FHIP_ERR_UNSUPPORTED when the register file
+ * exceeds LDS); depth > 10 is FHIP_ERR_UNSUPPORTED before any launch (at depth 10 the largest sum is below N^5 = 2^60).  Blocking;
+ * `out` points to a host fhip_occupancy, the struct below; it is declared void* so that bindings generated from this header need no new type. */
+typedef struct fhip_occupancy { uint64_t n, s1[3], s2[6]; uint32_t lo[3], hi[3]; uint32_t grid, pad; uint64_t cells[4]; } fhip_occupancy;
+fhip_status fhip_shape_occupancy(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
+                                 const uint64_t* var_keys, const float* var_values, uint32_t n_vars, void* out);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

@@ -10,6 +10,16 @@ use std::os::raw::{c_char, c_int, c_void};
 #[repr(C)] pub struct fhip_tape  { _p: [u8; 0] }
 #[repr(C)] pub struct fhip_mesh  { _p: [u8; 0] }
 
+/// The result of `fhip_shape_occupancy` (fidget_hip.h): integer sums over the inside voxels of the grid of `grid` per axis
+#[repr(C)]
+#[derive(Clone, Copy, Debug, Default, PartialEq, Eq)]
+pub struct fhip_occupancy {
+    pub n: u64, pub s1: [u64; 3], pub s2: [u64; 6],
+    pub lo: [u32; 3], pub hi: [u32; 3],
+    pub grid: u32, pub pad: u32,
+    pub cells: [u64; 4],
+}
+
 pub type fhip_status = c_int;           // 0 = OK, see fidget_hip.h
 pub const FHIP_ERR_BAD_VAR_SLICE: c_int = 1;     // -> TracingEvalError / BulkEvalError::BadVarSlice
 pub const FHIP_ERR_MISMATCHED_SLICES: c_int = 2; // -> BulkEvalError::MismatchedSlices
@@ -109,6 +119,9 @@ extern "C" {
     pub fn fhip_mesh_stl(ctx: *mut fhip_ctx, mesh: *const fhip_mesh, out: *mut c_void, out_is_device: c_int) -> fhip_status;
     pub fn fhip_mesh_vertex_grads(ctx: *mut fhip_ctx, tape: *const fhip_tape, mesh: *const fhip_mesh, axis_slots: *const i32,
                                   var_keys: *const u64, var_values: *const f32, n_vars: u32, out: *mut f32, out_is_device: c_int) -> fhip_status;
+    // volume, centroid, second moments and bounds as exact integer sums; `out`: a `fhip_occupancy` (the header declares it void*)
+    pub fn fhip_shape_occupancy(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
+                                var_keys: *const u64, var_values: *const f32, n_vars: u32, out: *mut c_void) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

@@ -12,6 +12,7 @@
 
 pub mod ffi;
 pub mod mesh;
+pub mod occupancy;
 pub mod render;
 
 use std::ops::Deref;
