@@ -1,4 +1,17 @@
 // Fragment of capi.hip (meshing (the only fragment the mesh path owns: tools/src_hash.py leaves it out of the render path's hash)); not a stand-alone header: included by capi.hip only.
+extern "C++" {
+#include "mesh_split.hpp"
+}
+// The context's pinned landing area (leaf records, octree cells and finished meshes on their way to the host), kept between calls - pinning
+// 17 GB takes over a second: at least `bytes`, and an eighth more where it has to grow
+static hipError_t pinned_ensure(fhip_ctx* ctx, size_t bytes) {
+    if (ctx->mesh_pinned_cap >= bytes) return hipSuccess;
+    if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
+    ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
+    const hipError_t e = hipHostMalloc(&ctx->mesh_pinned, bytes + bytes / 8, hipHostMallocDefault);
+    if (e == hipSuccess) ctx->mesh_pinned_cap = bytes + bytes / 8;
+    return e;
+}
 // ---- meshing: the evaluation side of fidget_mesh::Octree::build (fidget-mesh/src/octree.rs) --------------------------------
 // CELL_TO_VERT_TO_EDGES of fidget-mesh/build.rs:26-160: per corner mask, the inside -> outside edges grouped into cell vertices
 // by connected region (filled regions first, then empty ones, each in ascending order of their corner sets)
@@ -387,256 +400,241 @@ static const fhmesh::WalkTable& walk_table() {       // CELL_TO_EDGE_TO_VERT out
 }
 static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t depth, std::vector<fhmesh::OctLevel>& lv, const FhMeshLeaf* rec, uint32_t n_rec, const FhMdcTable* table,
                                        bool has_mat, const float* mat, MeshTimes& T, std::string& why);
-// MESH_OCC (fhip_shape_occupancy): the level loop alone, with k_occ_full after every level that has Full cells and k_occ_leaves over the
-// ambiguous cells of the last one - no leaf records, no mesh; the other modes make the launches they made without it, in the same order
 enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART, MESH_OCC };
-static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
-                            const uint64_t* var_keys, const float* var_values, uint32_t n_vars, MeshMode mode, uint32_t part, uint32_t n_parts, fhip_mesh** out,
-                            fhip_occupancy* occ = nullptr) {
-    if (!out) return FHIP_ERR_BAD_TAPE;
-    *out = nullptr;
-    const bool occ_mode = mode == MESH_OCC;
-    if (occ_mode && !occ) return FHIP_ERR_BAD_TAPE;
-    if (occ_mode && depth > 10) return fail(ctx, FHIP_ERR_UNSUPPORTED, "occupancy depth above 10: the second moments of a grid of more than 4096^3 voxels overflow 64 bits");
-    const bool assemble = mode == MESH_BUILD;
-    // fhip_mesh_build assembles the octree on the device: the levels' arrays and the leaf records stay in HBM, the host gets the finished
-    // octree for the dual walk.  (Option mesh_device_assembly 0: on the host's threads from copies of both, as fhip_mesh_merge does.)
-    const bool dev_asm = assemble && n_parts == 1 && ctx->opt.mesh_device_assembly;
-    const bool keep = (mode == MESH_BUILD || mode == MESH_PART) && !dev_asm;      // host copies of every level's classes and slots: for the host's assembly alone
-    if (depth > 20) return fail(ctx, FHIP_ERR_UNSUPPORTED, "octree depth above 20");
-    if (n_parts < 1 || n_parts > 8 || part >= n_parts) return fail(ctx, FHIP_ERR_UNSUPPORTED, "mesh parts: 1..8, part < n_parts");
-    std::shared_ptr<const fhip_tape> bound;     // (more input slots than a mesh binds: its bound tape, capi_bound.hpp; held for the call, which waits for its work)
-    if (tape->t.n_vars > FH_MAX_INPUTS) {
-        const fhip_status bs = bound_tape(ctx, tape, axis_slots, var_keys, var_values, n_vars, bound);
-        if (bs) return bs;
-        tape = bound.get();
-        axis_slots = BOUND_AXES; var_keys = nullptr; var_values = nullptr; n_vars = 0;
-    }
-    const fh::HostTape& t = tape->t;
-    if (t.n_outputs != 1) return fail(ctx, FHIP_ERR_BAD_TAPE, "shape tapes have exactly one output");
-    (void)hipSetDevice(ctx->device);
-    { fhip_status ts_ = tape_to_device(ctx, tape); if (ts_) return ts_; }
-    FhRender R;
-    memset(&R, 0, sizeof(R));
-    fhip_status st = bind_inputs(ctx, tape, axis_slots, var_keys, var_values, n_vars, R);
-    if (st) return st;
-    FhMeshParams P;
-    memset(&P, 0, sizeof(P));
-    P.tape = tape->d_ops; P.len = (uint32_t)t.ops.size(); P.n_regs = std::max<uint32_t>(t.n_regs, 1);
-    bool ident = true;
-    if (world_to_model) for (int i = 0; i < 16; i++) { P.mat[i] = world_to_model[i]; ident &= world_to_model[i] == ((i % 5 == 0) ? 1.0f : 0.0f); }
-    P.has_mat = (world_to_model && !ident) ? 1 : 0;     // octree.rs:487-492: no transform at all for the identity
-    for (int s = 0; s < FH_MAX_INPUTS; s++) { P.in_kind[s] = R.in_kind[s]; P.in_value[s] = R.in_value[s]; }
-    const size_t lds_iv = (size_t)P.n_regs * WAVE * 8, lds_leaf = (size_t)P.n_regs * WAVE * 16;
-    if (lds_leaf + 1024 > FH_LDS_MAX) return fail(ctx, FHIP_ERR_UNSUPPORTED, "register file exceeds LDS");
-    {   // (function attributes are per device; contexts on several host threads may arrive here together)
-        static std::mutex attr_lock;
-        static bool attr_done[64] = {};
-        std::lock_guard<std::mutex> guard(attr_lock);
-        const int d = ctx->device & 63;
-        if (!attr_done[d]) {
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_cells, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_choices, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_leaf, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX - 2048);
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_corners, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_edges, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)fhm::k_mesh_grads, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            (void)hipFuncSetAttribute((const void*)fhm::k_occ_leaves, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
-            attr_done[d] = true;
-        }
-    }
-    fhip_mesh* M = new fhip_mesh();
-    M->depth = depth; M->part = part; M->n_parts = n_parts;
+// What a call of mesh_run does, by entry point.  Every mode makes the launches it made before the others existed, in the same order.
+//                                                  the levels' classes, slots   leaf records                             then
+//   fhip_mesh_sample        MESH_SAMPLE            -                            sampled, copied into the mesh            -
+//   fhip_mesh_sample_part   MESH_PART              copied to the host           sampled, copied into the mesh            - (fhip_mesh_merge assembles)
+//   fhip_mesh_build         MESH_BUILD             stay in HBM (+ the cells)    sampled, stay in HBM                     octree and dual walk on the device
+//     option mesh_device_assembly 0                copied to the host           sampled, to the context's landing area   both on the host's threads, as fhip_mesh_merge
+//   fhip_shape_occupancy    MESH_OCC               on the device, per level     none                                     k_occ_full per level with Full cells, k_occ_leaves at the end
+struct MeshDoes { bool keep_host_levels, keep_dev_levels, need_classes, sample_leaves, assemble_on_device, assemble_on_host, occupancy; };
+static MeshDoes mesh_does(MeshMode mode, uint32_t n_parts, bool device_assembly) {
+    MeshDoes D;
+    D.occupancy = mode == MESH_OCC;
+    D.assemble_on_device = mode == MESH_BUILD && n_parts == 1 && device_assembly;
+    D.assemble_on_host = mode == MESH_BUILD && !D.assemble_on_device;
+    D.keep_dev_levels = D.assemble_on_device;
+    D.keep_host_levels = (mode == MESH_BUILD || mode == MESH_PART) && !D.assemble_on_device;       // for the host's assembly alone
+    D.need_classes = D.keep_host_levels || D.occupancy;     // (occupancy reads the classes alone, on the device; k_mesh_cells writes slots wherever it writes classes: both arrays)
+    D.sample_leaves = !D.occupancy;
+    return D;
+}
+static double mesh_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
+struct ScratchBuf : DevBuf {       // a device buffer that goes with its scope (movable for std::vector, not copyable)
+    ScratchBuf() = default;
+    ScratchBuf(ScratchBuf&& o) noexcept { p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
+    ~ScratchBuf() { release(); }
+};
+static_assert(sizeof(fhsplit::TabEntry) == sizeof(uint2) && offsetof(fhsplit::TabEntry, off) == 0 && offsetof(fhsplit::TabEntry, len) == 4 &&
+              alignof(fhsplit::TabEntry) <= alignof(uint2), "a split's table goes to the device as it is: {off, len} = uint2 {x, y}");
+#define MESH_CHECK(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed(#call, e_); } while (0)
+// One run of the mesh driver: its state, and its stages in the order mesh_run calls them.  Every buffer is released with the job.
+struct MeshJob {
+    fhip_ctx* const ctx;
+    const uint32_t depth, part, n_parts;
+    const MeshDoes does;
     const bool times = getenv("FHIP_MESH_TIMES") != nullptr;       // diagnostic: phase wall times on stderr
-    auto now = [] { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); };
-    const double t_start = now();
-    double t_cells = 0, t_leaf = 0, t_copy = 0;
-    DevBuf& leaves = ctx->mesh_leaves;      // (kept with the context between builds)
-    DevBuf bufs[2], counters, table, d_cls, d_slot, edge_list, edge_count, edge_br, edge_vars, edge_vals, sub_ops, sub_tab, sub_choices, sub_ops2, sub_tab2, occ_parts;
-    std::vector<DevBuf> lv_cls, lv_slot, lv_amb;        // dev_asm: every level's classes, slots and ambiguous cells stay
-    if (dev_asm) { lv_cls.resize(depth + 1); lv_slot.resize(depth + 1); lv_amb.resize(depth + 1); }
+    std::shared_ptr<const fhip_tape> bound;     // (more input slots than a mesh binds: its bound tape, capi_bound.hpp; held for the call, which waits for its work)
+    const fhip_tape* tape = nullptr; FhMeshParams P;
+    size_t lds_iv = 0, lds_leaf = 0, lds_f32 = 0;
+    std::unique_ptr<fhip_mesh> M;
+    double t_start = 0, t_cells = 0, t_leaf = 0;
+    ScratchBuf bufs[2], counters, table, d_cls, d_slot, edge_list, edge_count, edge_br, edge_vars, edge_vals, sub_ops, sub_tab, sub_choices, sub_ops2, sub_tab2, occ_parts;
+    std::vector<ScratchBuf> lv_cls, lv_slot, lv_amb;        // keep_dev_levels: every level's classes, slots and ambiguous cells stay
     std::vector<uint32_t> lv_n_amb;
-    auto cleanup = [&] {
-        bufs[0].release(); bufs[1].release(); counters.release(); table.release(); d_cls.release(); d_slot.release();
-        edge_list.release(); edge_count.release(); edge_br.release(); edge_vars.release(); edge_vals.release();
-        sub_ops.release(); sub_tab.release(); sub_choices.release(); sub_ops2.release(); sub_tab2.release(); occ_parts.release();
-        for (auto* v : {&lv_cls, &lv_slot, &lv_amb}) for (DevBuf& b : *v) b.release();
-    };
-#define MESH_TRY(call) do { hipError_t e_ = (call); if (e_ != hipSuccess) { cleanup(); delete M; return fail(ctx, FHIP_ERR_HIP, std::string(#call) + ": " + hipGetErrorString(e_)); } } while (0)
-    MESH_TRY(counters.ensure(16));
     uint32_t occ_used = 0;       // partial records written so far: every launch of the two occupancy kernels its own span, one record per block
-    if (occ_mode) MESH_TRY(occ_parts.ensure(((size_t)(depth + 1) * FH_OCC_FULL_BLOCKS + FH_OCC_LEAF_BLOCKS) * sizeof(FhOccPart)));
-    FhMeshCell root;
-    for (int k = 0; k < 3; k++) { root.b[2 * k] = -1.0f; root.b[2 * k + 1] = 1.0f; }     // CellBounds::new (cell.rs:171-176)
-    root.path = 1;
-    MESH_TRY(bufs[0].ensure(sizeof(FhMeshCell)));
-    MESH_TRY(hipMemcpyAsync(bufs[0].p, &root, sizeof(root), hipMemcpyHostToDevice, ctx->stream));
-    // (option mesh_simplify_min_ops, default 256: shorter tapes are evaluated as they are - gyroid-sphere's 28 ops gain nothing and keep the
-    // assembly bulk interpreter for their leaf samples; 0 = never.  The level: 4 - 4 096 cells at most, a 16th of the region across, where
-    // prospero.vm's 6 363 ops are down to a few hundred - or two above the leaves of a shallower octree)
-    const uint32_t split_level = (ctx->opt.mesh_simplify_min_ops > 0 && t.ops.size() >= (size_t)ctx->opt.mesh_simplify_min_ops && t.n_choices > 0 && depth >= 3)
-                                     ? std::min<uint32_t>(4, depth - 2) : 0;
-    // ... and once more at depth - 2 (at most level 7: a table of 8^7 entries), from the first split's tapes, when the first one was taken:
-    // prospero.vm's level-4 tapes still hold ~600 ops, and the leaf samples of a depth-8 build walked them 16 M times
-    const uint32_t split_level2 = (split_level == 4 && depth >= 7) ? std::min<uint32_t>(7, depth - 2) : 0;
-    std::vector<fh::HostTape> sub_keep;           // the first split's tapes, by table index (kept for the second)
+    fhsplit::SplitLevels split{0, 0};
+    std::vector<fh::HostTape> sub_keep;           // the first split's tapes (kept for the second)
     std::vector<int32_t> sub_of;                  // first-split table index -> index into sub_keep, -1: the root tape
-    uint32_t n_in = 1;      // cells in bufs[cur] to evaluate (level 0) or whose 8 children to evaluate
-    int cur = 0;
+    int cur = 0;                                  // bufs[cur]: the ambiguous cells of the level evaluated last
     uint32_t n_leaf_cells = 0;
-    for (uint32_t d = 0; d <= depth; d++) {
-        const uint64_t n64 = d == 0 ? 1 : (uint64_t)n_in * 8;
-        if (n64 > (1ull << 30)) { cleanup(); delete M; return fail(ctx, FHIP_ERR_OVERFLOW, "octree level above 2^30 cells"); }
-        const uint32_t n = (uint32_t)n64;
-        DevBuf& out_cells = dev_asm ? lv_amb[d] : bufs[cur ^ 1];
-        const void* in_cells = (dev_asm && d > 0) ? lv_amb[d - 1].p : bufs[cur].p;
-        MESH_TRY(out_cells.ensure((size_t)n * sizeof(FhMeshCell)));
-        MESH_TRY(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
-        // (occupancy reads the classes alone, on the device; k_mesh_cells writes slots wherever it writes classes, so it gets both arrays)
-        if (keep || occ_mode) { MESH_TRY(d_cls.ensure(n)); MESH_TRY(d_slot.ensure((size_t)n * 4)); }
-        if (dev_asm) { MESH_TRY(lv_cls[d].ensure(n)); MESH_TRY(lv_slot[d].ensure((size_t)n * 4)); }
-        uint8_t* const cls_p = dev_asm ? (uint8_t*)lv_cls[d].p : ((keep || occ_mode) ? (uint8_t*)d_cls.p : nullptr);
-        uint32_t* const slot_p = dev_asm ? (uint32_t*)lv_slot[d].p : ((keep || occ_mode) ? (uint32_t*)d_slot.p : nullptr);
-        const uint32_t child_mask = (d == 1 && n_parts > 1) ? mesh_part_mask(part, n_parts) : 0xFFu;      // (level 1 = the root's 8 children)
-        hipLaunchKernelGGL(fhm::k_mesh_cells, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, (const FhMeshCell*)in_cells, n, d == 0 ? 0 : 1,
-                           (FhMeshCell*)out_cells.p, (uint32_t*)counters.p, n, cls_p, slot_p, child_mask);
-        MESH_TRY(hipGetLastError());
-        uint32_t c[4];
-        MESH_TRY(hipMemcpyAsync(c, counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
-        if (keep) {
-            M->cls.emplace_back(n); M->slot.emplace_back(n);
-            MESH_TRY(hipMemcpyAsync(M->cls.back().data(), d_cls.p, n, hipMemcpyDeviceToHost, ctx->stream));
-            MESH_TRY(hipMemcpyAsync(M->slot.back().data(), d_slot.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+    FhMdcTable mdc;
+    static constexpr uint32_t LEAF_CH = 1u << 19;         // how the leaf cells are sampled (sample_leaves): cells per chunk, ...
+    bool leaf_passes = true, bulk_edges = false;
+    uint32_t n_slots = 1, bulk_per = 0; int bulk_which = 0;   // ... input slots, the bulk interpreter's points per wave and which of its kernels
+    MeshJob(fhip_ctx* c, uint32_t depth_, uint32_t part_, uint32_t n_parts_, MeshDoes d) : ctx(c), depth(depth_), part(part_), n_parts(n_parts_), does(d) {}
+    const fh::HostTape& t() const { return tape->t; }
+    fhip_status hip_failed(const char* call, hipError_t e) { return fail(ctx, FHIP_ERR_HIP, std::string(call) + ": " + hipGetErrorString(e)); }
+    // ---- stage 1: the arguments, the tape on the device, the kernels' parameters
+    fhip_status prepare(const fhip_tape* tape_, const float* world_to_model, const int32_t* axis_slots, const uint64_t* var_keys, const float* var_values, uint32_t n_vars) {
+        if (does.occupancy && depth > 10) return fail(ctx, FHIP_ERR_UNSUPPORTED, "occupancy depth above 10: the second moments of a grid of more than 4096^3 voxels overflow 64 bits");
+        if (depth > 20) return fail(ctx, FHIP_ERR_UNSUPPORTED, "octree depth above 20");
+        if (n_parts < 1 || n_parts > 8 || part >= n_parts) return fail(ctx, FHIP_ERR_UNSUPPORTED, "mesh parts: 1..8, part < n_parts");
+        tape = tape_;
+        if (tape->t.n_vars > FH_MAX_INPUTS) {
+            const fhip_status bs = bound_tape(ctx, tape, axis_slots, var_keys, var_values, n_vars, bound);
+            if (bs) return bs;
+            tape = bound.get();
+            axis_slots = BOUND_AXES; var_keys = nullptr; var_values = nullptr; n_vars = 0;
         }
-        MESH_TRY(hipStreamSynchronize(ctx->stream));
-        const uint32_t n_here = child_mask == 0xFFu ? n : (uint32_t)__builtin_popcount(child_mask);
-        M->cells_evaluated += n_here; M->full += c[1]; M->empty += c[2];
-        M->per_level.push_back(n_here);
-        if (occ_mode && c[1]) {      // this level's Full cells: their closed forms (the parents' paths are still in in_cells)
-            const uint32_t nb = std::min<uint32_t>((n + 255) / 256, FH_OCC_FULL_BLOCKS);
-            hipLaunchKernelGGL(fhm::k_occ_full, dim3(nb), dim3(256), 0, ctx->stream, (const FhMeshCell*)in_cells, (const uint8_t*)cls_p, n, d == 0 ? 0 : 1, d, depth,
-                               (FhOccPart*)occ_parts.p + occ_used);
-            MESH_TRY(hipGetLastError());
-            occ_used += nb;
-        }
-        cur ^= 1;
-        n_in = c[0];
-        lv_n_amb.push_back(c[0]);
-        if (d == depth) n_leaf_cells = c[0];
-        if (n_in == 0) break;
-        if (d == split_level && split_level > 0) {
-            // Tape simplification down the octree (octree.rs:546-553), once: the choices of the root tape over every ambiguous cell of this
-            // level (k_mesh_choices), VmData::simplify under them on the host's threads, the simplified tapes back as one array with a
-            // table indexed by the cell's path; every launch from here on gives a lane the tape of its cell's ancestor at this level.
-            const uint32_t na = c[0], nch = t.n_choices;
-            MESH_TRY(sub_choices.ensure((size_t)na * nch));
-            hipLaunchKernelGGL(fhm::k_mesh_choices, dim3((na + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, (const FhMeshCell*)out_cells.p, na, nch, (uint8_t*)sub_choices.p);
-            MESH_TRY(hipGetLastError());
-            std::vector<uint8_t> ch((size_t)na * nch);
-            std::vector<FhMeshCell> amb(na);
-            MESH_TRY(hipMemcpyAsync(ch.data(), sub_choices.p, ch.size(), hipMemcpyDeviceToHost, ctx->stream));
-            MESH_TRY(hipMemcpyAsync(amb.data(), out_cells.p, (size_t)na * sizeof(FhMeshCell), hipMemcpyDeviceToHost, ctx->stream));
-            MESH_TRY(hipStreamSynchronize(ctx->stream));
-            std::vector<fh::HostTape> sub(na);
-            std::vector<uint8_t> ok(na, 0);
-            fhmesh::parallel_for(na, [&](size_t j) { ok[j] = simplify_host(t, ch.data() + j * nch, sub[j]) ? 1 : 0; });
-            const size_t n_tab = (size_t)1 << (3 * split_level);
-            std::vector<uint2> tab(n_tab, make_uint2(0, 0));
-            std::vector<uint64_t> ops;
-            sub_of.assign(n_tab, -1);
-            for (uint32_t j = 0; j < na; j++) {
-                if (!ok[j] || sub[j].ops.empty() || sub[j].ops.size() >= t.ops.size()) continue;     // (nothing gained: the root tape)
-                const uint64_t idx = amb[j].path - ((uint64_t)1 << (3 * split_level));
-                if (idx >= n_tab) continue;
-                tab[(size_t)idx] = make_uint2((uint32_t)ops.size(), (uint32_t)sub[j].ops.size());
-                ops.insert(ops.end(), sub[j].ops.begin(), sub[j].ops.end());
-                M->sub_tapes++; M->sub_ops += sub[j].ops.size();
-                if (split_level2) { sub_of[(size_t)idx] = (int32_t)sub_keep.size(); sub_keep.push_back(std::move(sub[j])); }
-            }
-            // ... where it pays: the lanes of a wave then walk tapes of their own through the generic interpreter, and a tape that fits the
-            // assembly bulk interpreter (<= 32 registers) gives that up for its leaf samples - bear.vm's smooth blend keeps 3/4 of its ops
-            // at this level and meshes twice as fast WITHOUT (measured, profiles/r04g); prospero.vm keeps 1/20 and gains 16x
-            const double kept = M->sub_tapes ? (double)M->sub_ops / ((double)M->sub_tapes * (double)t.ops.size()) : 1.0;
-            const bool bulk_capable = ctx->use_asm && P.n_regs <= 32;
-            if (kept >= (bulk_capable ? 0.25 : 0.75)) { ops.clear(); M->sub_skipped = M->sub_tapes; M->sub_tapes = 0; sub_keep.clear(); }
-            if (!ops.empty()) {
-                MESH_TRY(sub_ops.ensure(ops.size() * 8));
-                MESH_TRY(sub_tab.ensure(n_tab * sizeof(uint2)));
-                MESH_TRY(hipMemcpyAsync(sub_ops.p, ops.data(), ops.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-                MESH_TRY(hipMemcpyAsync(sub_tab.p, tab.data(), n_tab * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-                MESH_TRY(hipStreamSynchronize(ctx->stream));
-                P.sub_ops = (const uint64_t*)sub_ops.p; P.sub_tab = (const uint2*)sub_tab.p; P.split_level = split_level;
+        if (t().n_outputs != 1) return fail(ctx, FHIP_ERR_BAD_TAPE, "shape tapes have exactly one output");
+        (void)hipSetDevice(ctx->device);
+        { fhip_status ts_ = tape_to_device(ctx, tape); if (ts_) return ts_; }
+        FhRender R;
+        memset(&R, 0, sizeof(R));
+        const fhip_status st = bind_inputs(ctx, tape, axis_slots, var_keys, var_values, n_vars, R);
+        if (st) return st;
+        memset(&P, 0, sizeof(P));
+        P.tape = tape->d_ops; P.len = (uint32_t)t().ops.size(); P.n_regs = std::max<uint32_t>(t().n_regs, 1);
+        bool ident = true;
+        if (world_to_model) for (int i = 0; i < 16; i++) { P.mat[i] = world_to_model[i]; ident &= world_to_model[i] == ((i % 5 == 0) ? 1.0f : 0.0f); }
+        P.has_mat = (world_to_model && !ident) ? 1 : 0;     // octree.rs:487-492: no transform at all for the identity
+        for (int s = 0; s < FH_MAX_INPUTS; s++) { P.in_kind[s] = R.in_kind[s]; P.in_value[s] = R.in_value[s]; }
+        lds_iv = (size_t)P.n_regs * WAVE * 8; lds_leaf = (size_t)P.n_regs * WAVE * 16; lds_f32 = (size_t)P.n_regs * WAVE * 4;
+        if (lds_leaf + 1024 > FH_LDS_MAX) return fail(ctx, FHIP_ERR_UNSUPPORTED, "register file exceeds LDS");
+        {   // (function attributes are per device; contexts on several host threads may arrive here together)
+            static std::mutex attr_lock;
+            static bool attr_done[64] = {};
+            std::lock_guard<std::mutex> guard(attr_lock);
+            const int d = ctx->device & 63;
+            if (!attr_done[d]) {
+                const void* const all_lds[] = {(const void*)fhm::k_mesh_cells, (const void*)fhm::k_mesh_choices, (const void*)fhm::k_mesh_corners, (const void*)fhm::k_mesh_edges,
+                                               (const void*)fhm::k_mesh_grads, (const void*)fhm::k_occ_leaves};
+                for (const void* k : all_lds) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
+                (void)hipFuncSetAttribute((const void*)fhm::k_mesh_leaf, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX - 2048);
+                attr_done[d] = true;
             }
         }
-        // (only where the first split left tapes worth pruning again: 128 ops on average - colonnade.vm's are ~50 and a second split cost it 20 %)
-        if (d == split_level2 && split_level2 > 0 && P.sub_tab && !sub_keep.empty() && M->sub_ops >= 128 * M->sub_tapes) {
-            // The second split: the choices of every ambiguous cell of this level over the tape it inherited (its level-4 ancestor's),
-            // VmData::simplify of THAT tape under them, a second table for everything below.
-            const uint32_t na = c[0];
-            uint32_t nch = 1;
-            for (const fh::HostTape& st : sub_keep) nch = std::max(nch, st.n_choices);
-            if ((size_t)na * nch <= ((size_t)3 << 30)) {
-                MESH_TRY(sub_choices.ensure((size_t)na * nch));
-                hipLaunchKernelGGL(fhm::k_mesh_choices, dim3((na + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, (const FhMeshCell*)out_cells.p, na, nch, (uint8_t*)sub_choices.p);
-                MESH_TRY(hipGetLastError());
-                std::vector<uint8_t> ch((size_t)na * nch);
-                std::vector<FhMeshCell> amb(na);
-                MESH_TRY(hipMemcpyAsync(ch.data(), sub_choices.p, ch.size(), hipMemcpyDeviceToHost, ctx->stream));
-                MESH_TRY(hipMemcpyAsync(amb.data(), out_cells.p, (size_t)na * sizeof(FhMeshCell), hipMemcpyDeviceToHost, ctx->stream));
-                MESH_TRY(hipStreamSynchronize(ctx->stream));
-                std::vector<fh::HostTape> sub2(na);
-                std::vector<uint8_t> ok(na, 0);
-                const int up = 3 * (int)(split_level2 - split_level);
-                const uint64_t base1 = (uint64_t)1 << (3 * split_level);
-                fhmesh::parallel_for(na, [&](size_t j) {
-                    const uint64_t i1 = (amb[j].path >> up) - base1;
-                    const int32_t k1 = i1 < sub_of.size() ? sub_of[(size_t)i1] : -1;
-                    if (k1 < 0) return;          // (its ancestor kept the root tape: so does it)
-                    const fh::HostTape& parent = sub_keep[(size_t)k1];
-                    ok[j] = simplify_host(parent, ch.data() + j * nch, sub2[j]) && !sub2[j].ops.empty() && sub2[j].ops.size() < parent.ops.size() ? 1 : 0;
-                });
-                const size_t n_tab2 = (size_t)1 << (3 * split_level2);
-                std::vector<uint2> tab2(n_tab2, make_uint2(0, 0));
-                std::vector<uint64_t> ops2;
-                uint64_t n2 = 0;
-                for (uint32_t j = 0; j < na; j++) {
-                    if (!ok[j]) continue;
-                    const uint64_t idx = amb[j].path - ((uint64_t)1 << (3 * split_level2));
-                    if (idx >= n_tab2 || ops2.size() + sub2[j].ops.size() >= ((size_t)1 << 32)) continue;
-                    tab2[(size_t)idx] = make_uint2((uint32_t)ops2.size(), (uint32_t)sub2[j].ops.size());
-                    ops2.insert(ops2.end(), sub2[j].ops.begin(), sub2[j].ops.end());
-                    n2++;
-                }
-                if (!ops2.empty()) {
-                    MESH_TRY(sub_ops2.ensure(ops2.size() * 8));
-                    MESH_TRY(sub_tab2.ensure(n_tab2 * sizeof(uint2)));
-                    MESH_TRY(hipMemcpyAsync(sub_ops2.p, ops2.data(), ops2.size() * 8, hipMemcpyHostToDevice, ctx->stream));
-                    MESH_TRY(hipMemcpyAsync(sub_tab2.p, tab2.data(), n_tab2 * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
-                    MESH_TRY(hipStreamSynchronize(ctx->stream));
-                    P.sub_ops2 = (const uint64_t*)sub_ops2.p; P.sub_tab2 = (const uint2*)sub_tab2.p; P.split_level2 = split_level2;
-                    if (times) fprintf(stderr, "fhip mesh: tape simplified again at level %u: %llu cells with tapes of their own, %.1f ops on average\n", split_level2,
-                                       (unsigned long long)n2, (double)ops2.size() / (double)n2);
-                }
-            }
-        }
+        M.reset(new fhip_mesh());
+        M->depth = depth; M->part = part; M->n_parts = n_parts;
+        t_start = mesh_now();
+        return FHIP_OK;
     }
-    M->ambiguous_leaves = n_leaf_cells;
-    t_cells = now() - t_start;
-    if (times && (M->sub_tapes || M->sub_skipped))
-        fprintf(stderr, "fhip mesh: tape simplified at level %u: %llu cells with tapes of their own, %.1f ops on average (root tape: %zu)%s\n", split_level,
-                (unsigned long long)(M->sub_tapes + M->sub_skipped), (double)M->sub_ops / (double)(M->sub_tapes + M->sub_skipped), t.ops.size(),
-                M->sub_skipped ? " - not used: too little gained" : "");
-    if (occ_mode) {
+    // ---- stage 2: the level loop - k_mesh_cells over the children of the level above's ambiguous cells, down to the leaf depth
+    fhip_status descend() {
+        if (does.keep_dev_levels) { lv_cls.resize(depth + 1); lv_slot.resize(depth + 1); lv_amb.resize(depth + 1); }
+        MESH_CHECK(counters.ensure(16));
+        if (does.occupancy) MESH_CHECK(occ_parts.ensure(((size_t)(depth + 1) * FH_OCC_FULL_BLOCKS + FH_OCC_LEAF_BLOCKS) * sizeof(FhOccPart)));
+        FhMeshCell root;
+        for (int k = 0; k < 3; k++) { root.b[2 * k] = -1.0f; root.b[2 * k + 1] = 1.0f; }     // CellBounds::new (cell.rs:171-176)
+        root.path = 1;
+        MESH_CHECK(bufs[0].ensure(sizeof(FhMeshCell)));
+        MESH_CHECK(hipMemcpyAsync(bufs[0].p, &root, sizeof(root), hipMemcpyHostToDevice, ctx->stream));
+        split = fhsplit::split_levels(ctx->opt.mesh_simplify_min_ops, t().ops.size(), t().n_choices, depth);
+        uint32_t n_in = 1;      // cells in bufs[cur] to evaluate (level 0) or whose 8 children to evaluate
+        for (uint32_t d = 0; d <= depth; d++) {
+            const uint64_t n64 = d == 0 ? 1 : (uint64_t)n_in * 8;
+            if (n64 > (1ull << 30)) return fail(ctx, FHIP_ERR_OVERFLOW, "octree level above 2^30 cells");
+            const uint32_t n = (uint32_t)n64;
+            DevBuf& out_cells = does.keep_dev_levels ? lv_amb[d] : bufs[cur ^ 1];
+            const void* in_cells = (does.keep_dev_levels && d > 0) ? lv_amb[d - 1].p : bufs[cur].p;
+            MESH_CHECK(out_cells.ensure((size_t)n * sizeof(FhMeshCell)));
+            MESH_CHECK(hipMemsetAsync(counters.p, 0, 16, ctx->stream));
+            if (does.need_classes) { MESH_CHECK(d_cls.ensure(n)); MESH_CHECK(d_slot.ensure((size_t)n * 4)); }
+            if (does.keep_dev_levels) { MESH_CHECK(lv_cls[d].ensure(n)); MESH_CHECK(lv_slot[d].ensure((size_t)n * 4)); }
+            uint8_t* const cls_p = does.keep_dev_levels ? (uint8_t*)lv_cls[d].p : (does.need_classes ? (uint8_t*)d_cls.p : nullptr);
+            uint32_t* const slot_p = does.keep_dev_levels ? (uint32_t*)lv_slot[d].p : (does.need_classes ? (uint32_t*)d_slot.p : nullptr);
+            const uint32_t child_mask = (d == 1 && n_parts > 1) ? mesh_part_mask(part, n_parts) : 0xFFu;      // (level 1 = the root's 8 children)
+            hipLaunchKernelGGL(fhm::k_mesh_cells, dim3((n + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, (const FhMeshCell*)in_cells, n, d == 0 ? 0 : 1,
+                               (FhMeshCell*)out_cells.p, (uint32_t*)counters.p, n, cls_p, slot_p, child_mask);
+            MESH_CHECK(hipGetLastError());
+            uint32_t c[4];
+            MESH_CHECK(hipMemcpyAsync(c, counters.p, 16, hipMemcpyDeviceToHost, ctx->stream));
+            if (does.keep_host_levels) {
+                M->cls.emplace_back(n); M->slot.emplace_back(n);
+                MESH_CHECK(hipMemcpyAsync(M->cls.back().data(), d_cls.p, n, hipMemcpyDeviceToHost, ctx->stream));
+                MESH_CHECK(hipMemcpyAsync(M->slot.back().data(), d_slot.p, (size_t)n * 4, hipMemcpyDeviceToHost, ctx->stream));
+            }
+            MESH_CHECK(hipStreamSynchronize(ctx->stream));
+            const uint32_t n_here = child_mask == 0xFFu ? n : (uint32_t)__builtin_popcount(child_mask);
+            M->cells_evaluated += n_here; M->full += c[1]; M->empty += c[2]; M->per_level.push_back(n_here);
+            if (does.occupancy && c[1]) {      // this level's Full cells: their closed forms (the parents' paths are still in in_cells)
+                const uint32_t nb = std::min<uint32_t>((n + 255) / 256, FH_OCC_FULL_BLOCKS);
+                hipLaunchKernelGGL(fhm::k_occ_full, dim3(nb), dim3(256), 0, ctx->stream, (const FhMeshCell*)in_cells, (const uint8_t*)cls_p, n, d == 0 ? 0 : 1, d, depth,
+                                   (FhOccPart*)occ_parts.p + occ_used);
+                MESH_CHECK(hipGetLastError());
+                occ_used += nb;
+            }
+            cur ^= 1; n_in = c[0]; lv_n_amb.push_back(c[0]);
+            if (d == depth) n_leaf_cells = c[0];
+            if (n_in == 0) break;
+            if (d == split.l1 && split.l1 > 0) { const fhip_status s = first_split((const FhMeshCell*)out_cells.p, c[0]); if (s) return s; }
+            if (d == split.l2 && split.l2 > 0) { const fhip_status s = second_split((const FhMeshCell*)out_cells.p, c[0]); if (s) return s; }
+        }
+        M->ambiguous_leaves = n_leaf_cells;
+        t_cells = mesh_now() - t_start;
+        if (times && (M->sub_tapes || M->sub_skipped))
+            fprintf(stderr, "fhip mesh: tape simplified at level %u: %llu cells with tapes of their own, %.1f ops on average (root tape: %zu)%s\n", split.l1,
+                    (unsigned long long)(M->sub_tapes + M->sub_skipped), (double)M->sub_ops / (double)(M->sub_tapes + M->sub_skipped), t().ops.size(),
+                    M->sub_skipped ? " - not used: too little gained" : "");
+        return FHIP_OK;
+    }
+    // Tape simplification down the octree (octree.rs:546-553) at one level: the choices over every ambiguous cell of the level of the tape the
+    // cell has so far (k_mesh_choices), VmData::simplify of that tape under them on the host's threads, the simplified tapes back as one array
+    // with a table indexed by the cell's path (mesh_split.hpp); every launch from here on gives a lane the tape of its cell's ancestor at
+    // this level.  `parent_of`: the tape a cell has so far, null: none worth simplifying.  `use`: what the caller makes of the result before
+    // it travels - false: the split is not used.  `into`: the buffers and the fields of P the kernels find it by.
+    struct SplitInto { DevBuf& ops; DevBuf& tab; const uint64_t*& p_ops; const uint2*& p_tab; uint32_t& p_level; };
+    fhip_status split_tapes(uint32_t level, const FhMeshCell* cells, uint32_t na, uint32_t nch, uint64_t ops_limit, const std::function<const fh::HostTape*(uint64_t)>& parent_of,
+                            const std::function<bool(const fhsplit::SplitPack&, const uint64_t*, std::vector<fh::HostTape>&)>& use, SplitInto into, fhsplit::SplitPack& S) {
+        MESH_CHECK(sub_choices.ensure((size_t)na * nch));
+        hipLaunchKernelGGL(fhm::k_mesh_choices, dim3((na + WAVE - 1) / WAVE), dim3(WAVE), lds_iv, ctx->stream, P, cells, na, nch, (uint8_t*)sub_choices.p);
+        MESH_CHECK(hipGetLastError());
+        std::vector<uint8_t> ch((size_t)na * nch); std::vector<FhMeshCell> amb(na);
+        MESH_CHECK(hipMemcpyAsync(ch.data(), sub_choices.p, ch.size(), hipMemcpyDeviceToHost, ctx->stream));
+        MESH_CHECK(hipMemcpyAsync(amb.data(), cells, (size_t)na * sizeof(FhMeshCell), hipMemcpyDeviceToHost, ctx->stream));
+        MESH_CHECK(hipStreamSynchronize(ctx->stream));
+        std::vector<fh::HostTape> sub(na); std::vector<uint8_t> ok(na, 0);
+        fhmesh::parallel_for(na, [&](size_t j) {
+            const fh::HostTape* const parent = parent_of(amb[j].path);
+            if (!parent) return;
+            const bool simplified = simplify_host(*parent, ch.data() + j * nch, sub[j]);
+            ok[j] = fhsplit::split_accepts(simplified, sub[j].ops.size(), parent->ops.size()) ? 1 : 0;     // (nothing gained: the tape it has)
+        });
+        std::vector<uint64_t> path(na); std::vector<const uint64_t*> ops(na); std::vector<size_t> len(na);      // the candidates, as pack_split takes them
+        for (uint32_t j = 0; j < na; j++) { path[j] = amb[j].path; ops[j] = ok[j] ? sub[j].ops.data() : nullptr; len[j] = sub[j].ops.size(); }
+        S = fhsplit::pack_split(level, na, path.data(), ops.data(), len.data(), ops_limit);
+        if ((use && !use(S, path.data(), sub)) || S.ops.empty()) return FHIP_OK;
+        MESH_CHECK(into.ops.ensure(S.ops.size() * 8));
+        MESH_CHECK(into.tab.ensure(S.tab.size() * sizeof(uint2)));
+        MESH_CHECK(hipMemcpyAsync(into.ops.p, S.ops.data(), S.ops.size() * 8, hipMemcpyHostToDevice, ctx->stream));
+        MESH_CHECK(hipMemcpyAsync(into.tab.p, S.tab.data(), S.tab.size() * sizeof(uint2), hipMemcpyHostToDevice, ctx->stream));
+        MESH_CHECK(hipStreamSynchronize(ctx->stream));
+        into.p_ops = (const uint64_t*)into.ops.p; into.p_tab = (const uint2*)into.tab.p; into.p_level = level;
+        return FHIP_OK;
+    }
+    // once, from the root tape, where the split pays (mesh_split.hpp split_worth_using)
+    fhip_status first_split(const FhMeshCell* cells, uint32_t na) {
+        auto use = [&](const fhsplit::SplitPack& got, const uint64_t* path, std::vector<fh::HostTape>& sub) {
+            M->sub_tapes = got.n_tapes; M->sub_ops = got.n_ops;
+            if (!fhsplit::split_worth_using(got.n_ops, got.n_tapes, t().ops.size(), ctx->use_asm && P.n_regs <= 32)) { M->sub_skipped = M->sub_tapes; M->sub_tapes = 0; return false; }
+            sub_of.assign(got.tab.size(), -1);
+            if (split.l2) for (uint32_t j : got.taken) { sub_of[(size_t)(path[j] - fhsplit::level_base(split.l1))] = (int32_t)sub_keep.size(); sub_keep.push_back(std::move(sub[j])); }
+            return true;
+        };
+        fhsplit::SplitPack S;
+        return split_tapes(split.l1, cells, na, t().n_choices, fhsplit::NO_OPS_LIMIT, [&](uint64_t) { return &t(); }, use, SplitInto{sub_ops, sub_tab, P.sub_ops, P.sub_tab, P.split_level}, S);
+    }
+    // The second split: the choices of every ambiguous cell of this level over the tape it inherited (its level-4 ancestor's),
+    // VmData::simplify of THAT tape under them, a second table for everything below (mesh_split.hpp second_split_wanted: when)
+    fhip_status second_split(const FhMeshCell* cells, uint32_t na) {
+        uint32_t nch = 1;
+        for (const fh::HostTape& st : sub_keep) nch = std::max(nch, st.n_choices);
+        if (!fhsplit::second_split_wanted(P.sub_tab != nullptr, sub_keep.size(), M->sub_ops, M->sub_tapes, na, nch)) return FHIP_OK;
+        fhsplit::SplitPack S;
+        auto inherited = [&](uint64_t path) -> const fh::HostTape* {      // (null: its ancestor kept the root tape, and so does it)
+            const int32_t k1 = fhsplit::split_parent(sub_of, path, split.l1, split.l2);
+            return k1 < 0 ? nullptr : &sub_keep[(size_t)k1];
+        };
+        const fhip_status st = split_tapes(split.l2, cells, na, nch, fhsplit::OPS_LIMIT_32, inherited, nullptr, SplitInto{sub_ops2, sub_tab2, P.sub_ops2, P.sub_tab2, P.split_level2}, S);
+        if (!st && times && P.sub_tab2)
+            fprintf(stderr, "fhip mesh: tape simplified again at level %u: %llu cells with tapes of their own, %.1f ops on average\n", split.l2,
+                    (unsigned long long)S.n_tapes, (double)S.ops.size() / (double)S.n_tapes);
+        return st;
+    }
+    // ---- stage 3 (occupancy): the ambiguous cells of the last level voxel by voxel, then the partial records added up on the host
+    fhip_status occupancy_finish(fhip_occupancy* occ) {
         if (n_leaf_cells) {
             const uint32_t nb = std::min<uint32_t>(n_leaf_cells, FH_OCC_LEAF_BLOCKS);
-            hipLaunchKernelGGL(fhm::k_occ_leaves, dim3(nb), dim3(WAVE), (size_t)P.n_regs * WAVE * 4, ctx->stream, P, (const FhMeshCell*)bufs[cur].p, n_leaf_cells, depth,
+            hipLaunchKernelGGL(fhm::k_occ_leaves, dim3(nb), dim3(WAVE), lds_f32, ctx->stream, P, (const FhMeshCell*)bufs[cur].p, n_leaf_cells, depth,
                                (FhOccPart*)occ_parts.p + occ_used);
-            MESH_TRY(hipGetLastError());
+            MESH_CHECK(hipGetLastError());
             occ_used += nb;
         }
         std::vector<FhOccPart> parts(occ_used);
-        if (occ_used) MESH_TRY(hipMemcpyAsync(parts.data(), occ_parts.p, (size_t)occ_used * sizeof(FhOccPart), hipMemcpyDeviceToHost, ctx->stream));
-        MESH_TRY(hipStreamSynchronize(ctx->stream));
+        if (occ_used) MESH_CHECK(hipMemcpyAsync(parts.data(), occ_parts.p, (size_t)occ_used * sizeof(FhOccPart), hipMemcpyDeviceToHost, ctx->stream));
+        MESH_CHECK(hipStreamSynchronize(ctx->stream));
         const uint32_t N = 4u << depth;
         memset(occ, 0, sizeof(*occ));
         occ->grid = N;
@@ -648,59 +646,50 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
             for (int k = 0; k < 6; k++) occ->s2[k] += q.s2[k];
         }
         occ->cells[0] = M->cells_evaluated; occ->cells[1] = M->full; occ->cells[2] = M->empty; occ->cells[3] = M->ambiguous_leaves;
-        if (times) fprintf(stderr, "fhip occupancy depth %u: %.4f s (%llu cells evaluated, %u leaf cells, %u partial records)\n", depth, now() - t_start,
+        if (times) fprintf(stderr, "fhip occupancy depth %u: %.4f s (%llu cells evaluated, %u leaf cells, %u partial records)\n", depth, mesh_now() - t_start,
                            (unsigned long long)M->cells_evaluated, n_leaf_cells, occ_used);
-        cleanup();
-        *out = M;
         return FHIP_OK;
     }
-    FhMdcTable mdc;
-    if (n_leaf_cells || dev_asm) {
-        build_mdc_table(mdc);
-        MESH_TRY(table.ensure(sizeof(mdc)));
-        MESH_TRY(hipMemcpyAsync(table.p, &mdc, sizeof(mdc), hipMemcpyHostToDevice, ctx->stream));
-    }
-    // one chunk of leaf cells sampled into records: as passes in which every lane has a point of its own (corners, the edge search over the
-    // chunk's list of edges, gradients), or - FHIP_MESH_LEAF_PASSES=0 - one wavefront per cell (k_mesh_leaf); then the cell vertices' QEFs
-    const uint32_t LEAF_CH = 1u << 19;
-    const char* const lp_env = getenv("FHIP_MESH_LEAF_PASSES");        // diagnostic: 0 = k_mesh_leaf, the kernel the passes are checked against
-    const bool leaf_passes = !(lp_env && lp_env[0] == '0');
-    const char* const be_env = getenv("FHIP_MESH_BULK_EDGES");          // diagnostic: 0 = the edge search by k_mesh_edges (the generic interpreter)
-    const bool bulk_edges = leaf_passes && ctx->use_asm && P.n_regs <= 32 && !(be_env && be_env[0] == '0') && !P.sub_tab;     // (one tape per launch)
-    uint32_t n_slots = std::max<uint32_t>(t.n_vars, 1);
-    for (uint32_t sl = 0; sl < FH_MAX_INPUTS; sl++) if (P.in_kind[sl] < 3) n_slots = std::max(n_slots, sl + 1);
-    const size_t lds_f32 = (size_t)P.n_regs * WAVE * 4;
-    auto sample_chunk = [&](const FhMeshCell* cells, FhMeshLeaf* recs, uint32_t cnt) -> hipError_t {
+    // ---- stage 3 (meshes): the leaf cells sampled into records, LEAF_CH cells at a time
+    static hipError_t first_of(hipError_t a, hipError_t b) { return a != hipSuccess ? a : b; }
+    // the slots bound to a value, for `n` points of the bulk interpreter's input
+    hipError_t fill_bound_slots(uint32_t n) {
         hipError_t e = hipSuccess;
-        auto ck = [&](hipError_t x) { if (x != hipSuccess && e == hipSuccess) e = x; };
+        for (uint32_t sl = 0; sl < n_slots; sl++)
+            if (P.in_kind[sl] >= 3) {
+                hipLaunchKernelGGL(fhm::k_mesh_fill, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float*)edge_vars.p + (size_t)sl * n, P.in_value[sl], n);
+                e = first_of(e, hipGetLastError());
+            }
+        return e;
+    }
+    // the root tape over `n` points, edge_vars -> edge_vals, through the assembly bulk interpreter
+    hipError_t bulk_eval(uint32_t n) {
+        struct { const uint64_t* tape; const float* vars; float* out; uint32_t len, n; } ka = {tape->d_ops, (const float*)edge_vars.p, (float*)edge_vals.p, P.len, n};
+        return launch_asm(ctx, ctx->stream, bulk_which, (n + bulk_per - 1) / bulk_per, &ka, sizeof(ka));
+    }
+    // one chunk: as passes in which every lane has a point of its own (corners, the edge search over the chunk's list of edges, gradients),
+    // or - FHIP_MESH_LEAF_PASSES=0 - one wavefront per cell (k_mesh_leaf); then the cell vertices' QEFs
+    hipError_t sample_chunk(const FhMeshCell* cells, FhMeshLeaf* recs, uint32_t cnt) {
+        hipError_t e = hipSuccess;
+        auto ck = [&](hipError_t x) { e = first_of(e, x); };
+        const FhMdcTable* const mdc_d = (const FhMdcTable*)table.p;
         if (leaf_passes && cnt < (1u << 28)) {
-            ck(edge_list.ensure((size_t)LEAF_CH * 12 * 4));
-            ck(edge_count.ensure(4));
+            ck(edge_list.ensure((size_t)LEAF_CH * 12 * 4)); ck(edge_count.ensure(4));
             if (e != hipSuccess) return e;
             ck(hipMemsetAsync(edge_count.p, 0, 4, ctx->stream));
             if (bulk_edges) {      // the corners through the assembly bulk interpreter too (k_mesh_corners: 48 of a 350 ms build through the generic one)
                 const uint32_t np = cnt * 8u;
-                ck(edge_vars.ensure((size_t)n_slots * np * 4));
-                ck(edge_vals.ensure((size_t)np * 4));
+                ck(edge_vars.ensure((size_t)n_slots * np * 4)); ck(edge_vals.ensure((size_t)np * 4));
                 if (e != hipSuccess) return e;
-                for (uint32_t sl = 0; sl < n_slots; sl++)
-                    if (P.in_kind[sl] >= 3) {
-                        hipLaunchKernelGGL(fhm::k_mesh_fill, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, (float*)edge_vars.p + (size_t)sl * np, P.in_value[sl], np);
-                        ck(hipGetLastError());
-                    }
+                ck(fill_bound_slots(np));
                 hipLaunchKernelGGL(fhm::k_mesh_corner_points, dim3((np + 255) / 256), dim3(256), 0, ctx->stream, P, cells, cnt, (float*)edge_vars.p);
                 ck(hipGetLastError());
-                struct { const uint64_t* tape; const float* vars; float* out; uint32_t len, n; } kc = {tape->d_ops, (const float*)edge_vars.p, (float*)edge_vals.p, P.len, np};
-                const bool plain_c = tape_asm_ok(t);
-                const uint32_t per_c = P.n_regs <= 16 ? 256 : 128;
-                const int which_c = P.n_regs <= 16 ? (plain_c ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain_c ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T);
-                ck(launch_asm(ctx, ctx->stream, which_c, (np + per_c - 1) / per_c, &kc, sizeof(kc)));
-                hipLaunchKernelGGL(fhm::k_mesh_corner_masks, dim3((cnt + 7) / 8), dim3(WAVE), 0, ctx->stream, cells, cnt, (const float*)edge_vals.p, (const FhMdcTable*)table.p, recs,
+                ck(bulk_eval(np));
+                hipLaunchKernelGGL(fhm::k_mesh_corner_masks, dim3((cnt + 7) / 8), dim3(WAVE), 0, ctx->stream, cells, cnt, (const float*)edge_vals.p, mdc_d, recs,
                                    (uint32_t*)edge_count.p, (uint32_t*)edge_list.p);
                 ck(hipGetLastError());
             } else {
-                hipLaunchKernelGGL(fhm::k_mesh_corners, dim3((cnt + 7) / 8), dim3(WAVE), lds_f32, ctx->stream, P, cells, cnt, (const FhMdcTable*)table.p, recs,
-                                   (uint32_t*)edge_count.p, (uint32_t*)edge_list.p);
+                hipLaunchKernelGGL(fhm::k_mesh_corners, dim3((cnt + 7) / 8), dim3(WAVE), lds_f32, ctx->stream, P, cells, cnt, mdc_d, recs, (uint32_t*)edge_count.p, (uint32_t*)edge_list.p);
                 ck(hipGetLastError());
             }
             uint32_t n_edges = 0;
@@ -709,27 +698,17 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
             if (e == hipSuccess && n_edges && bulk_edges) {
                 // the four rounds as passes over the chunk's edges, the samples' values from the assembly bulk interpreter (mesh_edges.hpp)
                 const uint32_t n = n_edges * 16u;
-                ck(edge_br.ensure((size_t)n_edges * sizeof(fhmesh::EdgeBracket)));
-                ck(edge_vars.ensure((size_t)n_slots * n * 4));
-                ck(edge_vals.ensure((size_t)n * 4));
+                ck(edge_br.ensure((size_t)n_edges * sizeof(fhmesh::EdgeBracket))); ck(edge_vars.ensure((size_t)n_slots * n * 4)); ck(edge_vals.ensure((size_t)n * 4));
                 if (e != hipSuccess) return e;
-                hipLaunchKernelGGL(fhm::k_mesh_edge_begin, dim3((n_edges + 255) / 256), dim3(256), 0, ctx->stream, (const FhMdcTable*)table.p, (const FhMeshLeaf*)recs,
-                                   (const uint32_t*)edge_list.p, n_edges, (fhmesh::EdgeBracket*)edge_br.p);
+                hipLaunchKernelGGL(fhm::k_mesh_edge_begin, dim3((n_edges + 255) / 256), dim3(256), 0, ctx->stream, mdc_d, (const FhMeshLeaf*)recs, (const uint32_t*)edge_list.p, n_edges,
+                                   (fhmesh::EdgeBracket*)edge_br.p);
                 ck(hipGetLastError());
-                for (uint32_t sl = 0; sl < n_slots; sl++)
-                    if (P.in_kind[sl] >= 3) {
-                        hipLaunchKernelGGL(fhm::k_mesh_fill, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, (float*)edge_vars.p + (size_t)sl * n, P.in_value[sl], n);
-                        ck(hipGetLastError());
-                    }
-                struct { const uint64_t* tape; const float* vars; float* out; uint32_t len, n; } ka = {tape->d_ops, (const float*)edge_vars.p, (float*)edge_vals.p, P.len, n};
-                const bool plain = tape_asm_ok(t);
-                const uint32_t per = P.n_regs <= 16 ? 256 : 128;
-                const int which = P.n_regs <= 16 ? (plain ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T);
+                ck(fill_bound_slots(n));
                 for (int round = 0; round < 4 && e == hipSuccess; round++) {
                     hipLaunchKernelGGL(fhm::k_mesh_edge_points, dim3((n + 255) / 256), dim3(256), 0, ctx->stream, P, (const FhMeshLeaf*)recs, (const uint32_t*)edge_list.p,
                                        (const fhmesh::EdgeBracket*)edge_br.p, n_edges, (float*)edge_vars.p, n);
                     ck(hipGetLastError());
-                    ck(launch_asm(ctx, ctx->stream, which, (n + per - 1) / per, &ka, sizeof(ka)));
+                    ck(bulk_eval(n));
                     hipLaunchKernelGGL(fhm::k_mesh_edge_narrow, dim3((n_edges + 255) / 256), dim3(256), 0, ctx->stream, (fhmesh::EdgeBracket*)edge_br.p, (const float*)edge_vals.p, n_edges);
                     ck(hipGetLastError());
                 }
@@ -738,53 +717,45 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
                 hipLaunchKernelGGL(fhm::k_mesh_grads, dim3((n_edges + WAVE - 1) / WAVE), dim3(WAVE), lds_leaf, ctx->stream, P, recs, (const uint32_t*)edge_list.p, n_edges);
                 ck(hipGetLastError());
             } else if (e == hipSuccess && n_edges) {
-                hipLaunchKernelGGL(fhm::k_mesh_edges, dim3((n_edges + 3) / 4), dim3(WAVE), lds_f32, ctx->stream, P, (const FhMdcTable*)table.p, recs, (const uint32_t*)edge_list.p, n_edges);
+                hipLaunchKernelGGL(fhm::k_mesh_edges, dim3((n_edges + 3) / 4), dim3(WAVE), lds_f32, ctx->stream, P, mdc_d, recs, (const uint32_t*)edge_list.p, n_edges);
                 ck(hipGetLastError());
                 hipLaunchKernelGGL(fhm::k_mesh_grads, dim3((n_edges + WAVE - 1) / WAVE), dim3(WAVE), lds_leaf, ctx->stream, P, recs, (const uint32_t*)edge_list.p, n_edges);
                 ck(hipGetLastError());
             }
         } else {
-            hipLaunchKernelGGL(fhm::k_mesh_leaf, dim3(cnt), dim3(WAVE), lds_leaf, ctx->stream, P, cells, cnt, (const FhMdcTable*)table.p, recs);
+            hipLaunchKernelGGL(fhm::k_mesh_leaf, dim3(cnt), dim3(WAVE), lds_leaf, ctx->stream, P, cells, cnt, mdc_d, recs);
             ck(hipGetLastError());
         }
-        hipLaunchKernelGGL(fhm::k_mesh_leaf_qef, dim3((cnt + WAVE - 1) / WAVE), dim3(WAVE), 0, ctx->stream, (const FhMdcTable*)table.p, recs, cnt);
+        hipLaunchKernelGGL(fhm::k_mesh_leaf_qef, dim3((cnt + WAVE - 1) / WAVE), dim3(WAVE), 0, ctx->stream, mdc_d, recs, cnt);
         ck(hipGetLastError());
         return e;
-    };
-    if (n_leaf_cells && dev_asm) {      // the records stay in HBM
-        MESH_TRY(leaves.ensure((size_t)n_leaf_cells * sizeof(FhMeshLeaf)));
-        const uint32_t CH = LEAF_CH;
-        const void* const leaf_cells = lv_amb[depth].p;
-        for (uint32_t off = 0; off < n_leaf_cells; off += CH) {
-            const uint32_t cnt = std::min<uint32_t>(CH, n_leaf_cells - off);
-            const hipError_t se = sample_chunk((const FhMeshCell*)leaf_cells + off, (FhMeshLeaf*)leaves.p + off, cnt);
-            MESH_TRY(se);
+    }
+    // the records stay in HBM (ctx->mesh_leaves), for the assembly on the device
+    fhip_status sample_resident() {
+        DevBuf& leaves = ctx->mesh_leaves;
+        for (uint32_t off = 0; off < n_leaf_cells; off += LEAF_CH) {
+            const uint32_t cnt = std::min<uint32_t>(LEAF_CH, n_leaf_cells - off);
+            MESH_CHECK(sample_chunk((const FhMeshCell*)lv_amb[depth].p + off, (FhMeshLeaf*)leaves.p + off, cnt));
         }
-        if (times) { MESH_TRY(hipStreamSynchronize(ctx->stream)); t_leaf = now() - t_start - t_cells; }
-    } else if (n_leaf_cells) {
-        MESH_TRY(leaves.ensure((size_t)n_leaf_cells * sizeof(FhMeshLeaf)));
-        // in chunks: the records of chunk k travel to the host (second stream) while chunk k + 1 is sampled
+        if (times) { MESH_CHECK(hipStreamSynchronize(ctx->stream)); t_leaf = mesh_now() - t_start - t_cells; }
+        return FHIP_OK;
+    }
+    // ... or travel to the host: the records of chunk k (second stream) while chunk k + 1 is sampled
+    fhip_status sample_to_host() {
+        DevBuf& leaves = ctx->mesh_leaves;
         const size_t leaf_bytes = (size_t)n_leaf_cells * sizeof(FhMeshLeaf);
-        if (assemble) {     // the records are only needed until the octree is assembled: the context's cached landing area
-            if (ctx->mesh_pinned_cap < leaf_bytes) {
-                if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
-                ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
-                MESH_TRY(hipHostMalloc(&ctx->mesh_pinned, leaf_bytes + leaf_bytes / 8, hipHostMallocDefault));
-                ctx->mesh_pinned_cap = leaf_bytes + leaf_bytes / 8;
-            }
-            M->leaves.p = (FhMeshLeaf*)ctx->mesh_pinned;
-            M->leaves.borrowed = true;
+        if (does.assemble_on_host) {     // the records are only needed until the octree is assembled: the context's cached landing area
+            MESH_CHECK(pinned_ensure(ctx, leaf_bytes));
+            M->leaves.p = (FhMeshLeaf*)ctx->mesh_pinned; M->leaves.borrowed = true;
         } else
-            MESH_TRY(hipHostMalloc((void**)&M->leaves.p, leaf_bytes, hipHostMallocDefault));
+            MESH_CHECK(hipHostMalloc((void**)&M->leaves.p, leaf_bytes, hipHostMallocDefault));
         M->leaves.n = n_leaf_cells;
-        const uint32_t CH = LEAF_CH;
         std::vector<hipEvent_t> evs;
         hipStream_t const copy_stream = ctx->stream2 ? ctx->stream2 : ctx->stream;
-        bool ok = true;
         hipError_t first_err = hipSuccess;
-        auto chk = [&](hipError_t e) { if (e != hipSuccess && ok) { ok = false; first_err = e; } };
-        for (uint32_t off = 0; off < n_leaf_cells && ok; off += CH) {
-            const uint32_t cnt = std::min<uint32_t>(CH, n_leaf_cells - off);
+        auto chk = [&](hipError_t e) { first_err = first_of(first_err, e); };
+        for (uint32_t off = 0; off < n_leaf_cells && first_err == hipSuccess; off += LEAF_CH) {
+            const uint32_t cnt = std::min<uint32_t>(LEAF_CH, n_leaf_cells - off);
             chk(sample_chunk((const FhMeshCell*)bufs[cur].p + off, (FhMeshLeaf*)leaves.p + off, cnt));
             hipEvent_t ev = nullptr;
             chk(hipEventCreateWithFlags(&ev, hipEventDisableTiming));
@@ -793,36 +764,80 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
             chk(hipStreamWaitEvent(copy_stream, ev, 0));
             chk(hipMemcpyAsync(M->leaves.p + off, (FhMeshLeaf*)leaves.p + off, (size_t)cnt * sizeof(FhMeshLeaf), hipMemcpyDeviceToHost, copy_stream));
         }
-        if (times) { chk(hipStreamSynchronize(ctx->stream)); t_leaf = now() - t_start - t_cells; }
+        if (times) { chk(hipStreamSynchronize(ctx->stream)); t_leaf = mesh_now() - t_start - t_cells; }
         chk(hipStreamSynchronize(ctx->stream));
         chk(hipStreamSynchronize(copy_stream));
         for (hipEvent_t e : evs) (void)hipEventDestroy(e);
-        MESH_TRY(first_err);
-    }
-    if (dev_asm) {
-        std::vector<fhmesh::OctLevel> lv(lv_n_amb.size());
-        for (size_t d = 0; d < lv.size(); d++) {
-            lv[d].cls = (const uint8_t*)lv_cls[d].p; lv[d].slot = (const uint32_t*)lv_slot[d].p;
-            lv[d].amb = (const FhMeshCell*)lv_amb[d].p; lv[d].n_amb = lv_n_amb[d];
-        }
-        MeshTimes MT{times, t_start, t_cells, t_leaf, 0.0, n_leaf_cells};
-        std::string why;
-        const hipError_t ae = mesh_assemble_device(ctx, M, depth, lv, (const FhMeshLeaf*)leaves.p, n_leaf_cells, (const FhMdcTable*)table.p, P.has_mat != 0, P.mat, MT, why);
-        if (ae != hipSuccess && !why.empty()) { cleanup(); delete M; return fail(ctx, FHIP_ERR_OVERFLOW, why); }
-        MESH_TRY(ae);
-        cleanup();
-        *out = M;
+        MESH_CHECK(first_err);
         return FHIP_OK;
     }
-#undef MESH_TRY
-    cleanup();
-    t_copy = now() - t_start - t_cells - t_leaf;
-    MeshTimes MT{times, t_start, t_cells, t_leaf, t_copy, n_leaf_cells};
-    if (assemble) mesh_assemble(ctx, M, depth, P.has_mat != 0, P.mat, MT);
-    else if (times)
-        fprintf(stderr, "fhip mesh depth %u (part %u of %u): cells %.4f s (%llu evaluated), leaf kernel %.4f s (%u leaves), copies %.4f s\n", depth, part, n_parts,
-                t_cells, (unsigned long long)M->cells_evaluated, t_leaf, n_leaf_cells, t_copy);
-    *out = M;
+    fhip_status sample_leaves() {
+        if (n_leaf_cells || does.assemble_on_device) {
+            build_mdc_table(mdc);
+            MESH_CHECK(table.ensure(sizeof(mdc)));
+            MESH_CHECK(hipMemcpyAsync(table.p, &mdc, sizeof(mdc), hipMemcpyHostToDevice, ctx->stream));
+        }
+        const char* const lp_env = getenv("FHIP_MESH_LEAF_PASSES");        // diagnostic: 0 = k_mesh_leaf, the kernel the passes are checked against
+        leaf_passes = !(lp_env && lp_env[0] == '0');
+        const char* const be_env = getenv("FHIP_MESH_BULK_EDGES");          // diagnostic: 0 = the edge search by k_mesh_edges (the generic interpreter)
+        bulk_edges = leaf_passes && ctx->use_asm && P.n_regs <= 32 && !(be_env && be_env[0] == '0') && !P.sub_tab;     // (one tape per launch)
+        n_slots = std::max<uint32_t>(t().n_vars, 1);
+        for (uint32_t sl = 0; sl < FH_MAX_INPUTS; sl++) if (P.in_kind[sl] < 3) n_slots = std::max(n_slots, sl + 1);
+        if (bulk_edges) {
+            const bool plain = tape_asm_ok(t());
+            bulk_per = P.n_regs <= 16 ? 256 : 128;
+            bulk_which = P.n_regs <= 16 ? (plain ? FH_ASM_FLOAT_16x4 : FH_ASM_FLOAT_16x4_T) : (plain ? FH_ASM_FLOAT_32x2 : FH_ASM_FLOAT_32x2_T);
+        }
+        if (!n_leaf_cells) return FHIP_OK;
+        MESH_CHECK(ctx->mesh_leaves.ensure((size_t)n_leaf_cells * sizeof(FhMeshLeaf)));      // (kept with the context between builds)
+        return does.keep_dev_levels ? sample_resident() : sample_to_host();
+    }
+    // ---- stage 4 (fhip_mesh_build): octree and dual walk on the device, from the levels' arrays and the records where they are
+    fhip_status assemble_device() {
+        std::vector<fhmesh::OctLevel> lv(lv_n_amb.size());
+        for (size_t d = 0; d < lv.size(); d++) { lv[d].cls = (const uint8_t*)lv_cls[d].p; lv[d].slot = (const uint32_t*)lv_slot[d].p; lv[d].amb = (const FhMeshCell*)lv_amb[d].p; lv[d].n_amb = lv_n_amb[d]; }
+        MeshTimes MT{times, t_start, t_cells, t_leaf, 0.0, n_leaf_cells};
+        std::string why;
+        const hipError_t ae = mesh_assemble_device(ctx, M.get(), depth, lv, (const FhMeshLeaf*)ctx->mesh_leaves.p, n_leaf_cells, (const FhMdcTable*)table.p, P.has_mat != 0, P.mat, MT, why);
+        if (ae != hipSuccess && !why.empty()) return fail(ctx, FHIP_ERR_OVERFLOW, why);
+        MESH_CHECK(ae);
+        return FHIP_OK;
+    }
+};
+#undef MESH_CHECK
+// The driver of fhip_mesh_sample / _build / _sample_part and fhip_shape_occupancy (MeshDoes: what each of them does)
+static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
+                            const uint64_t* var_keys, const float* var_values, uint32_t n_vars, MeshMode mode, uint32_t part, uint32_t n_parts, fhip_mesh** out,
+                            fhip_occupancy* occ = nullptr) {
+    if (!out) return FHIP_ERR_BAD_TAPE;
+    *out = nullptr;
+    if (mode == MESH_OCC && !occ) return FHIP_ERR_BAD_TAPE;
+    const MeshDoes does = mesh_does(mode, n_parts, ctx->opt.mesh_device_assembly != 0);
+    std::unique_ptr<fhip_mesh> M;
+    MeshTimes MT{};
+    bool has_mat = false;
+    float mat[16] = {};
+    {
+        MeshJob J(ctx, depth, part, n_parts, does);
+        fhip_status st = J.prepare(tape, world_to_model, axis_slots, var_keys, var_values, n_vars);
+        if (!st) st = J.descend();
+        if (!st && does.occupancy) st = J.occupancy_finish(occ);
+        if (!st && does.sample_leaves) st = J.sample_leaves();
+        if (!st && does.assemble_on_device) st = J.assemble_device();
+        if (st) return st;
+        M = std::move(J.M);
+        MT = MeshTimes{J.times, J.t_start, J.t_cells, J.t_leaf, 0.0, J.n_leaf_cells};
+        has_mat = J.P.has_mat != 0;
+        memcpy(mat, J.P.mat, sizeof(mat));
+    }   // (the job's buffers go here: their HBM is free before the host's threads assemble)
+    if (does.sample_leaves && !does.assemble_on_device) {
+        MT.t_copy = mesh_now() - MT.t_start - MT.t_cells - MT.t_leaf;
+        if (does.assemble_on_host) mesh_assemble(ctx, M.get(), depth, has_mat, mat, MT);
+        else if (MT.on)
+            fprintf(stderr, "fhip mesh depth %u (part %u of %u): cells %.4f s (%llu evaluated), leaf kernel %.4f s (%u leaves), copies %.4f s\n", depth, part, n_parts,
+                    MT.t_cells, (unsigned long long)M->cells_evaluated, MT.t_leaf, MT.n_leaf_cells, MT.t_copy);
+    }
+    *out = M.release();
     return FHIP_OK;
 }
 // Octree assembly (cell collapse included) and dual walk on the host's threads, from the classes / slots / leaf records in M
@@ -915,12 +930,7 @@ static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t dep
         if (wrc == fhmesh::WALK_OK && w.err == hipSuccess) {
             const double t_asm = now() - t0;
             const size_t vbytes = (size_t)wo.n_verts * sizeof(fhmesh::V3), tbytes = (size_t)wo.n_tris * 24, need = ((vbytes + 255) & ~(size_t)255) + tbytes + 256;
-            if (ctx->mesh_pinned_cap < need) {
-                if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
-                ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
-                if (hipHostMalloc(&ctx->mesh_pinned, need + need / 8, hipHostMallocDefault) == hipSuccess) ctx->mesh_pinned_cap = need + need / 8;
-            }
-            if (ctx->mesh_pinned_cap >= need) {
+            if (pinned_ensure(ctx, need) == hipSuccess) {
                 char* pv = (char*)ctx->mesh_pinned;
                 char* pt = pv + ((vbytes + 255) & ~(size_t)255);
                 if (vbytes) w.chk(hipMemcpyAsync(pv, wo.verts, vbytes, hipMemcpyDeviceToHost, ctx->stream));
@@ -954,14 +964,7 @@ static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t dep
         w.release();        // (the host's walk takes over: too big an octree for the passes' 32-bit numbers, or no memory for them)
     }
     const size_t cell_bytes = (size_t)oo.n_blocks * 8 * sizeof(fhmesh::Cell);
-    if (ctx->mesh_pinned_cap < cell_bytes + 256) {
-        if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
-        ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
-        const size_t room = cell_bytes + cell_bytes / 8 + 256;
-        const hipError_t e = hipHostMalloc(&ctx->mesh_pinned, room, hipHostMallocDefault);
-        if (e != hipSuccess) return give_up(e);
-        ctx->mesh_pinned_cap = room;
-    }
+    { const hipError_t e = pinned_ensure(ctx, cell_bytes + 256); if (e != hipSuccess) return give_up(e); }
     fhmesh::Octree o;
     o.root = oo.root;
     o.cells_view = (const std::array<fhmesh::Cell, 8>*)ctx->mesh_pinned; o.n_cells_view = oo.n_blocks;
@@ -1230,12 +1233,7 @@ uint64_t fhip_mesh_stl_bytes(const fhip_mesh* m) { return fhm::FH_STL_HEADER + (
 // `bytes` from device memory to a host buffer of the caller's through the context's pinned landing area, as a built mesh travels
 static fhip_status mesh_to_host(fhip_ctx* ctx, void* dst, const void* d_src, size_t bytes) {
     if (!bytes) return FHIP_OK;
-    if (ctx->mesh_pinned_cap < bytes) {
-        if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
-        ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
-        HIP_TRY(ctx, hipHostMalloc(&ctx->mesh_pinned, bytes + bytes / 8, hipHostMallocDefault));
-        ctx->mesh_pinned_cap = bytes + bytes / 8;
-    }
+    HIP_TRY(ctx, pinned_ensure(ctx, bytes));
     HIP_TRY(ctx, hipMemcpyAsync(ctx->mesh_pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
     HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
     const size_t CH = (size_t)4 << 20;

@@ -436,6 +436,8 @@ def test_device_assembly_equals_the_host_assembly(model, depth):
     with shape.hip.options(mesh_device_assembly=0):
         t2, v2, c2 = F.mesh(shape, depth)
     assert counts == c2 and len(tris) > 10000
+    if (model, depth) == ("gyroid-sphere.vm", 8):
+        assert counts["leaf_cells"] > (1 << 19)       # several chunks of leaf cells: the host assembly's copies chunk by chunk on the second stream
     assert tris.shape == t2.shape and (tris == t2).all()
     assert verts.shape == v2.shape and (verts.view(np.uint32) == v2.view(np.uint32)).all()
 

@@ -28,6 +28,7 @@ def test_hash_covers_the_render_path_only(tmp_path):
     assert edited("mesh_collapse.hpp", b"OctRes", b"OctRez") == base
     assert edited("host_mesh.hpp", b"ParallelWalker", b"ParallelWalkez") == base
     assert edited("capi_mesh.hpp", b"static hipError_t mesh_assemble_device", b"static hipError_t mesh_assemble_devicf") == base
+    assert edited("mesh_split.hpp", b"split_levels", b"split_levelz") == base
     # the render path: kernels, generators, the frame driver in capi.hip, shared headers
     assert edited("kernels.hip", b"k_classify3d", b"k_classify3e") != base
     assert edited("gen_interp.py", b"fh_columns", b"fh_columnz") != base
