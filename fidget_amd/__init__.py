@@ -25,7 +25,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -52,7 +52,7 @@ EXPORTS = [
     "fhip_ctx_create", "fhip_ctx_destroy", "fhip_ctx_trim", "fhip_ctx_reserve_arena", "fhip_libm_probe", "fhip_last_error", "fhip_ctx_sync", "fhip_cancel", "fhip_cancel_reset", "fhip_cancel_watch", "fhip_ctx_set_option", "fhip_ctx_get_option",
     "fhip_tape_from_bytecode", "fhip_tape_free", "fhip_tape_len", "fhip_tape_reg_tape", "fhip_tape_choice_count", "fhip_tape_reg_count",
     "fhip_tape_var_count", "fhip_tape_output_count", "fhip_tape_ops", "fhip_simplify", "fhip_interval_eval",
-    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads", "fhip_shape_occupancy",
+    "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads", "fhip_shape_occupancy", "fhip_voxels_words", "fhip_shape_voxels", "fhip_voxels_slices", "fhip_voxels_layer_counts",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -179,6 +179,8 @@ def lib():
             "fhip_mesh_stl_bytes": (u64, [vp]), "fhip_mesh_stl": (i32, [vp, vp, vp, i32]),
             "fhip_mesh_vertex_grads": (i32, [vp, vp, vp, vp, vp, vp, u32, vp, i32]),
             "fhip_shape_occupancy": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp]),
+            "fhip_voxels_words": (u64, [u32]), "fhip_shape_voxels": (i32, [vp, vp, u32, vp, vp, vp, vp, u32, vp, i32, vp]),
+            "fhip_voxels_slices": (i32, [vp, vp, u32, u32, u32, vp, i32]), "fhip_voxels_layer_counts": (i32, [vp, vp, u32, vp, i32]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1310,6 +1312,112 @@ def occupancy(shape, depth, world_to_model=None, vars=None):
         raise ValueError("MissingVar")
     hip.check(st)
     return Occupancy(raw)
+
+
+# ---- shape voxels: the inside voxels as a packed bitmap, layer images, voxels per layer (fhip_shape_voxels) ---------------
+def voxels_unpack(bricks):
+    """bricks uint64 [B, B, B] (indexed [bz, by, bx]; bit lx + 4 ly + 16 lz of a word: voxel (4 bx + lx, 4 by + ly, 4 bz + lz)) ->
+    bool [N, N, N], N = 4 B, indexed [i, j, k]"""
+    b = np.ascontiguousarray(bricks, "<u8")
+    B = b.shape[0]
+    bits = np.unpackbits(b.view(np.uint8).reshape(B, B, B, 8), axis=-1, bitorder="little")       # [bz, by, bx, 16 lz + 4 ly + lx]
+    return bits.reshape(B, B, B, 4, 4, 4).transpose(2, 5, 1, 4, 0, 3).reshape(4 * B, 4 * B, 4 * B).astype(bool)
+
+
+class Voxels:
+    """The bitmap of `voxelize`: `.bricks` [B, B, B] (numpy uint64, or a view of the caller's torch CUDA tensor as int64), `.depth`,
+    `.grid` = N = 4 B, `.cells` = {"cells", "full", "empty", "leaf_cells"} as Occupancy's, `.n` = the number of inside voxels.  What is
+    made of it runs where the bricks are: on the host's arrays through the library's staging buffers, or on the device in place and
+    asynchronous on the context's stream."""
+
+    def __init__(self, hip, bricks, depth, cells):
+        self._hip, self.bricks, self.depth, self.grid, self.cells = hip, bricks, int(depth), 4 << int(depth), cells
+        self._n = None
+
+    @property
+    def on_device(self):
+        return not isinstance(self.bricks, np.ndarray)
+
+    def _ptr(self):
+        return _dev_ptr(self.bricks) if self.on_device else _p(self.bricks)
+
+    def slices(self, k0, k1, out=None):
+        """fhip_voxels_slices: uint8 [k1 - k0, N, N], [k - k0, j, i] = 255 where voxel (i, j, k) is inside, 0 where not: numpy for bricks
+        on the host; for bricks on the device a torch CUDA tensor (`out`, contiguous uint8 of that size, or a new one)"""
+        N = self.grid
+        k0, k1 = int(k0), int(k1)
+        n = max(k1 - k0, 0) * N * N
+        if self.on_device:
+            if out is None:
+                import torch
+                out = torch.empty((max(k1 - k0, 0), N, N), dtype=torch.uint8, device=self.bricks.device)
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 1 and out.numel() >= n
+            self._hip.check(lib().fhip_voxels_slices(self._hip._h, self._ptr(), self.depth, k0, k1, _dev_ptr(out), 1))
+            return out
+        assert out is None, "bricks on the host: the images are returned as a numpy array"
+        img = np.zeros((max(k1 - k0, 0), N, N), np.uint8)
+        self._hip.check(lib().fhip_voxels_slices(self._hip._h, self._ptr(), self.depth, k0, k1, _p(img), 0))
+        return img
+
+    def layer_counts(self):
+        """fhip_voxels_layer_counts: [N] inside voxels per third index k: numpy uint64, or a torch CUDA int64 tensor for bricks on the device"""
+        if self.on_device:
+            import torch
+            out = torch.empty(self.grid, dtype=torch.int64, device=self.bricks.device)
+            self._hip.check(lib().fhip_voxels_layer_counts(self._hip._h, self._ptr(), self.depth, _dev_ptr(out), 1))
+            return out
+        out = np.zeros(self.grid, np.uint64)
+        self._hip.check(lib().fhip_voxels_layer_counts(self._hip._h, self._ptr(), self.depth, _p(out), 0))
+        return out
+
+    @property
+    def n(self):
+        """the number of set bits (Occupancy.n at the same depth)"""
+        if self._n is None:
+            self._n = int(self.layer_counts().sum())
+        return self._n
+
+    def inside(self):
+        """bool [N, N, N] indexed [i, j, k], unpacked on the host (bricks on the device are copied there first)"""
+        b = self.bricks.cpu().numpy().view(np.uint64) if self.on_device else self.bricks
+        return voxels_unpack(b)
+
+    def __repr__(self):
+        return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
+
+
+def voxelize(shape, depth, world_to_model=None, vars=None, out=None):
+    """fhip_shape_voxels: the solid `shape < 0` on the grid of 4 << depth voxels per axis over [-1, 1]^3 (world_to_model as for `mesh`)
+    as a bitmap of 4 x 4 x 4 bricks, written down the octree `occupancy` counts -> Voxels.  `out`: a contiguous torch CUDA tensor of at
+    least 8 B^3 bytes, B = 1 << depth (int64 is the natural dtype) - the bitmap stays on the device, `.bricks` views it - or a contiguous
+    numpy array of that size, filled in place; without it a new numpy uint64 [B, B, B].  Either is written completely."""
+    hip = shape.hip
+    depth = int(depth)
+    w2m = None if world_to_model is None else np.ascontiguousarray(world_to_model, np.float32)
+    vk, vv = _var_arrays(shape, vars)
+    ax = None
+    if shape._vars is not None:
+        ax = np.array(shape._vars, dtype=np.int32)
+        vk = np.array([shape._named_slot(k) for k in (vars or {})], dtype=np.uint64)
+    B = 1 << depth
+    words = int(lib().fhip_voxels_words(depth))       # (0 beyond depth 10: the call below refuses before it touches `out`)
+    cells = np.zeros(4, np.uint64)
+    if out is not None and not isinstance(out, np.ndarray):
+        import torch
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
+        ptr, dev = _dev_ptr(out), 1
+        bricks = (lambda: out.reshape(-1).view(torch.int64)[:words].view(B, B, B))
+    else:
+        if out is None:
+            out = np.zeros((B, B, B) if words else 0, np.uint64)
+        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
+        ptr, dev = _p(out), 0
+        bricks = (lambda: out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B))
+    st = lib().fhip_shape_voxels(hip._h, shape._h, depth, _p(w2m), _p(ax), _p(vk), _p(vv), len(vk), ptr, dev, _p(cells))
+    if st == 4:
+        raise ValueError("MissingVar")
+    hip.check(st)
+    return Voxels(hip, bricks(), depth, dict(zip(("cells", "full", "empty", "leaf_cells"), (int(v) for v in cells))))
 
 
 # ---- constraint solver (fidget::solver, fidget-solver/src/lib.rs) ---------------------------------------------------------

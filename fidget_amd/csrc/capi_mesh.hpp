@@ -400,7 +400,7 @@ static const fhmesh::WalkTable& walk_table() {       // CELL_TO_EDGE_TO_VERT out
 }
 static hipError_t mesh_assemble_device(fhip_ctx* ctx, fhip_mesh* M, uint32_t depth, std::vector<fhmesh::OctLevel>& lv, const FhMeshLeaf* rec, uint32_t n_rec, const FhMdcTable* table,
                                        bool has_mat, const float* mat, MeshTimes& T, std::string& why);
-enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART, MESH_OCC };
+enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART, MESH_OCC, MESH_VOX };
 // What a call of mesh_run does, by entry point.  Every mode makes the launches it made before the others existed, in the same order.
 //                                                  the levels' classes, slots   leaf records                             then
 //   fhip_mesh_sample        MESH_SAMPLE            -                            sampled, copied into the mesh            -
@@ -408,16 +408,18 @@ enum MeshMode { MESH_SAMPLE, MESH_BUILD, MESH_PART, MESH_OCC };
 //   fhip_mesh_build         MESH_BUILD             stay in HBM (+ the cells)    sampled, stay in HBM                     octree and dual walk on the device
 //     option mesh_device_assembly 0                copied to the host           sampled, to the context's landing area   both on the host's threads, as fhip_mesh_merge
 //   fhip_shape_occupancy    MESH_OCC               on the device, per level     none                                     k_occ_full per level with Full cells, k_occ_leaves at the end
-struct MeshDoes { bool keep_host_levels, keep_dev_levels, need_classes, sample_leaves, assemble_on_device, assemble_on_host, occupancy; };
+//   fhip_shape_voxels       MESH_VOX               on the device, per level     none                                     the bitmap cleared before level 0, k_vox_full per level with Full cells, k_vox_leaves at the end
+struct MeshDoes { bool keep_host_levels, keep_dev_levels, need_classes, sample_leaves, assemble_on_device, assemble_on_host, occupancy, voxels; };
 static MeshDoes mesh_does(MeshMode mode, uint32_t n_parts, bool device_assembly) {
     MeshDoes D;
     D.occupancy = mode == MESH_OCC;
+    D.voxels = mode == MESH_VOX;
     D.assemble_on_device = mode == MESH_BUILD && n_parts == 1 && device_assembly;
     D.assemble_on_host = mode == MESH_BUILD && !D.assemble_on_device;
     D.keep_dev_levels = D.assemble_on_device;
     D.keep_host_levels = (mode == MESH_BUILD || mode == MESH_PART) && !D.assemble_on_device;       // for the host's assembly alone
-    D.need_classes = D.keep_host_levels || D.occupancy;     // (occupancy reads the classes alone, on the device; k_mesh_cells writes slots wherever it writes classes: both arrays)
-    D.sample_leaves = !D.occupancy;
+    D.need_classes = D.keep_host_levels || D.occupancy || D.voxels;     // (occupancy and voxels read the classes alone, on the device; k_mesh_cells writes slots wherever it writes classes: both arrays)
+    D.sample_leaves = !D.occupancy && !D.voxels;
     return D;
 }
 static double mesh_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
@@ -444,6 +446,7 @@ struct MeshJob {
     std::vector<ScratchBuf> lv_cls, lv_slot, lv_amb;        // keep_dev_levels: every level's classes, slots and ambiguous cells stay
     std::vector<uint32_t> lv_n_amb;
     uint32_t occ_used = 0;       // partial records written so far: every launch of the two occupancy kernels its own span, one record per block
+    uint64_t* vox_out = nullptr;   // voxels: the bitmap on the device, fhvox::n_words(depth) words
     fhsplit::SplitLevels split{0, 0};
     std::vector<fh::HostTape> sub_keep;           // the first split's tapes (kept for the second)
     std::vector<int32_t> sub_of;                  // first-split table index -> index into sub_keep, -1: the root tape
@@ -459,6 +462,7 @@ struct MeshJob {
     // ---- stage 1: the arguments, the tape on the device, the kernels' parameters
     fhip_status prepare(const fhip_tape* tape_, const float* world_to_model, const int32_t* axis_slots, const uint64_t* var_keys, const float* var_values, uint32_t n_vars) {
         if (does.occupancy && depth > 10) return fail(ctx, FHIP_ERR_UNSUPPORTED, "occupancy depth above 10: the second moments of a grid of more than 4096^3 voxels overflow 64 bits");
+        if (does.voxels && depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10: the bitmap of a grid of more than 4096^3 voxels exceeds 8 GiB");
         if (depth > 20) return fail(ctx, FHIP_ERR_UNSUPPORTED, "octree depth above 20");
         if (n_parts < 1 || n_parts > 8 || part >= n_parts) return fail(ctx, FHIP_ERR_UNSUPPORTED, "mesh parts: 1..8, part < n_parts");
         tape = tape_;
@@ -490,7 +494,7 @@ struct MeshJob {
             const int d = ctx->device & 63;
             if (!attr_done[d]) {
                 const void* const all_lds[] = {(const void*)fhm::k_mesh_cells, (const void*)fhm::k_mesh_choices, (const void*)fhm::k_mesh_corners, (const void*)fhm::k_mesh_edges,
-                                               (const void*)fhm::k_mesh_grads, (const void*)fhm::k_occ_leaves};
+                                               (const void*)fhm::k_mesh_grads, (const void*)fhm::k_occ_leaves, (const void*)fhm::k_vox_leaves};
                 for (const void* k : all_lds) (void)hipFuncSetAttribute(k, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX);
                 (void)hipFuncSetAttribute((const void*)fhm::k_mesh_leaf, hipFuncAttributeMaxDynamicSharedMemorySize, FH_LDS_MAX - 2048);
                 attr_done[d] = true;
@@ -506,6 +510,7 @@ struct MeshJob {
         if (does.keep_dev_levels) { lv_cls.resize(depth + 1); lv_slot.resize(depth + 1); lv_amb.resize(depth + 1); }
         MESH_CHECK(counters.ensure(16));
         if (does.occupancy) MESH_CHECK(occ_parts.ensure(((size_t)(depth + 1) * FH_OCC_FULL_BLOCKS + FH_OCC_LEAF_BLOCKS) * sizeof(FhOccPart)));
+        if (does.voxels) MESH_CHECK(hipMemsetAsync(vox_out, 0, (size_t)fhvox::n_words(depth) * 8, ctx->stream));       // the one clearing pass: Empty cells and zero ballots are never written
         FhMeshCell root;
         for (int k = 0; k < 3; k++) { root.b[2 * k] = -1.0f; root.b[2 * k + 1] = 1.0f; }     // CellBounds::new (cell.rs:171-176)
         root.path = 1;
@@ -545,6 +550,14 @@ struct MeshJob {
                                    (FhOccPart*)occ_parts.p + occ_used);
                 MESH_CHECK(hipGetLastError());
                 occ_used += nb;
+            }
+            if (does.voxels && c[1]) {         // ... or their boxes of all-ones words
+                const fhvox::FullSlots S = fhvox::full_slots(depth, d, ((uintptr_t)vox_out & 15u) == 0);
+                const uint64_t slots = (uint64_t)n << S.lg_per_cell;
+                const uint32_t nb = (uint32_t)std::min<uint64_t>((slots + 255) / 256, fhm::FH_VOX_FULL_BLOCKS);
+                hipLaunchKernelGGL(fhm::k_vox_full, dim3(nb), dim3(256), 0, ctx->stream, (const FhMeshCell*)in_cells, (const uint8_t*)cls_p, n, d == 0 ? 0 : 1, d, depth,
+                                   (((uintptr_t)vox_out & 15u) == 0) ? 1 : 0, vox_out);
+                MESH_CHECK(hipGetLastError());
             }
             cur ^= 1; n_in = c[0]; lv_n_amb.push_back(c[0]);
             if (d == depth) n_leaf_cells = c[0];
@@ -648,6 +661,19 @@ struct MeshJob {
         occ->cells[0] = M->cells_evaluated; occ->cells[1] = M->full; occ->cells[2] = M->empty; occ->cells[3] = M->ambiguous_leaves;
         if (times) fprintf(stderr, "fhip occupancy depth %u: %.4f s (%llu cells evaluated, %u leaf cells, %u partial records)\n", depth, mesh_now() - t_start,
                            (unsigned long long)M->cells_evaluated, n_leaf_cells, occ_used);
+        return FHIP_OK;
+    }
+    // ---- stage 3 (voxels): the ambiguous cells of the last level, one ballot each; the bitmap is complete when the stream is idle
+    fhip_status voxels_finish(uint64_t cells[4]) {
+        if (n_leaf_cells) {
+            const uint32_t nb = std::min<uint32_t>(n_leaf_cells, FH_OCC_LEAF_BLOCKS);
+            hipLaunchKernelGGL(fhm::k_vox_leaves, dim3(nb), dim3(WAVE), lds_f32, ctx->stream, P, (const FhMeshCell*)bufs[cur].p, n_leaf_cells, depth, vox_out);
+            MESH_CHECK(hipGetLastError());
+        }
+        MESH_CHECK(hipStreamSynchronize(ctx->stream));
+        if (cells) { cells[0] = M->cells_evaluated; cells[1] = M->full; cells[2] = M->empty; cells[3] = M->ambiguous_leaves; }
+        if (times) fprintf(stderr, "fhip voxels depth %u: %.4f s (%llu cells evaluated, %llu Full, %u leaf cells)\n", depth, mesh_now() - t_start,
+                           (unsigned long long)M->cells_evaluated, (unsigned long long)M->full, n_leaf_cells);
         return FHIP_OK;
     }
     // ---- stage 3 (meshes): the leaf cells sampled into records, LEAF_CH cells at a time
@@ -805,13 +831,15 @@ struct MeshJob {
     }
 };
 #undef MESH_CHECK
-// The driver of fhip_mesh_sample / _build / _sample_part and fhip_shape_occupancy (MeshDoes: what each of them does)
+struct VoxTarget { uint64_t* d_out; uint64_t* cells; };       // MESH_VOX: the bitmap on the device, the four counters (or null)
+// The driver of fhip_mesh_sample / _build / _sample_part, fhip_shape_occupancy and fhip_shape_voxels (MeshDoes: what each of them does)
 static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
                             const uint64_t* var_keys, const float* var_values, uint32_t n_vars, MeshMode mode, uint32_t part, uint32_t n_parts, fhip_mesh** out,
-                            fhip_occupancy* occ = nullptr) {
+                            fhip_occupancy* occ = nullptr, const VoxTarget* vox = nullptr) {
     if (!out) return FHIP_ERR_BAD_TAPE;
     *out = nullptr;
     if (mode == MESH_OCC && !occ) return FHIP_ERR_BAD_TAPE;
+    if (mode == MESH_VOX && !(vox && vox->d_out)) return FHIP_ERR_BAD_TAPE;
     const MeshDoes does = mesh_does(mode, n_parts, ctx->opt.mesh_device_assembly != 0);
     std::unique_ptr<fhip_mesh> M;
     MeshTimes MT{};
@@ -819,9 +847,11 @@ static fhip_status mesh_run(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth
     float mat[16] = {};
     {
         MeshJob J(ctx, depth, part, n_parts, does);
+        if (does.voxels) J.vox_out = vox->d_out;
         fhip_status st = J.prepare(tape, world_to_model, axis_slots, var_keys, var_values, n_vars);
         if (!st) st = J.descend();
         if (!st && does.occupancy) st = J.occupancy_finish(occ);
+        if (!st && does.voxels) st = J.voxels_finish(vox->cells);
         if (!st && does.sample_leaves) st = J.sample_leaves();
         if (!st && does.assemble_on_device) st = J.assemble_device();
         if (st) return st;
@@ -1351,4 +1381,74 @@ fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const f
     }
     HIP_TRY(ctx, hipGetLastError());
     return out_is_device ? FHIP_OK : mesh_to_host(ctx, out, d_out, (size_t)n * 16);
+}
+
+// ---- the voxel bitmap ---------------------------------------------------------------------------------------------------------------------
+// The voxel bitmap (fidget_hip.h): occupancy's level loop with the bitmap kernels of mesh.hip; a host `out` is filled from the context's
+// buffer through the pinned landing area
+uint64_t fhip_voxels_words(uint32_t depth) { return fhvox::n_words(depth); }
+fhip_status fhip_shape_voxels(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
+                              const uint64_t* var_keys, const float* var_values, uint32_t n_vars, uint64_t* out, int out_is_device, uint64_t cells[4]) {
+    if (!ctx || !tape || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_shape_voxels: context, tape and output buffer");
+    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10: the bitmap of a grid of more than 4096^3 voxels exceeds 8 GiB");
+    const size_t bytes = (size_t)fhvox::n_words(depth) * 8;
+    VoxTarget vt{out, cells};
+    if (out_is_device) {
+        if ((uintptr_t)out & 7u) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxels to the device: the buffer must be 8-byte aligned");
+    } else {
+        (void)hipSetDevice(ctx->device);
+        HIP_TRY(ctx, ctx->io_d.ensure(bytes));
+        vt.d_out = (uint64_t*)ctx->io_d.p;
+    }
+    fhip_mesh* m = nullptr;
+    const fhip_status st = mesh_run(ctx, tape, depth, world_to_model, axis_slots, var_keys, var_values, n_vars, MESH_VOX, 0, 1, &m, nullptr, &vt);
+    delete m;
+    if (st || out_is_device) return st;
+    return mesh_to_host(ctx, out, vt.d_out, bytes);
+}
+// What is made of a bitmap (k_vox_slices, k_vox_layer_counts): the effects' convention - device pointers and asynchronous, or host buffers
+static fhip_status voxels_in(fhip_ctx* ctx, FxStage& st, const uint64_t* bricks, uint32_t depth, const uint64_t*& d_bricks) {
+    if (st.on_device && ((uintptr_t)bricks & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap on the device must be 8-byte aligned");
+    hipError_t e = hipSuccess;
+    d_bricks = (const uint64_t*)st.in(ctx->io_a, bricks, (size_t)fhvox::n_words(depth) * 8, e);
+    HIP_TRY(ctx, e);
+    return FHIP_OK;
+}
+fhip_status fhip_voxels_slices(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint32_t k0, uint32_t k1, uint8_t* out, int on_device) {
+    if (!ctx) return FHIP_ERR_BAD_TAPE;
+    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
+    const uint32_t N = 4u << depth;
+    if (k0 > k1 || k1 > N) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel slices: layers k0 <= k1 <= 4 << depth");
+    if (k0 == k1) return FHIP_OK;
+    if (!bricks || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_slices: bitmap and output buffer");
+    if (on_device && ((uintptr_t)out & 15u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel slices to the device: the buffer must be 16-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    FxStage st{ctx, on_device, {}};
+    const uint64_t* d_bricks = nullptr;
+    { const fhip_status s = voxels_in(ctx, st, bricks, depth, d_bricks); if (s) return s; }
+    hipError_t e = hipSuccess;
+    uint8_t* const d_out = (uint8_t*)st.out(ctx->io_b, out, (size_t)(k1 - k0) * N * N, e); HIP_TRY(ctx, e);
+    const uint64_t runs = ((uint64_t)(k1 - k0) * N) << (depth < 2 ? 0 : depth - 2);
+    const uint32_t nb = (uint32_t)std::min<uint64_t>((runs + 255) / 256, fhm::FH_VOX_SLICE_BLOCKS);
+    hipLaunchKernelGGL(fhm::k_vox_slices, dim3(nb), dim3(256), 0, ctx->stream, d_bricks, depth, k0, k1, d_out);
+    return st.finish();
+}
+fhip_status fhip_voxels_layer_counts(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint64_t* out, int on_device) {
+    if (!ctx) return FHIP_ERR_BAD_TAPE;
+    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
+    if (!bricks || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_layer_counts: bitmap and output buffer");
+    if (on_device && ((uintptr_t)out & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "layer counts to the device: the buffer must be 8-byte aligned");
+    (void)hipSetDevice(ctx->device);
+    FxStage st{ctx, on_device, {}};
+    const uint64_t* d_bricks = nullptr;
+    { const fhip_status s = voxels_in(ctx, st, bricks, depth, d_bricks); if (s) return s; }
+    const uint32_t B = 1u << depth, N = 4u << depth;
+    const uint32_t n_parts = (uint32_t)std::min<uint64_t>((((uint64_t)B * B) + 255) / 256, fhm::FH_VOX_COUNT_PARTS);
+    hipError_t e = hipSuccess;
+    uint64_t* const d_out = (uint64_t*)st.out(ctx->io_b, out, (size_t)N * 8, e); HIP_TRY(ctx, e);
+    HIP_TRY(ctx, ctx->io_c.ensure((size_t)B * n_parts * 4 * 8));
+    hipLaunchKernelGGL(fhm::k_vox_layer_counts, dim3(n_parts, B), dim3(256), 0, ctx->stream, d_bricks, depth, (uint64_t*)ctx->io_c.p);
+    HIP_TRY(ctx, hipGetLastError());
+    hipLaunchKernelGGL(fhm::k_vox_layer_sum, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)ctx->io_c.p, n_parts, N, d_out);
+    return st.finish();
 }

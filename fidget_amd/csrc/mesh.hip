@@ -21,6 +21,8 @@
 //                 mesh's vertices numbered by first use through atomic minima and prefix sums (mesh_walk.hpp).
 //   k_mesh_stl    Mesh::write_stl (fidget-mesh/src/output.rs:14-36): the binary STL file of a mesh, 256 triangles per block, the records
 //                 put together in LDS and stored as whole dwords;
+//   k_vox_full / k_vox_leaves / k_vox_slices / k_vox_layer_counts   the inside voxels themselves (fhip_shape_voxels): the octree of occupancy
+//                 written down as a bitmap of 4 x 4 x 4 bricks, and what is made of the bitmap - layer images, voxels per layer;
 //   k_mesh_vertex_grads   the tape's value and gradient at every vertex of a mesh (VmGradSliceEval::eval, vm/mod.rs:1091-1397): one
 //                 vertex per lane, read from the V3 array where the dual walk left it.
 #pragma once
@@ -31,6 +33,7 @@
 #include "mesh_walk.hpp"
 #include "mesh_edges.hpp"
 #include "mesh_qef.hpp"
+#include "mesh_vox.hpp"
 // (included by capi.hip after kernels.hip: Regs, step, ballot, uni, ctape_t)
 
 struct FhMeshParams {
@@ -691,13 +694,8 @@ FH_DEV void occ_zero(FhOccPart& a) {
     for (int k = 0; k < 6; k++) a.s2[k] = 0;
 }
 // the origin (in cells of its level) of the cell with this path: 3 bits per level below a leading 1, bit 0 x, 1 y, 2 z, the last level lowest
-FH_DEV void occ_origin(uint64_t path, uint32_t level, uint32_t o[3]) {
-    o[0] = o[1] = o[2] = 0;
-    for (uint32_t l = 0; l < level; l++) {
-        const uint32_t b = (uint32_t)(path >> (3 * l)) & 7u;
-        o[0] |= (b & 1u) << l; o[1] |= ((b >> 1) & 1u) << l; o[2] |= ((b >> 2) & 1u) << l;
-    }
-}
+// (mesh_vox.hpp: the voxel bitmap's index arithmetic starts from the same origin, on the device and in its host build)
+FH_DEV void occ_origin(uint64_t path, uint32_t level, uint32_t o[3]) { fhvox::cell_origin(path, level, o); }
 // all the voxels of the box [X, X + w) x [Y, Y + w) x [Z, Z + w): with S1(X) = sum of a over [X, X + w) = w X + w (w - 1) / 2 and
 // S2(X) = sum of a^2 = w X^2 + X w (w - 1) + (w - 1) w (2 w - 1) / 6:  n = w^3, sum i = w^2 S1(X), sum i^2 = w^2 S2(X), sum ij = w S1(X) S1(Y).
 // (N <= 4096: the largest, sum i^2 of the whole grid, is below N^5 = 2^60)
@@ -810,5 +808,117 @@ __global__ void __launch_bounds__(WAVE) k_occ_leaves(FhMeshParams P, const FhMes
         a.n += cnt;
     }
     if (lane == 0) out[blockIdx.x] = a;
+}
+
+// ---- the voxel bitmap: occupancy's inside voxels written down, one 64-bit word per brick of 4 x 4 x 4 (layout: mesh_vox.hpp) ----------
+// The same octree with the same leaf: a Full cell becomes a box of all-ones words (k_vox_full), an Empty one stays as the one clearing pass
+// before level 0 left it, an ambiguous cell of the last level stores the ballot k_occ_leaves counts (k_vox_leaves).  Cells of one octree are
+// disjoint, so every word has one writer after the clearing pass: plain stores, no atomics, the same bitmap in any order.
+constexpr uint32_t FH_VOX_FULL_BLOCKS = 4096, FH_VOX_SLICE_BLOCKS = 1u << 16, FH_VOX_COUNT_PARTS = 64;
+
+// The Full cells of one level (cls / in / expand as for k_occ_full).  A lane takes one slot of fhvox::full_slots at a time - 16 bytes (8 for
+// single-word rows and a bitmap off 16-byte alignment) at the same place of up to 8 rows of one cell - and the blocks stride over the
+// n << lg_per_cell slots of ALL the level's cells; the slots of a cell that is not Full cost its class byte, which the lanes around share.
+// Neighbouring lanes hold neighbouring pieces of a row: rows of 32 words and more are stored as whole 256-byte lines per 16 lanes, shorter
+// ones (r = 2: 16 bytes per row) as the pieces the layout leaves.  Nothing is read but classes and paths and nothing computed but
+// addresses: what bounds the kernel is the store path to HBM (a plain streaming store pass, as the clearing memset is), for short rows
+// the partial lines it writes.
+__global__ void __launch_bounds__(256) k_vox_full(const FhMeshCell* in, const uint8_t* cls, uint32_t n, int expand, uint32_t level, uint32_t depth, int aligned16, uint64_t* out) {
+    const fhvox::FullSlots S = fhvox::full_slots(depth, level, aligned16 != 0);
+    const uint64_t total = (uint64_t)n << S.lg_per_cell;
+    for (uint64_t s = (uint64_t)blockIdx.x * 256 + threadIdx.x; s < total; s += (uint64_t)gridDim.x * 256) {
+        const uint32_t i = (uint32_t)(s >> S.lg_per_cell), k = (uint32_t)s & ((1u << S.lg_per_cell) - 1);
+        if (cls[i] != 2) continue;
+        const uint64_t path = expand ? ((in[i >> 3].path << 3) | (i & 7)) : in[i].path;
+        uint32_t o[3];
+        occ_origin(path, level, o);
+        const uint32_t sh = depth - level;
+        const uint64_t cell = fhvox::word_index(depth, o[0] << sh, o[1] << sh, o[2] << sh);
+        for (uint32_t q = 0; q < S.rows; q++) {
+            uint64_t* const w = out + fhvox::slot_word(S, depth, cell, k, q);
+            if (S.vec == 2) *(ulonglong2*)w = make_ulonglong2(~0ull, ~0ull);       // (16-byte aligned: `out` is, the row starts at a multiple of r >= 2 words, the piece at an even word)
+            else *w = ~0ull;
+        }
+    }
+}
+
+// k_occ_leaves' loop with the sums replaced by the store of the ballot: bit lane = lx + 4 ly + 16 lz of the cell's word is its voxel
+// (lx, ly, lz), which is the bitmap's bit numbering.  One ordinary 8-byte vector store from lane 0; a zero ballot is what the clearing
+// pass left.
+__global__ void __launch_bounds__(WAVE) k_vox_leaves(FhMeshParams P, const FhMeshCell* cells, uint32_t n, uint32_t depth, uint64_t* out) {
+    extern __shared__ __attribute__((aligned(16))) char smem[];
+    const int lane = threadIdx.x;
+    const uint32_t lx = lane & 3, ly = (lane >> 2) & 3, lz = lane >> 4;
+    const int32_t N = (int32_t)(4u << depth);
+    const float inv = 1.0f / (float)N;
+    Regs<float, WAVE> R{(float*)smem, lane};
+    for (uint32_t ci = blockIdx.x; ci < n; ci += gridDim.x) {
+        const uint64_t pv = cells[ci].path;
+        const uint64_t path = ((uint64_t)uni((uint32_t)(pv >> 32)) << 32) | (uint64_t)uni((uint32_t)pv);      // (wave-uniform, and known to be)
+        uint32_t o[3];
+        occ_origin(path, depth, o);
+        const uint32_t X = 4 * o[0], Y = 4 * o[1], Z = 4 * o[2];
+        const float x = (float)(2 * (int32_t)(X + lx) + 1 - N) * inv, y = (float)(2 * (int32_t)(Y + ly) + 1 - N) * inv, z = (float)(2 * (int32_t)(Z + lz) + 1 - N) * inv;
+        const float v = eval_point(P, R, x, y, z, path);
+        const uint64_t m = ballot(v < 0.0f);       // (NaN: not inside)
+        if (m != 0 && lane == 0) out[fhvox::word_index(depth, o[0], o[1], o[2])] = m;
+    }
+}
+
+// Layer images out of the bitmap: out[(k - k0) * N * N + j * N + i] = 255 where voxel (i, j, k) is inside, 0 where not, for k0 <= k < k1.
+// A lane takes a run of `nb` bricks (4; all B of a row where B < 4) of one (k, j): per brick one 8-byte load - the same word serves the
+// 16 (ly, lz) of its bricks' rows, from cache after the first - the nibble at 4 ly + 16 lz spread into four bytes, and the run stored as
+// one 16-byte vector (`out` 16-byte aligned, N >= 16) or dword by dword.  Bounded grid; a block strides over the runs.
+__global__ void __launch_bounds__(256) k_vox_slices(const uint64_t* __restrict__ bricks, uint32_t depth, uint32_t k0, uint32_t k1, uint8_t* __restrict__ out) {
+    const uint32_t B = 1u << depth, N = 4u << depth;
+    const uint32_t nb = B < 4 ? B : 4, lg_runs = depth < 2 ? 0 : depth - 2;       // runs per row: B / nb
+    const uint64_t total = ((uint64_t)(k1 - k0) * N) << lg_runs;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256) {
+        const uint32_t g = (uint32_t)t & ((1u << lg_runs) - 1);
+        const uint64_t row = t >> lg_runs;                 // (k - k0) * N + j
+        const uint32_t j = (uint32_t)(row & (N - 1)), k = k0 + (uint32_t)(row >> (depth + 2));
+        const uint32_t shift = 4 * (j & 3) + 16 * (k & 3);
+        const uint64_t* const src = bricks + fhvox::word_index(depth, g * nb, j >> 2, k >> 2);
+        uint32_t px[4] = {0, 0, 0, 0};
+        for (uint32_t q = 0; q < nb; q++) {
+            const uint32_t nib = (uint32_t)(src[q] >> shift) & 0xFu;
+            px[q] = ((nib & 1u) | ((nib & 2u) << 7) | ((nib & 4u) << 14) | ((nib & 8u) << 21)) * 0xFFu;
+        }
+        uint8_t* const dst = out + row * N + (size_t)g * 16;
+        if (nb == 4) *(uint4*)dst = make_uint4(px[0], px[1], px[2], px[3]);
+        else for (uint32_t q = 0; q < nb; q++) ((uint32_t*)dst)[q] = px[q];
+    }
+}
+
+// Inside voxels per layer: layer k = 4 bz + lz holds the bits 16 lz .. 16 lz + 15 of the bricks of slab bz - popcounts against the
+// constant masks k_occ_leaves uses.  Block (part, bz) adds up its share of the slab's B^2 words and writes one partial of four counts;
+// k_vox_layer_sum adds a layer's partials.  Integers throughout: the same counts in any order.
+__global__ void __launch_bounds__(256) k_vox_layer_counts(const uint64_t* __restrict__ bricks, uint32_t depth, uint64_t* __restrict__ parts /* [B][gridDim.x][4] */) {
+    __shared__ uint32_t sh[256 / WAVE][4];
+    const uint32_t bz = blockIdx.y;
+    const uint64_t per_slab = (uint64_t)1 << (2 * depth);
+    const uint64_t* const slab = bricks + bz * per_slab;
+    constexpr uint64_t MZ = 0xFFFFull;
+    uint32_t c[4] = {0, 0, 0, 0};                   // (a thread sees at most 2^20 / 256 words of 16 bits per layer: far below 2^32)
+    for (uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x; i < per_slab; i += (uint64_t)gridDim.x * 256) {
+        const uint64_t w = slab[i];
+        for (int q = 0; q < 4; q++) c[q] += (uint32_t)__popcll(w & (MZ << (16 * q)));
+    }
+    for (int q = 0; q < 4; q++)
+        for (int d = WAVE / 2; d > 0; d >>= 1) c[q] += (uint32_t)__shfl_down((int)c[q], d);
+    if ((threadIdx.x & (WAVE - 1)) == 0) for (int q = 0; q < 4; q++) sh[threadIdx.x / WAVE][q] = c[q];
+    __syncthreads();
+    if (threadIdx.x < 4) {
+        uint64_t s = 0;
+        for (int v = 0; v < 256 / WAVE; v++) s += sh[v][threadIdx.x];
+        parts[((uint64_t)bz * gridDim.x + blockIdx.x) * 4 + threadIdx.x] = s;
+    }
+}
+__global__ void __launch_bounds__(256) k_vox_layer_sum(const uint64_t* __restrict__ parts, uint32_t n_parts, uint32_t n_layers, uint64_t* __restrict__ out) {
+    const uint32_t k = blockIdx.x * 256 + threadIdx.x;
+    if (k >= n_layers) return;
+    uint64_t s = 0;
+    for (uint32_t p = 0; p < n_parts; p++) s += parts[((uint64_t)(k >> 2) * n_parts + p) * 4 + (k & 3)];
+    out[k] = s;
 }
 }  // namespace fhm

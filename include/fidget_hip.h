@@ -358,6 +358,30 @@ typedef struct fhip_occupancy { uint64_t n, s1[3], s2[6]; uint32_t lo[3], hi[3];
 fhip_status fhip_shape_occupancy(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
                                  const uint64_t* var_keys, const float* var_values, uint32_t n_vars, void* out);
 
+/* ---- shape voxels: the inside voxels themselves, as a packed bitmap, and what is made of one ----------
+ * The grid, the voxel centres and "inside" are fhip_shape_occupancy's, recursion included: a Full cell of the octree is all inside, an
+ * Empty one all outside, an ambiguous cell of level `depth` is sampled at the 64 centres of its 4 x 4 x 4 voxels.  The bitmap stores
+ * exactly that, one 64-bit word per such brick: B^3 little-endian uint64_t with B = 1 << depth (fhip_voxels_words; N = 4 B voxels per
+ * axis).  Word (bz * B + by) * B + bx is the brick of the voxels (4 bx + lx, 4 by + ly, 4 bz + lz), lx, ly, lz in 0..3, and its bit
+ * lx + 4 ly + 16 lz is set iff that voxel is inside.  The number of set bits is fhip_occupancy.n at the same depth; the bitmap does not
+ * depend on "mesh_simplify_min_ops" and is identical from run to run.
+ * fhip_shape_voxels: arguments, variable binding, bound tapes and statuses are fhip_shape_occupancy's; depth > 10 (a bitmap beyond
+ * 8 GiB) is FHIP_ERR_UNSUPPORTED before any launch.  `out` holds fhip_voxels_words words and is written completely, zeros included:
+ * the caller need not clear it.  out_is_device != 0: a device pointer, 8-byte aligned (a 16-byte aligned one lets the Full cells be
+ * stored 16 bytes per lane); otherwise a host buffer, filled through the context's pinned landing area as fhip_mesh_stl does.  Blocking
+ * either way.  `cells`: NULL, or the four counters fhip_occupancy.cells holds.
+ * fhip_voxels_slices: layer images for k0 <= k < k1, out[((k - k0) * N + j) * N + i] = 255 where voxel (i, j, k) is inside and 0 where
+ * not.  k0 > k1, k1 > N and depth > 10 are FHIP_ERR_UNSUPPORTED; k0 == k1 is FHIP_OK and writes nothing.
+ * fhip_voxels_layer_counts: out[k], k < N, = the number of inside voxels with third index k; their sum is the number of set bits.
+ * Both follow the effects' convention: on_device != 0, every pointer is a device pointer (bricks and counts 8-byte, slices 16-byte
+ * aligned) and the call is asynchronous on the context's stream; otherwise every pointer is a host buffer. */
+uint64_t fhip_voxels_words(uint32_t depth);
+fhip_status fhip_shape_voxels(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
+                              const uint64_t* var_keys, const float* var_values, uint32_t n_vars, uint64_t* out, int out_is_device,
+                              uint64_t cells[4]);
+fhip_status fhip_voxels_slices(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint32_t k0, uint32_t k1, uint8_t* out, int on_device);
+fhip_status fhip_voxels_layer_counts(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint64_t* out, int on_device);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

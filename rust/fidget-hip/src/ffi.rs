@@ -122,6 +122,13 @@ extern "C" {
     // volume, centroid, second moments and bounds as exact integer sums; `out`: a `fhip_occupancy` (the header declares it void*)
     pub fn fhip_shape_occupancy(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                 var_keys: *const u64, var_values: *const f32, n_vars: u32, out: *mut c_void) -> fhip_status;
+    // the inside voxels as a bitmap of 4 x 4 x 4 bricks (one u64 each, `fhip_voxels_words(depth)` of them), layer images and voxels per layer
+    pub fn fhip_voxels_words(depth: u32) -> u64;
+    pub fn fhip_shape_voxels(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
+                             var_keys: *const u64, var_values: *const f32, n_vars: u32, out: *mut u64, out_is_device: c_int,
+                             cells: *mut u64) -> fhip_status;
+    pub fn fhip_voxels_slices(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, k0: u32, k1: u32, out: *mut u8, on_device: c_int) -> fhip_status;
+    pub fn fhip_voxels_layer_counts(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, out: *mut u64, on_device: c_int) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

@@ -14,6 +14,7 @@ pub mod ffi;
 pub mod mesh;
 pub mod occupancy;
 pub mod render;
+pub mod voxels;
 
 use std::ops::Deref;
 use std::sync::Arc;
