@@ -28,8 +28,6 @@
 #include "host_mesh.hpp"
 #include "frame_schedule.hpp"
 
-#define FH_LDS_MAX 163840  // 160 KiB per workgroup on gfx950
-
 // The C ABI as one translation unit in ten fragments (each was a section of this file when it was 2 900 lines long): the fragments are
 // not stand-alone headers - they are included here, in this order, and share the static helpers of capi_core.hpp.
 #include "capi_core.hpp"

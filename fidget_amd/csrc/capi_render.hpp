@@ -1,9 +1,5 @@
 // Fragment of capi.hip (the 2D / 3D tile renderers: frame set-up, the coarse levels, slabs, streams and frame pipelining); not a stand-alone header: included by capi.hip only.
 // ---- renders ---------------------------------------------------------------------------
-static const uint32_t VM_TILES_2D[] = {128, 32, 8};        // fidget-core/src/vm/mod.rs:255-257
-static const uint32_t FH_LEAF_REGS = 40, FH_LEAF_REGS_T = 44;      // (gen_interp.py main(): fh_columns' 40 x 2 shape, fh_columns_t's 44 x 4)
-static const uint32_t FH_NORMAL_REGS = 40;                         // (gen_normals.py NR)
-
 static fhip_status bind_inputs(fhip_ctx* ctx, const fhip_tape* tape, const int32_t* axis_slots, const uint64_t* keys,
                                const float* vals, uint32_t n, FhRender& P) {
     const fh::HostTape& t = tape->t;
@@ -23,24 +19,6 @@ static fhip_status bind_inputs(fhip_ctx* ctx, const fhip_tape* tape, const int32
     return FHIP_OK;
 }
 
-// 2D hint of the HIP shape: 128 -> 16 with 16 x 16 pixel leaves - what fidget-jit uses (fidget-jit/src/lib.rs:984-986); a fan-out
-// of 64 children per parent fills a wavefront of the tile-stage kernels (the VM's 128 / 32 / 8 fans out by 16)
-static const uint32_t HIP_TILES_2D[] = {128, 16};
-// medium LDS layout of the tile stage (pre-pass levels below the root): 48 KB, three waves per CU
-static const uint32_t MID_REGS = 64, MID_CHOICES = 768;
-static size_t tiles_lds(uint32_t regs, uint32_t choices, uint32_t TL) {
-    size_t b = (size_t)regs * TL * 8 + (size_t)((choices + 15) / 16) * TL * 4 + (size_t)regs * TL + 256;
-    return (b + 15) & ~(size_t)15;
-}
-
-// Which part of the volume a render covers (multi-GPU): root-tile columns round robin (index % n_shards == shard, full
-// depth), or a block of an nx x ny x nz split of the root-tile grid and of the z-slabs (octants: 2 x 2 x 2)
-struct PartSpec {
-    uint32_t shard = 0, n_shards = 1;
-    uint32_t ix = 0, nx = 1, iy = 0, ny = 1, iz = 0, nz = 1;
-};
-// 3D: input slots of the axes, which inputs change along a pixel column (a z coefficient in the axis' matrix row, or a projective
-// matrix), and whether the root tape reads any of them - from the camera matrix, the input binding and the tape alone (before prepare)
 // (option stats, bit 1: where the host thread's time of a 3D frame goes - set-up, prepare, state upload, coarse levels, slabs, finish -
 // printed every 200 frames; tools/host_enqueue.py)
 struct HostSpans {
@@ -59,44 +37,16 @@ struct HostSpans {
 static thread_local HostSpans g_spans;      // (one context per thread: each thread's frames, not a mix)
 #define FH_SPAN(k) do { if (ctx->opt.stats & 2) g_spans.mark(k); } while (0)
 
-static void column_setup(fhip_ctx* ctx, const fhip_tape* tape, const FhRender& P, RenderSetup& R) {
-    uint32_t u[16];
-    memcpy(u, P.mat, sizeof(u));
-    const bool proj = (((u[12] | u[13] | u[14]) & 0x7FFFFFFFu) | (u[15] ^ 0x3F800000u)) != 0;
-    int slot[3] = {-1, -1, -1};
-    for (int sl = 0; sl < FH_MAX_INPUTS; sl++) if (P.in_kind[sl] < 3) slot[P.in_kind[sl]] = sl;   // (the last slot of an axis)
-    for (int ax = 0; ax < 3; ax++) {
-        R.col_slots |= (uint32_t)(slot[ax] < 0 ? 0xFF : slot[ax]) << (8 * ax);
-        const bool dep = proj || (u[4 * ax + 2] & 0x7FFFFFFFu) != 0;
-        if (dep && slot[ax] >= 0) R.col_depmask |= 1u << slot[ax];
-        if (dep) R.col_flags |= 0x20000u << ax;     // (bits 17 .. 19: this axis of the model changes along a pixel column - from the camera alone)
-    }
-    R.col_flags |= proj ? 0x10000u : 0u;
-    // tiles of a tape that reads nothing varying along z repeat along z: worth looking for when x and y do not vary with it
-    R.xy_fixed = !proj && (slot[0] < 0 || !((R.col_depmask >> slot[0]) & 1)) && (slot[1] < 0 || !((R.col_depmask >> slot[1]) & 1));
-    // (FHIP_NO_COLUMN_INV=1, diagnostics / bench: no column-invariance short cut anywhere - every input counts as varying
-    // along z - which is what a model with z in every tape gets)
-    const bool no_inv = ctx->opt.no_column_inv != 0;
-    if (no_inv) R.col_depmask = 0xFFFFFFFFu;
-    R.root_invariant = !no_inv && R.col_depmask != 0xFFFFFFFFu;
-    if (R.root_invariant) {
-        // (the input slots the tape reads, found once per tape: a frame's set-up walked the tape three times for this)
-        uint32_t reads = tape->input_slots.load(std::memory_order_acquire);
-        if (reads & 0x80000000u) {          // not known yet (bit 31: input slots are < 31... FH_MAX_INPUTS)
-            reads = 0;
-            for (uint64_t w : tape->t.ops)
-                if (FH_W_OP((uint32_t)w) == FH_INPUT) reads |= 1u << ((uint32_t)(w >> 32) & 31u);
-            reads &= 0x7FFFFFFFu;
-            tape->input_slots.store(reads, std::memory_order_release);
-        }
-        R.root_invariant = (reads & R.col_depmask & 0x7FFFFFFFu) == 0;
-    }
-    R.column_inv = R.xy_fixed && R.root_invariant && (ctx->opt.no_zrep == 0 || ctx->opt.no_zrep == 3);
+// The facts of a context the frame plan is made from (frame_plan.hpp); arena_bytes: the caller's (prepare: what the frame's arena will have)
+static PlanInputs plan_inputs(const fhip_ctx* ctx) {
+    PlanInputs in;
+    in.slab_layers = ctx->opt.slab_layers; in.no_zrep = ctx->opt.no_zrep; in.no_column_inv = ctx->opt.no_column_inv; in.no_columns_t = ctx->opt.no_columns_t;
+    in.no_asm_normals = ctx->opt.no_asm_normals; in.no_asm_tiles = ctx->opt.no_asm_tiles; in.no_asm_tiles_t = ctx->opt.no_asm_tiles_t;
+    in.no_tape_groups = ctx->opt.no_tape_groups; in.prune2 = ctx->opt.prune2; in.root32_max = ctx->opt.root32_max;
+    in.use_asm = ctx->use_asm; in.use_split = ctx->use_split; in.n_cu = (uint32_t)ctx->n_cu; in.slab_contexts = ctx->slab_contexts; in.arena_bytes = ctx->arena_bytes;
+    return in;
 }
 
-// A frame before this one ran out of tape arena (k_finish3d / k_latch_arena said so in the pinned host word): wait for what is in flight
-// and let the sets come back twice as large, up to option arena_mb.  The frames that overflowed were right (their tiles kept their
-// parents' tapes), only slower.
 // Wait for the work of THIS context - its own streams and its lanes' - and nobody else's: other contexts on the device keep running
 // (hipDeviceSynchronize here stalled every thread's context for an arena that belongs to one).
 static hipError_t sync_own_streams(fhip_ctx* ctx) {
@@ -109,349 +59,92 @@ static hipError_t sync_own_streams(fhip_ctx* ctx) {
         if (L) { const hipError_t r = sync_own_streams(L); if (r != hipSuccess && e == hipSuccess) e = r; }
     return e;
 }
-// `volume_hint`: voxels of a 3D frame whose ROOT tape reads an input that changes along a pixel column (0: none such, or 2D): every
-// tile of every slab then keeps a tape of its own, and the first 128 MB overflow in the first frame - which is then right but many
-// times slower (children keep their parents' tapes), as are the frames until the growth below has caught up.  Sized at about a byte
-// per voxel from the start instead (prospero.vm 1024^3 with z in every tape: peak 0.9 GB per set), before anything is in flight.
-static fhip_status grow_arena_if_asked(fhip_ctx* ctx, size_t tape_ops, uint64_t volume_hint = 0) {
-    size_t need = ((tape_ops + 64) * 8 + 4096) * 4;       // (root tape + its groups, with room to prune into)
-    if (volume_hint) need = std::max<size_t>(need, std::min<uint64_t>(volume_hint, ctx->arena_cap_bytes));
-    bool grow = ctx->host_flags && ctx->host_flags[0] != 0 && ctx->arena_bytes < ctx->arena_cap_bytes;
-    size_t want = grow ? ctx->arena_bytes * (ctx->arena_bytes <= ((size_t)FH_ARENA_START_MB << 20) ? 4 : 2) : ctx->arena_bytes;      // (the first step is the big one: a frame that outgrows the first 128 MB is usually one with z in every tape, at 4 x the ops and more)
-    if (want < need) { want = need; grow = ctx->arena_bytes < std::min(need, ctx->arena_cap_bytes); }
-    if (!grow) return FHIP_OK;
+// The arena of the context's sets becomes `want` bytes (frame_plan.hpp arena_bytes_for: a frame before this one ran out, or this frame
+// needs more from the start): wait for what is in flight and let the sets come back larger
+static fhip_status grow_arena_if_asked(fhip_ctx* ctx, size_t want) {
+    if (want == ctx->arena_bytes) return FHIP_OK;
     HIP_TRY(ctx, sync_own_streams(ctx));       // (every stream of the context, its lanes included: a set's arena is about to be replaced)
-    ctx->host_flags[0] = 0;
-    ctx->arena_bytes = std::min(ctx->arena_cap_bytes, want);
+    if (ctx->host_flags) ctx->host_flags[0] = 0;
+    ctx->arena_bytes = want;
     return FHIP_OK;
 }
 
-static fhip_status prepare(fhip_ctx* ctx, const fhip_tape* tape, bool is3d, const std::vector<uint32_t>& ts,
-                           const PartSpec& part, RenderSetup& R) {
-    const uint32_t shard = part.shard, n_shards = part.n_shards;
-    FhRenderState& S = R.S;
-    FhRender& P = S.P;
+// The root tables of a tape on the device, made once per tape by the first frame that takes the groups path: top ops and choice sources, and
+// (option prune2) the links of the root tape with its choice table and root chain for the linked prune
+static fhip_status ensure_root_tables(fhip_ctx* ctx, const fhip_tape* tape) {
     const fh::HostTape& t = tape->t;
-    if (t.n_outputs != 1) return fail(ctx, FHIP_ERR_BAD_TAPE, "shape tapes have exactly one output");
-    if (ts.empty() || ts.size() > FH_MAX_LEVELS) return fail(ctx, FHIP_ERR_UNSUPPORTED, "1..8 tile levels supported");
-    P.n_levels = (uint32_t)ts.size();
-    uint32_t fanout = 1;
-    for (size_t i = 0; i < ts.size(); i++) {
-        P.tiles[i] = ts[i];
-        if (i) {
-            if (ts[i - 1] <= ts[i] || ts[i - 1] % ts[i]) return fail(ctx, FHIP_ERR_UNSUPPORTED, "bad tile size list");
-            const uint32_t n = ts[i - 1] / ts[i];
-            fanout = std::max(fanout, is3d ? n * n * n : n * n);
-        }
+    std::lock_guard<std::mutex> guard(tape->upload_lock);
+    if (tape->device >= 0 && tape->device != ctx->device) return fail(ctx, FHIP_ERR_UNSUPPORTED, "this tape's device copies belong to another device: build the tape per device");
+    tape->device = ctx->device;
+    if (!tape->d_top) {
+        static_assert(sizeof(FhTopOp) == sizeof(fh::TopOp), "top op layout");
+        HIP_TRY(ctx, hipMalloc((void**)&tape->d_top, tape->plan.top.size() * sizeof(FhTopOp)));
+        HIP_TRY(ctx, hipMemcpy(tape->d_top, tape->plan.top.data(), tape->plan.top.size() * sizeof(FhTopOp), hipMemcpyHostToDevice));
+        HIP_TRY(ctx, hipMalloc((void**)&tape->d_chsrc, std::max<size_t>(tape->plan.choice_src.size(), 1) * 4));
+        HIP_TRY(ctx, hipMemcpy(tape->d_chsrc, tape->plan.choice_src.data(), tape->plan.choice_src.size() * 4, hipMemcpyHostToDevice));
     }
-    if (fanout > 64) return fail(ctx, FHIP_ERR_UNSUPPORTED, "tile fan-out above 64 children");
-    // (a one-level 2D list - the small-image passes of render2d_frame: root groups of 64 tiles - takes the 64-lane tile stage too)
-    const uint32_t TL = R.tl = (fanout > 16 || (!is3d && ts.size() == 1 && R.one_level_64)) ? 64 : 16;
-    if (is3d && ts.back() != 8) return fail(ctx, FHIP_ERR_UNSUPPORTED, "3D leaves must be 8^3 (one 8x8 footprint per wave)");
-    // (register numbers are 12-bit fields of a tape word.  The device prunes keep old -> new register maps in bytes with 0xFF =
-    // dead: a CHILD tape has 255 registers at most - one that would need more keeps its parent's tape; the root tape may have
-    // more, its register file then lives in HBM: gscratch below)
-    if (t.n_regs >= FH_MAX_REGS) return fail(ctx, FHIP_ERR_UNSUPPORTED, "renders support up to 4095 registers");
-    if (t.ops.size() >= (1u << 24)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "renders support tapes of up to 2^24 ops");   // (FhLeafRef packs length | registers << 24)
-    P.max_regs = std::max<uint32_t>(t.n_regs, 1);
-    P.max_choices = t.n_choices;
-    P.roots_x = (P.width + ts[0] - 1) / ts[0];
-    P.roots_y = (P.height + ts[0] - 1) / ts[0];
-    // z-slabs: the per-slab chains (tile stage, leaf kernel, tail) take `slab_layers` root-tile layers per step when the coarse
-    // levels are evaluated for the whole volume up front (the length of the tile chain is its number of steps: every step's
-    // launches leave most of the machine idle); one layer per step otherwise
-    const uint32_t n_layers = is3d ? (P.depth + ts[0] - 1) / ts[0] : 1;
-    // (a two-level list - root tiles of 32^3 straight above the leaves, what small images and parts of a frame take - gets a pre-pass of
-    // its ONE coarse level; option slab_layers counts layers of 128 voxels, whatever the root tile)
-    const bool prepass_ok = is3d && ts.size() >= 2 && n_layers <= FH_MAX_SLABS;
-    uint32_t SL = prepass_ok ? (uint32_t)std::max(1, std::min(8, ctx->opt.slab_layers)) * std::max<uint32_t>(1, 128 / ts[0]) : 1u;
-    // (the leaf table: <= 64 eight-voxel layers per slab; at least two slabs, so that the tile stage of one still runs beside the
-    // leaf kernel of the other - bear.vm at 512^3, four layers: 3.68 ms per frame as two slabs, 3.77 as one)
-    while (SL > 1 && (ts[0] * SL / 8 > 64 || SL * 2 > n_layers)) SL >>= 1;
-    P.slab = ts[0] * SL;
-    R.n_slabs = is3d ? (P.depth + P.slab - 1) / P.slab : 1;
-    R.n_layers = n_layers;
-    R.full = tape_is_full(t);
-    // assembly leaf kernels: supported opcodes only (any 4x4 screen-to-model matrix, projective ones included)
-    R.asm_points = ctx->use_asm && is3d && (tape_asm_ok(t) || !ctx->opt.no_columns_t);
-    R.asm_points_t = R.asm_points && !tape_asm_ok(t);   // transcendental / modulo / rng opcodes: the variant that calls the compiled routines
-    // (the most registers of a leaf the leaf kernel takes - gen_interp.py main(): the largest register-file shape of fh_columns / fh_columns_t)
-    R.S.leaf_asm_regs = !R.asm_points ? 32u : (R.asm_points_t ? FH_LEAF_REGS_T : FH_LEAF_REGS);
-    // (fh_normals_t has the transcendental, rng and atan2 handlers; a modulo's gradient - div_euclid - keeps the C++ kernel)
-    R.asm_normals = R.asm_points && !ctx->opt.no_asm_normals && (!R.asm_points_t || !tape_has_mod(t));
-    R.S.norm_asm_regs = R.asm_normals ? FH_NORMAL_REGS : 32u;
-
-    // LDS budgets: BIG = bounded by the root tape (children never need more); SMALL = fixed
-    R.lds_tiles_big = tiles_lds(P.max_regs, P.max_choices, TL);
-    R.lds_tiles_small = tiles_lds(SMALL_REGS, SMALL_CHOICES, TL);
-    R.lds_tiles_mid = tiles_lds(MID_REGS, MID_CHOICES, TL);
-    R.lds_points_big = (size_t)P.max_regs * WAVE * 4;
-    R.lds_normals_big = (size_t)P.max_regs * WAVE * 16;
-    R.lds_normals_small = (size_t)32 * WAVE * 16;
-    // A register file that does not fit LDS (more than ~160 registers for the gradients, ~280 for the intervals) lives in HBM:
-    // the reference spills registers beyond its file to memory slots (compiler/alloc.rs:116-125), this is the device's form of
-    // it - the root-sized kernel variants take a region of `gscratch` per workgroup instead of LDS.  A slow path by design
-    // (a few hundred workgroups, no pipelining: render3d_part), for tapes the fast paths cannot take anyway.
-    S.gscratch = nullptr; S.gscratch_stride = 0;
-    R.big_hbm = R.lds_tiles_big > FH_LDS_MAX || R.lds_normals_big > FH_LDS_MAX || R.lds_points_big > FH_LDS_MAX;
-    if (R.big_hbm) {
-        const size_t stride = (std::max(std::max(R.lds_tiles_big, R.lds_normals_big), R.lds_points_big) + 255) & ~(size_t)255;
-        if (stride >= ((size_t)1 << 31)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "register file too large");
-        R.hbm_waves = (uint32_t)std::max<size_t>(64, std::min<size_t>((size_t)ctx->n_cu * 4, ((size_t)1 << 30) / stride));
-        HIP_TRY(ctx, ctx->gscratch.ensure((size_t)R.hbm_waves * stride));
-        S.gscratch = (char*)ctx->gscratch.p; S.gscratch_stride = (uint32_t)stride;
-        R.lds_tiles_big = R.lds_normals_big = R.lds_points_big = 0;      // (no dynamic LDS for those launches; grids: blocks_big)
-    }
-
-    // pre-pass: with >= 3 levels the two coarsest levels are evaluated for all z-slabs at once
-    S.n_slabs = R.n_slabs;
-    S.frame_stamp = ++ctx->frame_stamp;
-    S.pre_levels = prepass_ok ? std::min<uint32_t>(2, (uint32_t)ts.size() - 1) : 0;
-
-    // root-tile layers of this part: layer k of the block split belongs to iz = k * nz / n_layers (iz = nz - 1: the front);
-    // its z-slabs are those that hold one of its layers (a slab shared with another part has work for this part's layers only)
-    uint32_t layer_lo = 0, layer_hi = n_layers;
-    if (part.nz > 1) {
-        layer_lo = n_layers; layer_hi = 0;
-        for (uint32_t k = 0; k < n_layers; k++)
-            if ((uint64_t)k * part.nz / n_layers == part.iz) { layer_lo = std::min(layer_lo, k); layer_hi = std::max(layer_hi, k + 1); }
-        if (layer_lo >= layer_hi) layer_lo = layer_hi = 0;   // more parts than layers: nothing to do
-    }
-    R.slab_lo = layer_lo / SL; R.slab_hi = (layer_hi + SL - 1) / SL;
-    if (!S.pre_levels) { R.slab_lo = layer_lo; R.slab_hi = layer_hi; }
-    // root groups: runs of <= TL root tiles of this part, index = first + lane * stride (one set per slab in pre-pass mode)
-    struct Run { uint32_t first, n, stride; };
-    std::vector<Run> runs;
-    if (part.nx > 1 || part.ny > 1) {       // a block of root-tile columns: per x, the run of its y range (x-major numbering)
-        for (uint32_t tx = 0; tx < P.roots_x; tx++) {
-            if ((uint64_t)tx * part.nx / P.roots_x != part.ix) continue;
-            uint32_t y0 = P.roots_y, y1 = 0;
-            for (uint32_t ty = 0; ty < P.roots_y; ty++)
-                if ((uint64_t)ty * part.ny / P.roots_y == part.iy) { y0 = std::min(y0, ty); y1 = std::max(y1, ty + 1); }
-            for (uint32_t ty = y0; ty < y1; ty += TL) runs.push_back(Run{tx * P.roots_y + ty, std::min<uint32_t>(TL, y1 - ty), 1});
-        }
-    } else {
-        std::vector<uint32_t> mine;
-        for (uint32_t ri = shard; ri < P.roots_x * P.roots_y; ri += n_shards) mine.push_back(ri);
-        for (size_t i = 0; i < mine.size(); i += TL) runs.push_back(Run{mine[i], (uint32_t)std::min<size_t>(TL, mine.size() - i), n_shards});
-    }
-    FhTapeRef root{0, (uint32_t)t.ops.size(), (uint16_t)t.n_regs, (uint16_t)t.n_choices};
-    R.smooth_tape = t.ops.size() > 200 && (size_t)t.n_choices * 10 < t.ops.size();
-    // Column invariance at the ROOT: a root tape that reads no input varying along a pixel column, under a camera
-    // that keeps x and y fixed along it, has the same interval, the same choices and the same pruned tape in every root tile of a
-    // column of root tiles.  One layer per z-slab is evaluated (the slab's back-most: FhGroup::x = how many layers of the slab it stands
-    // for) and the push stage hands the result to the stack - a fill with the nearest copy's depth, ONE queue entry carrying the copies,
-    // exactly what the levels below do for column-invariant parents.  prospero.vm at 1024^3: 64 root tiles instead of 512.
-    R.root_zrep = is3d && S.pre_levels > 0 && ctx->use_split && TL == 64 && R.column_inv;
-    // ... and of such a frame ONLY THE FRONT SLAB is rendered at all.  Nothing the frame evaluates depends on z: every tile, every leaf of
-    // a slab further back repeats the front slab's result for its column with a smaller depth - a filled tile is filled in front of it, a
-    // leaf's hits are the front leaf's hits, a pixel the front slab left empty is outside the model at every z - and the image takes the
-    // largest depth.  The slabs behind the first (prospero.vm at 1024^3: half the root level's children - the linked prune then runs
-    // its workgroups in one round instead of two -, one of two tile chains, one of two leaf launches) are not queued.  (no_zrep 3: every
-    // slab, as before.)
-    R.front_only = R.root_zrep && ctx->opt.no_zrep == 0;
-    R.slab_stop = R.front_only && R.slab_hi > R.slab_lo ? R.slab_hi - 1 : R.slab_lo;
-    uint32_t q0_layers = S.pre_levels ? layer_hi - layer_lo : 1;
-    if (R.root_zrep) {
-        q0_layers = 0;
-        for (uint32_t sb = R.slab_hi; sb-- > R.slab_stop;) {       // front slabs first
-            const uint32_t lo = std::max(layer_lo, sb * SL), hi = std::min(layer_hi, (sb + 1) * SL);
-            if (lo >= hi) continue;
-            q0_layers++;
-            for (const Run& r : runs) {
-                FhGroup g{};
-                g.tape = root;
-                g.first = r.first; g.n = r.n; g.stride = r.stride;
-                g.z = lo * ts[0]; g.x = hi - lo;
-                R.roots.push_back(g);
+    if (ctx->opt.prune2 && !tape->links_tried) {
+        tape->links_tried = true;
+        std::vector<uint64_t> lk;
+        std::vector<uint64_t> cops;
+        if (fh::compute_links(t, lk, cops)) {
+            // (published together or not at all: a failure half way must not leave links without their choice table)
+            uint64_t *dl = nullptr, *dc = nullptr;
+            // the root chain's ops (plan.chain: acc = min / max(acc, term) all the way to the OUTPUT op) in evaluation order, behind the choice
+            // table: the linked prune's liveness pass starts from every kept op of the chain at once instead of walking it link by link
+            std::vector<uint32_t> chain = chain_table(tape, cops);
+            const size_t n_cops = std::max<size_t>(cops.size(), 1);
+            cops.resize(n_cops + (chain.size() + 1) / 2, 0);
+            if (!chain.empty()) memcpy(cops.data() + n_cops, chain.data(), chain.size() * 4);
+            hipError_t e = hipMalloc((void**)&dl, lk.size() * 8);
+            if (e == hipSuccess) e = hipMemcpy(dl, lk.data(), lk.size() * 8, hipMemcpyHostToDevice);
+            if (e == hipSuccess) e = hipMalloc((void**)&dc, std::max<size_t>(cops.size(), 1) * 8);
+            if (e == hipSuccess) e = hipMemcpy(dc, cops.data(), cops.size() * 8, hipMemcpyHostToDevice);
+            if (e != hipSuccess) {
+                if (dl) (void)hipFree(dl);
+                if (dc) (void)hipFree(dc);
+                HIP_TRY(ctx, e);
             }
+            tape->d_links = dl; tape->d_ctab = dc; tape->n_chain = (uint32_t)chain.size();
         }
-    } else
-    for (uint32_t k = 0; k < q0_layers; k++)
-        for (const Run& r : runs) {
-            FhGroup g{};
-            g.tape = root;
-            g.first = r.first; g.n = r.n; g.stride = r.stride;
-            g.z = (layer_hi - 1 - k) * ts[0];  // front layers first
-            R.roots.push_back(g);
-        }
-    R.groups_per_slab = (uint32_t)(R.roots.size() / std::max<uint32_t>(q0_layers, 1));
-    if (layer_lo >= layer_hi) { R.roots.clear(); R.groups_per_slab = 0; }
-
-    // capacities (exact upper bounds): queue[l] holds the tiles of size ts[l-1] that can be
-    // ambiguous, per slab for the per-slab levels and for the whole volume for pre-pass levels
-    uint32_t qcaps[FH_MAX_LEVELS] = {0};
-    qcaps[0] = std::max<uint32_t>((uint32_t)R.roots.size(), 1);
-    for (size_t l = 1; l < ts.size(); l++) {
-        const uint64_t tp = ts[l - 1];
-        uint64_t c = (uint64_t)((P.width + tp - 1) / tp) * ((P.height + tp - 1) / tp) * (is3d ? P.slab / tp : 1);
-        if (l < S.pre_levels) c *= R.n_slabs;
-        qcaps[l] = (uint32_t)std::max<uint64_t>(c, 1);
     }
-    const uint64_t tl = ts.back();
-    const uint64_t fw = (P.width + tl - 1) / tl, fhh = (P.height + tl - 1) / tl;
-    const uint64_t leaf_cap = fw * fhh * (is3d ? P.slab / tl : 1);
-    R.table_words = is3d ? (uint32_t)leaf_cap : 0;
-    R.n_footprints = (uint32_t)(fw * fhh);
+    return FHIP_OK;
+}
 
-    { const fhip_status gs_ = grow_arena_if_asked(ctx, t.ops.size(), is3d && !R.root_invariant ? (uint64_t)P.width * P.height * P.depth : 0); if (gs_) return gs_; }
-    HIP_TRY(ctx, ctx->state.ensure(4 * sizeof(FhRenderState)));
-    { void* const before = ctx->arena.p; HIP_TRY(ctx, ctx->arena.ensure(ctx->arena_bytes)); if (ctx->arena.p != before) ctx->resident_serial = 0; }
-    for (size_t l = 0; l < ts.size(); l++) HIP_TRY(ctx, ctx->queue[l].ensure((size_t)qcaps[l] * sizeof(FhGroup)));
-    if (S.pre_levels) HIP_TRY(ctx, ctx->squeue.ensure((size_t)qcaps[S.pre_levels] * R.n_slabs * sizeof(FhGroup)));
-    HIP_TRY(ctx, ctx->leaves.ensure(leaf_cap * sizeof(FhLeaf)));
-    const size_t extra = std::min<uint32_t>(ctx->slab_contexts, std::max<uint32_t>(R.n_slabs, 1)) - 1;      // (slab contexts beyond the first)
-    if (is3d) HIP_TRY(ctx, ctx->leaves_b.ensure(extra * leaf_cap * sizeof(FhLeaf)));
+// The frame's pointers into the context's buffers, its counters at zero, its stamp
+static void bind_state(fhip_ctx* ctx, const fhip_tape* tape, bool is3d, RenderSetup& R) {
+    FhRenderState& S = R.S;
+    const FhRender& P = S.P;
+    S.frame_stamp = ++ctx->frame_stamp;
+    if (R.hip_tiles_unasked) ctx->hip_tile_frames++;
+    S.gscratch = R.big_hbm ? (char*)ctx->gscratch.p : nullptr;
     if (is3d) {
-        if (P.width > 65535 || P.height > 65535) return fail(ctx, FHIP_ERR_UNSUPPORTED, "3D renders support images up to 65535 x 65535");
-        // (the assembly leaf and normals kernels address the z-buffer as base + a 32-bit byte offset of 8 bytes per pixel)
-        if ((uint64_t)P.width * P.height >= ((uint64_t)1 << 29)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "3D renders support images of fewer than 2^29 pixels");
-        HIP_TRY(ctx, ctx->leaf_table.ensure(leaf_cap * sizeof(FhLeafRef)));
-        HIP_TRY(ctx, ctx->leaf_table_b.ensure(extra * leaf_cap * sizeof(FhLeafRef)));
-        HIP_TRY(ctx, ctx->zbuf.ensure((size_t)P.width * P.height * 8));
-        HIP_TRY(ctx, ctx->normals.ensure((size_t)P.width * P.height * 12));
-        // (three footprint lists and the normals kernel's list of leaves with a hit: at most every leaf of a slab)
-        // (a footprint's pixels name at most one leaf per layer of the slab; footprint i of the class lists goes to bucket i % 64)
-        R.hit_bucket_cap = (uint32_t)(((size_t)R.n_footprints + FH_HIT_BUCKETS - 1) / FH_HIT_BUCKETS * (P.slab / tl));
-        R.hit_words = (size_t)FH_HIT_BUCKETS * (FH_HIT_STRIDE + R.hit_bucket_cap);
-        HIP_TRY(ctx, ctx->fp_lists.ensure(((size_t)R.n_footprints * 3 + R.hit_words) * 4));
-        HIP_TRY(ctx, ctx->fp_lists_b.ensure(extra * ((size_t)R.n_footprints * 3 + R.hit_words) * 4));
-        size_t mind_words = 0;
-        for (size_t l = 0; l < ts.size(); l++) mind_words += (size_t)((P.width + ts[l] - 1) / ts[l]) * ((P.height + ts[l] - 1) / ts[l]);
-        HIP_TRY(ctx, ctx->mind.ensure(mind_words * 4));
-        R.mind_words = mind_words;   // (cleared - empty image: nothing occluded - by the frame's first launch, upload_frame)
         uint32_t* mp = (uint32_t*)ctx->mind.p;
-        for (size_t l = 0; l < ts.size(); l++) {
+        for (uint32_t l = 0; l < P.n_levels; l++) {
             S.mind[l] = mp;
-            mp += (size_t)((P.width + ts[l] - 1) / ts[l]) * ((P.height + ts[l] - 1) / ts[l]);
+            mp += (size_t)((P.width + P.tiles[l] - 1) / P.tiles[l]) * ((P.height + P.tiles[l] - 1) / P.tiles[l]);
         }
         for (int c = 0; c < 3; c++) S.fp_list[c] = (uint32_t*)ctx->fp_lists.p + (size_t)c * R.n_footprints;
         S.hit_list = (uint32_t*)ctx->fp_lists.p + (size_t)3 * R.n_footprints;
     }
     S.arena = (uint64_t*)ctx->arena.p;
-    S.arena_cap = (uint32_t)std::min<size_t>(ctx->arena_bytes / 8 - 64, 0x7FFFFFE0u);  // slack: the interpreters prefetch up to 12 ops past a tape's end
-    S.arena_head = S.arena_root_end = (uint32_t)t.ops.size();
     S.arena_overflow = 0;
     for (int l = 0; l < FH_MAX_LEVELS; l++) {
         S.queue[l] = (FhGroup*)ctx->queue[l].p;
         S.count[l] = S.cursor[l] = S.count_big[l] = S.cursor_big[l] = 0;
     }
     S.count_big[0] = (uint32_t)R.roots.size();  // the root tape always takes the large LDS layout
-    for (size_t l = 0; l < ts.size(); l++) S.qcap[l] = qcaps[l];
-    R.split = ctx->use_split && R.tl == 64;
-    // (tapes with sin cos tan asin acos atan exp ln: the *_t variants of the tile kernels, which carry those interval handlers;
-    // and, since round 5, those for atan2, mod, mix, rand)
-    R.asm_tiles_t = !tape_asm_ok(t) && tape_tiles_t_ok(t) && !ctx->opt.no_asm_tiles_t;
-    // (not with a register file in HBM: the assembly tile kernels - fh_prune1, the groups path and the linked prune with them - keep
-    // registers AND choices in LDS, and a tape of few registers can still outgrow it by its choices alone, ~5 600 of them)
-    R.asm_tiles = R.split && ctx->use_asm && !ctx->opt.no_asm_tiles && (tape_asm_ok(t) || R.asm_tiles_t) && t.n_regs <= 128 && !R.big_hbm;
-    R.asm_tiles_t = R.asm_tiles_t && R.asm_tiles;
-    // (fhip_render_counters out[6]: frames whose tile stage took the HIP kernels although nobody switched the assembly ones off - left: tapes
-    // of more than 128 registers and register files in HBM)
-    if (!R.asm_tiles && R.split && ctx->use_asm && !ctx->opt.no_asm_tiles) ctx->hip_tile_frames++;
-    // levels whose forward pass exports its choices to the one-wave-per-child prune (fh_prune1): long tapes, few parents.
-    // 3D: of the pre-pass levels, level 0 (measured); 2D: level 0
-    R.exp_levels = is3d ? std::min(S.pre_levels, 1u) : 1u;
-    R.prune1 = R.asm_tiles && !R.asm_tiles_t && R.exp_levels > 0;      // (the *_t kernels have no export mode)
-    // tape parallelism: level 0 evaluates the root tree's terms as independent groups on different
-    // waves, then the tree itself; the prune sees the root tape with its usual choices
-    R.groups = R.prune1 && !tape->tgroups.empty() && !ctx->opt.no_tape_groups;
-    S.n_tgroups = 0;
     if (R.groups) {
-        uint32_t off = (uint32_t)t.ops.size() + 16, mr = 1, mc = 0;
-        for (size_t g = 0; g < tape->tgroups.size(); g++) {
-            const fh::HostTape& gt = tape->tgroups[g];
-            S.tgroup[g] = FhTapeRef{off, (uint32_t)gt.ops.size(), (uint16_t)gt.n_regs, (uint16_t)gt.n_choices};
-            off += (uint32_t)gt.ops.size() + 16;  // slack: the interpreters prefetch past a tape's end
-            mr = std::max(mr, gt.n_regs); mc = std::max(mc, gt.n_choices);
-        }
-        R.group_regs = mr; R.group_choices = mc;
-        R.lds_tiles_group = tiles_lds(mr, mc, TL);
-        if (mr <= 128 && R.lds_tiles_group <= FH_LDS_MAX && (size_t)off * 8 + 4096 <= ctx->arena_bytes) {
-            S.n_tgroups = (uint32_t)tape->tgroups.size();
-            S.n_terms = tape->plan.n_terms; S.n_top = (uint32_t)tape->plan.top.size(); S.top_chain = tape->plan.chain ? 1 : 0;
-            S.troot_len = (uint32_t)t.ops.size(); S.troot_choices = t.n_choices; S.troot_regs = std::max<uint32_t>(t.n_regs, 1);
-            S.arena_head = S.arena_root_end = off;
-            std::lock_guard<std::mutex> guard(tape->upload_lock);
-            if (tape->device >= 0 && tape->device != ctx->device) return fail(ctx, FHIP_ERR_UNSUPPORTED, "this tape's device copies belong to another device: build the tape per device");
-            tape->device = ctx->device;
-            if (!tape->d_top) {
-                static_assert(sizeof(FhTopOp) == sizeof(fh::TopOp), "top op layout");
-                HIP_TRY(ctx, hipMalloc((void**)&tape->d_top, tape->plan.top.size() * sizeof(FhTopOp)));
-                HIP_TRY(ctx, hipMemcpy(tape->d_top, tape->plan.top.data(), tape->plan.top.size() * sizeof(FhTopOp), hipMemcpyHostToDevice));
-                HIP_TRY(ctx, hipMalloc((void**)&tape->d_chsrc, std::max<size_t>(tape->plan.choice_src.size(), 1) * 4));
-                HIP_TRY(ctx, hipMemcpy(tape->d_chsrc, tape->plan.choice_src.data(), tape->plan.choice_src.size() * 4, hipMemcpyHostToDevice));
-            }
-            S.ttop = tape->d_top; S.chsrc = tape->d_chsrc;
-            // the linked prune of the root level (option prune2; prune2.hip): links of the root tape, made once with it.  0.275 ms
-            // against fh_prune1's 0.344 per 1024^3 frame of prospero.vm (a child of that root tape keeps ~580 ops, up to 1011);
-            // fh_prune1 stays behind it for the children it leaves marked (more than 64 registers / FH_P2_MAX_KEPT ops)
-            if (ctx->opt.prune2 && !tape->links_tried) {
-                tape->links_tried = true;
-                std::vector<uint64_t> lk;
-                std::vector<uint64_t> cops;
-                if (fh::compute_links(t, lk, cops)) {
-                    // (published together or not at all: a failure half way must not leave links without their choice table)
-                    uint64_t *dl = nullptr, *dc = nullptr;
-                    // the root chain's ops (plan.chain: acc = min / max(acc, term) all the way to the OUTPUT op) in evaluation order, behind the choice
-                    // table: the linked prune's liveness pass starts from every kept op of the chain at once instead of walking it link by link
-                    std::vector<uint32_t> chain = chain_table(tape, cops);
-                    const size_t n_cops = std::max<size_t>(cops.size(), 1);
-                    cops.resize(n_cops + (chain.size() + 1) / 2, 0);
-                    if (!chain.empty()) memcpy(cops.data() + n_cops, chain.data(), chain.size() * 4);
-                    hipError_t e = hipMalloc((void**)&dl, lk.size() * 8);
-                    if (e == hipSuccess) e = hipMemcpy(dl, lk.data(), lk.size() * 8, hipMemcpyHostToDevice);
-                    if (e == hipSuccess) e = hipMalloc((void**)&dc, std::max<size_t>(cops.size(), 1) * 8);
-                    if (e == hipSuccess) e = hipMemcpy(dc, cops.data(), cops.size() * 8, hipMemcpyHostToDevice);
-                    if (e != hipSuccess) {
-                        if (dl) (void)hipFree(dl);
-                        if (dc) (void)hipFree(dc);
-                        HIP_TRY(ctx, e);
-                    }
-                    tape->d_links = dl; tape->d_ctab = dc; tape->n_chain = (uint32_t)chain.size();
-                }
-            }
-            R.p2_cap_kept = (uint32_t)FH_P2_MAX_KEPT;
-            R.lds_prune2 = (size_t)FH_P2_WPB * fh_p2_wave_lds(t.n_choices, R.p2_cap_kept) + (((size_t)tape->n_chain * 4 + 15) & ~(size_t)15);
-            R.n_chain = tape->n_chain;
-            // (one workgroup of FH_P2_WPB children per CU: beyond two rounds of them - 2048^3 has 4 096 root tiles - the scalar sweep,
-            // whose waves all fit the machine at once, is the faster one again: 2.09 against 2.17 ms per frame)
-            R.prune2 = tape->d_links && tape->d_ctab && ctx->opt.prune2 && t.ops.size() <= FH_P2_MAX_OPS && t.n_choices <= FH_P2_MAX_CHOICES &&
-                       R.lds_prune2 <= FH_LDS_MAX && R.roots.size() * 64 <= (size_t)2 * ctx->n_cu * FH_P2_WPB;      // (a root group = up to 64 root tiles)
-            R.d_ctab = tape->d_ctab;
-            R.d_links = tape->d_links;
-            const size_t blocks = qcaps[0];
-            HIP_TRY(ctx, ctx->tvals.ensure(blocks * S.n_terms * WAVE * 8));
-            HIP_TRY(ctx, ctx->topch.ensure(blocks * S.n_top * WAVE));
-            HIP_TRY(ctx, ctx->chwr.ensure(blocks * S.n_tgroups * ((t.n_choices + 15) / 16) * WAVE * 4 + 256));
-            S.tvals = (float*)ctx->tvals.p; S.topch = (uint8_t*)ctx->topch.p; S.chwr = (uint32_t*)ctx->chwr.p;
-        } else R.groups = false;
+        S.ttop = tape->d_top; S.chsrc = tape->d_chsrc;
+        R.d_ctab = tape->d_ctab; R.d_links = tape->d_links;
+        S.tvals = (float*)ctx->tvals.p; S.topch = (uint8_t*)ctx->topch.p; S.chwr = (uint32_t*)ctx->chwr.p;
     }
-    if (R.prune1) {  // choice words of the pre-pass levels' forward passes: [slot][word][lane]
-        uint32_t cap = 1;
-        for (uint32_t l = 0; l < std::max(S.pre_levels, R.exp_levels); l++) cap = std::max(cap, qcaps[l] * (l == 0 && R.groups ? S.n_tgroups : 1u));
-        const size_t words[2] = {(SMALL_CHOICES + 15) / 16, ((size_t)P.max_choices + 15) / 16};
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(ctx, ctx->chw[k].ensure(std::max<size_t>(cap * words[k] * 256, 256)));
-            S.chw[k] = (uint32_t*)ctx->chw[k].p;
-        }
-    }
-    if (R.split) {
-        uint32_t cap = 1;
-        for (size_t l = 0; l < ts.size(); l++) cap = std::max(cap, qcaps[l] * (l == 0 && R.groups ? S.n_tgroups : 1u));
-        for (int k = 0; k < 2; k++) {
-            HIP_TRY(ctx, ctx->slots[k].ensure((size_t)cap * sizeof(FhSlot)));
-            S.slots[k] = (FhSlot*)ctx->slots[k].p;
-            S.slot_cap[k] = cap;
-        }
-    }
+    if (R.prune1) for (int k = 0; k < 2; k++) S.chw[k] = (uint32_t*)ctx->chw[k].p;
+    if (R.split) for (int k = 0; k < 2; k++) S.slots[k] = (FhSlot*)ctx->slots[k].p;
     S.squeue = (FhGroup*)ctx->squeue.p;
-    S.squeue_cap = qcaps[S.pre_levels];
-    S.arena_frame_end = S.arena_root_end;
     for (int k = 0; k < FH_MAX_SLABS; k++) S.scount[k] = S.scount_big[k] = 0;
     S.queue_overflow = 0;
     S.leaves = (FhLeaf*)ctx->leaves.p;
-    S.leaf_cap = (uint32_t)leaf_cap;
     S.n_leaves = S.leaf_cursor = S.leaf_cursor_big = S.normal_cursor = S.normal_cursor_big = 0;
     S.leaf_table = (FhLeafRef*)ctx->leaf_table.p;
     for (int c = 0; c < 3; c++) S.fp_count[c] = S.fp_cursor[c] = 0;
@@ -461,9 +154,36 @@ static fhip_status prepare(fhip_ctx* ctx, const fhip_tape* tape, bool is3d, cons
     memset(S.stat, 0, sizeof(S.stat));
     memset(S.leaf_stat, 0, sizeof(S.leaf_stat));
     S.want_stats = (ctx->profiling || ctx->probe || (ctx->opt.stats & 1)) ? 1 : 0;
-    if (((size_t)t.ops.size() + 64) * 8 > ctx->arena_bytes) return fail(ctx, FHIP_ERR_UNSUPPORTED, "tape larger than the arena");
-    // level-0 groups sit at the back of queue[0] (the "big" half), in reverse order
-    std::reverse(R.roots.begin(), R.roots.end());
+}
+
+// A frame's set-up: the plan (frame_plan.hpp: every check, size and path), then the device's part of it in a fixed order - the arena's
+// growth, the buffers, the tape's root tables, the pointers
+static fhip_status prepare(fhip_ctx* ctx, const fhip_tape* tape, const TapeFacts& facts, bool is3d, const std::vector<uint32_t>& ts,
+                           const PartSpec& part, RenderSetup& R) {
+    static_assert(PLAN_BAD_TAPE == FHIP_ERR_BAD_TAPE && PLAN_UNSUPPORTED == FHIP_ERR_UNSUPPORTED, "the plan's refusals are fhip_status values");
+    const FhRender& P = R.S.P;
+    PlanInputs in = plan_inputs(ctx);
+    in.arena_bytes = arena_bytes_for(ctx->arena_bytes, ctx->arena_cap_bytes, (size_t)FH_ARENA_START_MB << 20, ctx->host_flags && ctx->host_flags[0] != 0, facts.n_ops,
+                                     is3d && !R.root_invariant ? (uint64_t)P.width * P.height * P.depth : 0);
+    const PlanStatus ps = plan_frame(facts, in, is3d, ts, part, R);
+    if (ps.status) return fail(ctx, (fhip_status)ps.status, ps.msg);
+    { const fhip_status gs = grow_arena_if_asked(ctx, in.arena_bytes); if (gs) return gs; }
+    const FrameBytes& B = R.bytes;
+    HIP_TRY(ctx, ctx->gscratch.ensure(B.gscratch));
+    HIP_TRY(ctx, ctx->state.ensure(4 * sizeof(FhRenderState)));
+    { void* const before = ctx->arena.p; HIP_TRY(ctx, ctx->arena.ensure(ctx->arena_bytes)); if (ctx->arena.p != before) ctx->resident_serial = 0; }
+    for (size_t l = 0; l < ts.size(); l++) HIP_TRY(ctx, ctx->queue[l].ensure(B.queue[l]));
+    const std::pair<DevBuf*, size_t> list[] = {{&ctx->squeue, B.squeue}, {&ctx->leaves, B.leaves}, {&ctx->leaves_b, B.leaves_b}, {&ctx->leaf_table, B.leaf_table},
+                                               {&ctx->leaf_table_b, B.leaf_table_b}, {&ctx->zbuf, B.zbuf}, {&ctx->normals, B.normals}, {&ctx->fp_lists, B.fp_lists},
+                                               {&ctx->fp_lists_b, B.fp_lists_b}, {&ctx->mind, B.mind}, {&ctx->tvals, B.tvals}, {&ctx->topch, B.topch}, {&ctx->chwr, B.chwr},
+                                               {&ctx->chw[0], B.chw[0]}, {&ctx->chw[1], B.chw[1]}, {&ctx->slots[0], B.slots}, {&ctx->slots[1], B.slots}};
+    for (const auto& b : list) HIP_TRY(ctx, b.first->ensure(b.second));      // (0 bytes: not needed by this frame, left as it is)
+    if (R.groups) {
+        const fhip_status us = ensure_root_tables(ctx, tape);
+        if (us) return us;
+        plan_linked_prune(facts, in, tape->d_links && tape->d_ctab, tape->n_chain, R);
+    }
+    bind_state(ctx, tape, is3d, R);
     return FHIP_OK;
 }
 
@@ -747,7 +467,7 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
                 while (a / b > 8) {       // the largest tile below `a` that takes at most 8 x 8 of `a` and is made of whole `b`s
                     uint32_t c = 0;
                     for (uint32_t k = 8; k >= 2 && !c; k--) if (a % k == 0 && (a / k) % b == 0 && a / k > b) c = a / k;
-                    if (!c) break;        // (no such divisor: left to prepare(), which refuses the fan-out)
+                    if (!c) break;        // (no such divisor: left to the plan, which refuses the fan-out)
                     out.push_back(c); tags.push_back((uint32_t)i);
                     a = c;
                 }
@@ -760,10 +480,11 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     const size_t npix = (size_t)cfg->width * cfg->height;
     float* d_out = out;
     if (!out_is_device) { HIP_TRY(ctx, ctx->tmp_out.ensure(npix * 4)); d_out = (float*)ctx->tmp_out.p; }
+    const TapeFacts facts = tape_facts(tape);
     // One pass over a tile list: the tile levels, then the leaf pixels (`classify_only`: the root level's fills, nothing else)
     auto pass = [&](RenderSetup& Q, const std::vector<uint32_t>& tiles, const std::vector<uint32_t>& tg) -> fhip_status {
         for (size_t i = 0; i < FH_MAX_LEVELS; i++) Q.S.P.tag[i] = i < tg.size() ? tg[i] : (uint32_t)i;
-        fhip_status ps = prepare(ctx, tape, false, tiles, PartSpec{}, Q);
+        fhip_status ps = prepare(ctx, tape, facts, false, tiles, PartSpec{}, Q);
         if (ps) return ps;
         Q.S.image2d = d_out;
         FhRenderState* dS = (FhRenderState*)ctx->state.p;
@@ -798,10 +519,7 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     // still decides is the level a fill SAYS it was decided at (pixel.rs:225-229): a leaf tile's fill is tagged with the last level, and a
     // second, classify-only pass over the root tiles writes the fills of the decided ones - level 0 - over whatever their leaf tiles
     // wrote (a decided root tile's leaf tiles are all decided the same way, so nothing else is overwritten).
-    const fh::HostTape& tt = tape->t;
-    const bool small_ok = ts.size() == 2 && tags.size() == 2 && ts[1] >= 8 && ts[0] / ts[1] <= 8 && ctx->opt.root32_max > 0 && ctx->use_split && ctx->use_asm &&
-                          !tape->tgroups.empty() && !ctx->opt.no_tape_groups && ctx->opt.prune2 && tape_asm_ok(tt) && tt.ops.size() <= FH_P2_MAX_OPS &&
-                          tt.n_choices <= FH_P2_MAX_CHOICES &&
+    const bool small_ok = ts.size() == 2 && tags.size() == 2 && ts[1] >= 8 && ts[0] / ts[1] <= 8 && ctx->opt.root32_max > 0 && linked_root_tape(facts, plan_inputs(ctx)) &&
                           (uint64_t)((P.width + ts[1] - 1) / ts[1]) * ((P.height + ts[1] - 1) / ts[1]) <= 2048u &&
                           (uint64_t)((P.width + ts[0] - 1) / ts[0]) * ((P.height + ts[0] - 1) / ts[0]) <= 64u;
     if (small_ok) {
@@ -1015,11 +733,12 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     const float ident[16] = {1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1, 0, 0, 0, 0, 1};
     fhip_screen_to_world(size, 3, s2w);
     mat_product(cfg->world_to_model ? cfg->world_to_model : ident, s2w, 4, P.mat);  // voxel.rs:107-109
-    column_setup(ctx, tape, P, R);
+    const TapeFacts facts = tape_facts(tape);
+    const PlanInputs pin = plan_inputs(ctx);
+    column_facts(P, facts, pin, R);
     // choose the tiles
-    const bool root32_tape = ctx->use_split && ctx->use_asm && !tape->tgroups.empty() && !ctx->opt.no_tape_groups && ctx->opt.prune2 && tape_asm_ok(tape->t) &&
-                             tape->t.ops.size() <= FH_P2_MAX_OPS && tape->t.n_choices <= FH_P2_MAX_CHOICES;
-    const TileChoice tiles = choose_tiles_3d(cfg->tile_sizes, cfg->n_tile_sizes, size, part.n_shards * part.nx * part.ny, part.nz, R.column_inv, ctx->opt.root32_max, ctx->opt.no_zrep, root32_tape);
+    const TileChoice tiles = choose_tiles_3d(cfg->tile_sizes, cfg->n_tile_sizes, size, part.n_shards * part.nx * part.ny, part.nz, R.column_inv, pin.root32_max, pin.no_zrep,
+                                             linked_root_tape(facts, pin));
     if (!tiles.valid) return fail(ctx, FHIP_ERR_UNSUPPORTED, "bad tile size list");
     if (tiles.substituted) ctx->substituted_tiles++;
     // pick the buffer set: a pipelined frame takes the set used longest ago
@@ -1036,10 +755,9 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
         (void)hipGetLastError();
     }
     FH_SPAN(0);
-    st = prepare(ctx, tape, true, tiles.ts, part, R);
+    st = prepare(ctx, tape, facts, true, tiles.ts, part, R);
     if (st) return st;
     FH_SPAN(1);
-    R.zrep = R.split && R.S.pre_levels > 0 && R.xy_fixed && !ctx->opt.no_column_inv && ctx->opt.no_zrep != 1;
     // schedule: every decision about streams, launches and slabs of this frame (frame_schedule.hpp)
     in.pre_turn = ctx->pre_turn;
     if (ctx->host_flags) { in.rare_seen = ctx->host_flags[2]; in.last_leaves = ctx->host_flags[3]; }

@@ -120,6 +120,30 @@ static bool tape_has_mod(const fh::HostTape& t) { return (tape_class(t) & 4) != 
 // The assembly interpreters implement every opcode except the transcendental, modulo and rng ones
 static bool tape_asm_ok(const fh::HostTape& t) { return (tape_class(t) & 2) == 0; }
 static bool tape_is_full(const fh::HostTape& t) { return (tape_class(t) & 8) != 0; }
+// The input slots a tape reads, bit per slot: found once per tape (a frame's set-up walked the tape three times for this)
+static uint32_t tape_input_slots(const fhip_tape* tape) {
+    uint32_t reads = tape->input_slots.load(std::memory_order_acquire);
+    if (reads & 0x80000000u) {          // not known yet (bit 31: input slots are < 31... FH_MAX_INPUTS)
+        reads = 0;
+        for (uint64_t w : tape->t.ops)
+            if (FH_W_OP((uint32_t)w) == FH_INPUT) reads |= 1u << ((uint32_t)(w >> 32) & 31u);
+        reads &= 0x7FFFFFFFu;
+        tape->input_slots.store(reads, std::memory_order_release);
+    }
+    return reads;
+}
+// What the frame plan needs to know of a tape (frame_plan.hpp)
+static TapeFacts tape_facts(const fhip_tape* tape) {
+    const fh::HostTape& t = tape->t;
+    TapeFacts f;
+    f.n_ops = t.ops.size(); f.n_regs = t.n_regs; f.n_choices = t.n_choices; f.n_outputs = t.n_outputs;
+    f.asm_ok = tape_asm_ok(t); f.is_full = tape_is_full(t); f.has_mod = tape_has_mod(t); f.tiles_t_ok = tape_tiles_t_ok(t);
+    f.input_slots = tape_input_slots(tape);
+    f.n_groups = (uint32_t)std::min<size_t>(tape->tgroups.size(), FH_MAX_GROUPS);
+    for (uint32_t g = 0; g < f.n_groups; g++) f.group[g] = {(uint32_t)tape->tgroups[g].ops.size(), tape->tgroups[g].n_regs, tape->tgroups[g].n_choices};
+    f.n_terms = tape->plan.n_terms; f.n_top = (uint32_t)tape->plan.top.size(); f.chain = tape->plan.chain;
+    return f;
+}
 
 static fhip_status tape_to_device(fhip_ctx* ctx, const fhip_tape* t) {
     std::lock_guard<std::mutex> guard(t->upload_lock);

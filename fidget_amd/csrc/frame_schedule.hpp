@@ -1,7 +1,8 @@
 // The schedule of a 3D frame: which stream every stage goes to, which launches exist and how the slabs are arranged - decided ONCE per
-// frame, after prepare(), by schedule_frame() below from facts alone (the frame's RenderSetup, a few options, what the context has, three
-// observations of the moment); capi_render.hpp runs it.  No HIP call, no global: this header compiles with plain g++ next to
-// render_state.h, and tests/test_frame_schedule.py pins the schedules of named frames (tests/host_build/frame_schedule_host.cpp).
+// frame by schedule_frame() below from facts alone: the frame's plan (frame_plan.hpp: the RenderSetup that plan_frame and plan_linked_prune
+// leave), a few options, what the context has, three observations of the moment; capi_render.hpp runs it.  No HIP call, no global: this
+// header compiles with plain g++ next to render_state.h, and tests/test_frame_schedule.py pins the schedules of named frames, planned by
+// the same functions the driver calls (tests/host_build/frame_schedule_host.cpp).
 // How to read one: a frame is root level -> level 1 (flags, evaluate) -> `fork_on` (flags of the parked parents, frame mark, fork of the
 // slab contexts) -> per slab: tile chain, footprint lists, leaf kernel, normals -> k_finish3d on the caller's stream.  Wherever two
 // consecutive stages have different roles there is an event between them; the edges that are not a plain hop are the fork_* / ev_pre fields.
@@ -12,124 +13,13 @@
 #include <algorithm>
 #include <vector>
 
+#include "frame_plan.hpp"
 #include "render_state.h"
 
 // register-file shapes of the VGPR tile kernels (gen_tilesv.py): registers, choices
 static const uint32_t V32_REGS = 32, V32_CHOICES = 256, V64_REGS = 64, V64_CHOICES = 512;
 // Rare mode: blocks per folded launch (a slab context's blocks keep their register files in rare_scratch: capi_render.hpp rare_file)
 static const uint32_t FH_RARE_BLOCKS = 8;
-
-struct RenderSetup {
-    FhRenderState S;
-    std::vector<FhGroup> roots;
-    uint32_t n_slabs = 1, n_layers = 1;      // z-slabs (steps of the per-slab chains), root-tile layers
-    uint32_t slab_lo = 0, slab_hi = 1;   // z-slabs this render covers (all of them unless the volume is split in z: octant shards)
-    size_t lds_tiles_mid = 0, lds_tiles_big = 0, lds_tiles_small = 0, lds_points_big = 0, lds_normals_big = 0, lds_normals_small = 0;
-    uint32_t table_words = 0, n_footprints = 0, groups_per_slab = 0;
-    bool smooth_tape = false;      // the root tape has a choice in fewer than every tenth op (and more than 200 ops): a blend whose leaves stay long
-    uint32_t hit_bucket_cap = 0;   // the normals kernel's work lists (k_hits3d): entries per bucket, words of the whole thing per slab context
-    size_t hit_words = 0;
-    size_t mind_words = 0;      // words of the min-depth pyramid (cleared at the head of the frame)
-    uint32_t tl = 16;  // sibling tiles per wave in the tile kernel (16 or 64)
-    bool full = false;  // tape uses transcendental / modulo ops -> FULL kernel variants
-    bool asm_points = false;  // leaf stage on the assembly interpreters
-    bool asm_points_t = false;  // ... on fh_columns_t (tapes with transcendental / modulo / rng opcodes)
-    bool asm_normals = false;   // normals by the assembly gradient interpreter fh_normals (gen_normals.py): footprints of leaves of <= 32 registers
-    bool split = false;       // 3D tile stage as setup / evaluate+prune / push kernels
-    bool asm_tiles = false;   // ... with the evaluate+prune step in assembly (fh_tiles)
-    bool asm_tiles_t = false; // ... by the *_t variants (transcendental opcodes)
-    uint32_t group_regs = 0, group_choices = 0;  // bounds over the tape's groups
-    size_t lds_tiles_group = 0;
-    bool groups = false;      // ... and level 0 evaluated as the tape's independent groups (tape parallelism)
-    bool prune1 = false;      // ... and, on the first exp_levels levels, the prune as one wave per child (fh_prune1)
-    bool prune2 = false;      // ... by the linked prune (prune2.hip k_prune2: visits only the ops a child keeps) where the tape qualifies
-    const uint64_t* d_links = nullptr;
-    const uint64_t* d_ctab = nullptr;
-    size_t lds_prune2 = 0;
-    uint32_t n_chain = 0;          // ops of the root chain (their table lies behind d_ctab's t.n_choices entries)
-    uint32_t p2_cap_kept = 0;      // kept ops per child the linked prune's LDS areas are sized for (children beyond: the scalar sweep behind it)
-    uint32_t exp_levels = 0;
-    uint32_t col_slots = 0, col_depmask = 0, col_flags = 0;   // 3D: axis slots x | y << 8 | z << 16 (0xFF none), inputs varying along a pixel column, bit 16 projective
-    bool zrep = false;        // ... column-invariant parents are evaluated for one z-layer only (k_tape_flags)
-    bool xy_fixed = false, root_invariant = false;   // 3D, set before prepare(): x and y do not move along a pixel column; the ROOT tape reads nothing that does
-    // ... both, and the short cut is on (option no_zrep 0 or 3): no tape of the frame reads anything that changes along a pixel column, so at most
-    // one leaf per pixel column and slab.  Computed HERE ONLY (column_setup); read by the tile choice, by prepare() (root_zrep) and by the schedule
-    bool column_inv = false;
-    bool one_level_64 = false;   // 2D, a one-level list: root groups of 64 tiles through the split tile stage (render2d_frame's small-image passes)
-    bool classify_only = false;  // ... and the pass that only classifies its tiles and writes their fills (no prune, no leaves)
-    bool root_zrep = false;   // ... then the root level evaluates ONE layer of root tiles per z-slab and hands the result to the layers stacked on it
-    bool front_only = false;  // ... and only the front slab is rendered (slab_stop = slab_hi - 1)
-    uint32_t slab_stop = 0;   // the slabs rendered: slab_hi - 1 down to slab_stop (= slab_lo unless front_only)
-    bool big_hbm = false;     // the root-sized register files live in HBM (S.gscratch): hbm_waves workgroups per root-sized launch
-    uint32_t hbm_waves = 0;
-};
-
-// ---- the tile list of a 3D frame ----------------------------------------------------------------------------------------
-static const uint32_t VM_TILES_3D[] = {128, 64, 32, 16, 8};  // fidget-core/src/vm/mod.rs:251-253
-// fidget-raster/src/lib.rs:59-66
-static std::vector<uint32_t> trim_tiles(const uint32_t* tiles, uint32_t n, uint32_t max_size) {
-    uint32_t i = n;
-    for (uint32_t k = 0; k < n; k++) if (tiles[k] < max_size) { i = k; break; }
-    i = i ? i - 1 : 0;
-    return std::vector<uint32_t>(tiles + i, tiles + n);
-}
-// RenderHints of the HIP shape (the reference lets every shape type pick its own, shape.rs RenderHints): a fan-out of 4^3 = 64 children
-// fills a wavefront (128 -> 32 -> 8).  The root tile stays the one the reference's VmShape hints give for the image size, so that exactly
-// the same voxels are covered (a root tile overhanging the image in z is evaluated there by the reference too).
-static std::vector<uint32_t> hip_tiles_3d(uint32_t max_size) {
-    std::vector<uint32_t> v = trim_tiles(VM_TILES_3D, 5, max_size);
-    std::vector<uint32_t> out{v[0]};
-    for (uint32_t t = v[0]; t > 8;) { t = std::max<uint32_t>(t / 4, 8); out.push_back(t); }
-    return out;
-}
-// valid = false: the caller's list is not one the reference accepts; substituted: it is, but not one the kernels take - rendered with the library's
-struct TileChoice { std::vector<uint32_t> ts; bool valid = true, substituted = false; };
-// The caller's list (or null) for an image of `size`; columns_split, nz: parts of a frame - n_shards * nx * ny, nz (1, 1: a whole frame); column_inv:
-// RenderSetup::column_inv; the options; root32_tape: split + assembly on, and the tape is one the groups + linked prune path takes
-static TileChoice choose_tiles_3d(const uint32_t* tile_sizes, uint32_t n_tile_sizes, const uint32_t (&size)[3], uint32_t columns_split, uint32_t nz, bool column_inv,
-                                  int root32_max, int no_zrep, bool root32_tape) {
-    const uint32_t width = size[0], height = size[1], depth = size[2];
-    TileChoice T;
-    const uint32_t image = std::max(width, height);
-    T.ts = tile_sizes ? trim_tiles(tile_sizes, n_tile_sizes, image) : hip_tiles_3d(image);
-    bool own_tiles = !tile_sizes;
-    if (tile_sizes) {
-        // Any list the reference accepts (TileSizes::new, fidget-core/src/render/mod.rs:181-251: descending, each a multiple of the next;
-        // fidget-jit's own hint is [64, 16, 8], a caller's [64, 16, 4] is valid there) is accepted here: what the device's kernels cannot
-        // take as given - leaves other than 8^3 (one 8 x 8 footprint per wavefront), a fan-out above 64 children (one per lane) - is
-        // rendered with the library's list instead.  A 3D image does not depend on the tile sizes, so the caller
-        // cannot tell, except by the time; fhip_render_counters out[7] counts such frames.
-        T.valid = n_tile_sizes >= 1 && tile_sizes[n_tile_sizes - 1] >= 1;
-        for (uint32_t i = 1; i < n_tile_sizes && T.valid; i++)
-            T.valid = tile_sizes[i - 1] > tile_sizes[i] && tile_sizes[i] > 0 && tile_sizes[i - 1] % tile_sizes[i] == 0;
-        if (!T.valid) return T;
-        bool native = T.ts.back() == 8 && T.ts.size() <= FH_MAX_LEVELS;
-        for (size_t i = 1; i < T.ts.size() && native; i++) { const uint32_t n = T.ts[i - 1] / T.ts[i]; native = n * n * n <= 64; }
-        if (!native) { T.ts = hip_tiles_3d(image); own_tiles = T.substituted = true; }
-    }
-    // Few tiles, long tape (a small image, a part of a frame on one rank of several, a model without z): root tiles of 32^3 straight
-    // above the leaves.  With 128^3 root tiles such a frame is a handful of one-wave chains over tapes that a 128^3 tile barely prunes
-    // (prospero.vm at 512^3: a root tile keeps up to 1 795 of 6 363 ops - beyond the linked prune's and fh_tiles_v64's limits, so the
-    // LDS-file kernel and the scalar sweep walk them: 3.3 ms for one frame).  The root level's forward pass is parallel over the tape
-    // (term groups) however many tiles there are, and the linked prune handles a thousand children in one round, each a wave: pruning
-    // the ROOT tape per 32^3 tile costs what pruning it per 128^3 tile costs, its tapes are what level 1 would have arrived at, and
-    // level 1 - the longest kernel of the frame - is not run at all: 512^3 3.25 -> 1.45 ms alone.  A 3D image does not depend on the
-    // tile sizes, so this is the library's choice whenever the caller gave none: taken while the root level has at
-    // most `root32_max` children - counting one layer per z-slab when the root tape reads nothing that changes along a pixel column
-    // (root_zrep, prepare) - and the tape is one the groups + linked prune path takes.
-    if (own_tiles && root32_max > 0 && T.ts.size() == 3 && T.ts[0] == 128 && root32_tape) {
-        const uint64_t cols = (uint64_t)((width + 31) / 32) * ((height + 31) / 32) / std::max<uint32_t>(1, columns_split);
-        const uint64_t layers = column_inv ? (no_zrep == 0 ? 1u : (uint64_t)std::max<uint32_t>(2, (depth + 511) / 512))      // (one layer per slab; the front slab only)
-                                             : (uint64_t)((depth + 31) / 32) / std::max<uint32_t>(1, nz);
-        // (measured, profiles/r05c: up to two rounds of the linked prune's workgroups - 2 048 children - always; up to root32_max when a
-        // 128^3 root tile is a quarter of the image or more - there the 128^3 tiles' tapes stay long whatever is done: 512^3 with z in
-        // every tape, 4 096 children, 3.65 -> 1.72 ms; an octant of a 1024^3 frame, as many children of a model twice the size: 1.10 -> 1.33)
-        const uint64_t children = cols * std::max<uint64_t>(layers, 1);
-        if ((children <= 2048 || (children <= (uint64_t)root32_max && image <= 512)) && (depth + 31) / 32 <= FH_MAX_SLABS)
-            T.ts = {32, 8};
-    }
-    return T;
-}
 
 // ---- the schedule ----------------------------------------------------------------------------------------------------------
 // Which stream of the context: the caller's, the pre-pass stream, the side stream (high priority), the tail stream

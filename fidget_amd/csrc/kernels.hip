@@ -30,7 +30,6 @@
 
 using namespace fhd;
 
-#define WAVE 64
 #define AS4 __attribute__((address_space(4)))
 typedef const AS4 uint64_t* ctape_t;  // constant address space => scalar (SMEM) loads
 
@@ -314,10 +313,7 @@ FH_DEV void prune_sweep(ctape_t tape, uint32_t len, uint32_t n_choices, const ui
     out_choices = kept_choices;
 }
 
-// Small tapes (the overwhelming majority below the root levels) run with a small LDS
-// budget so that many waves fit per CU; the rest use the root tape's bounds.
-#define SMALL_REGS 32u
-#define SMALL_CHOICES 256u
+// Small tapes (render_state.h SMALL_REGS / SMALL_CHOICES)
 FH_DEV bool tape_is_small(const FhTapeRef& t) { return t.n_regs <= SMALL_REGS && t.n_choices <= SMALL_CHOICES; }
 
 // The tile kernel: interval-evaluate the children of one parent tile per wave, classify

@@ -41,12 +41,9 @@
 
 #include "render_state.h"
 
-#define FH_P2_WPB 4                                             // children per workgroup (they share the root chain's table in LDS)
+// (FH_P2_WPB children per workgroup, the limits FH_P2_MAX_OPS / _CHOICES / _KEPT and fh_p2_wave_lds: render_state.h, the host's frame plan reads them too)
 #define FH_P2_WPC 4                                             // waves per child (the phases that are parallel over the tape; B1 and B3 are one wave's)
 #define FH_P2_PER_SLOT ((64 + FH_P2_WPB - 1) / FH_P2_WPB)      // ... workgroups per slot (the last one's spare waves idle)
-#define FH_P2_MAX_OPS 8192u
-#define FH_P2_MAX_CHOICES 4096u
-#define FH_P2_MAX_KEPT 1280u                                    // (four children's areas: 104 KB of the CU's 160)
 // op classes of a link
 enum { FH_LK_OUT = 0, FH_LK_NONE = 1, FH_LK_A = 2, FH_LK_RR = 3, FH_LK_COPY = 4, FH_LK_CRR = 5, FH_LK_CRI = 6 };
 // Link of an op, 8 bytes: word 0 = opcode | class << 8 | choice ordinal << 16, word 1 = fa | fb << 16: the producers of operands a and
@@ -55,12 +52,6 @@ enum { FH_LK_OUT = 0, FH_LK_NONE = 1, FH_LK_A = 2, FH_LK_RR = 3, FH_LK_COPY = 4,
 // its index | class << 16.
 #define FH_LK_CHOICE 0x8000u
 #define FH_LK_IMM 0x4000u        // E: the choice's value is its immediate (reg,imm op decided Right): the op stays, as COPY_IMM
-
-// bytes of LDS per wave: wanted-op mask (128 x 8), position prefixes (128 x 2), E (2 per choice), kept-op records (8 each), last
-// uses (4 each), registers by position (1 each; 2 spare bytes each)
-static inline __host__ __device__ size_t fh_p2_wave_lds(uint32_t n_choices, uint32_t cap_kept = FH_P2_MAX_KEPT) {
-    return 1024 + 256 + (((size_t)n_choices * 2 + 15) & ~(size_t)15) + (size_t)cap_kept * (8 + 4 + 1 + 2) + 64;       // (the last 64: FH_P2_WPC waves' shared words)
-}
 
 namespace fhp2 {
 __device__ __forceinline__ uint32_t rfl(uint32_t v) { return __builtin_amdgcn_readfirstlane(v); }

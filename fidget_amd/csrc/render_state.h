@@ -1,14 +1,39 @@
 // Device-resident state of one render, shared by the host driver (capi.hip) and the
 // kernels.  Plain C structs; all device pointers.
 #pragma once
+#include <stddef.h>
 #include <stdint.h>
 
 #include "tape_format.h"
 
+#if defined(__HIPCC__)
+#define FH_HOST_DEVICE __host__ __device__
+#else
+#define FH_HOST_DEVICE
+#endif
+
+#define WAVE 64
+#define FH_LDS_MAX 163840  // 160 KiB per workgroup on gfx950
 #define FH_MAX_LEVELS 8
 #define FH_MAX_INPUTS 16
 #define FH_MAX_SLABS 64
 #define FH_MAX_GROUPS 32  // independent sub-tapes of a root min / max (tape parallelism at level 0): at most; FHIP_GROUPS when a tape is built
+
+// Small tapes (the overwhelming majority below the root levels) run with a small LDS
+// budget so that many waves fit per CU; the rest use the root tape's bounds.
+#define SMALL_REGS 32u
+#define SMALL_CHOICES 256u
+// The linked prune of the root level (prune2.hip): children per workgroup (they share the root chain's table in LDS), the parent tapes it
+// takes, the kept ops per child its LDS areas hold (four children's areas: 104 KB of the CU's 160)
+#define FH_P2_WPB 4
+#define FH_P2_MAX_OPS 8192u
+#define FH_P2_MAX_CHOICES 4096u
+#define FH_P2_MAX_KEPT 1280u
+// ... and its bytes of LDS per wave: wanted-op mask (128 x 8), position prefixes (128 x 2), E (2 per choice), kept-op records (8 each), last
+// uses (4 each), registers by position (1 each; 2 spare bytes each)
+static inline FH_HOST_DEVICE size_t fh_p2_wave_lds(uint32_t n_choices, uint32_t cap_kept = FH_P2_MAX_KEPT) {
+    return 1024 + 256 + (((size_t)n_choices * 2 + 15) & ~(size_t)15) + (size_t)cap_kept * (8 + 4 + 1 + 2) + 64;       // (the last 64: FH_P2_WPC waves' shared words)
+}
 
 // One wave's worth of interval work: a parent tile (or, at level 0, a run of root tiles)
 // together with the tape that evaluates its children.

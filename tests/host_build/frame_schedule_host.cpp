@@ -1,7 +1,9 @@
 // Host build of the 3D frame schedule (fidget_amd/csrc/frame_schedule.hpp: no HIP, no device) for tests/test_frame_schedule.py:
-// fills the facts of named frames - the part of prepare()'s arithmetic the schedule reads, for a tape of prospero.vm's kind (every
-// assembly path on, term groups, linked prune) - and prints their schedules, one line each; then a sweep for the edge property.
+// plans named frames as the driver does (frame_plan.hpp: column_facts, choose_tiles_3d, plan_frame, plan_linked_prune) for a tape of
+// prospero.vm's kind (every assembly path on, term groups, linked prune) and prints their schedules, one line each; then a sweep for
+// the edge property.
 #include <stdio.h>
+#include <stdlib.h>
 #include <string.h>
 
 #include <string>
@@ -14,40 +16,33 @@ struct Case {
     ScheduleInputs in;
 };
 
-// What column_setup + choose_tiles_3d + prepare leave in a RenderSetup for a size^3 frame of a tape that reads no z (camera: identity)
+// A tape of prospero.vm's kind: 6363 ops, 72 registers, 3000 choices, reads x and y only; term groups, links and a root chain present
+static TapeFacts prospero_kind() {
+    TapeFacts t;
+    t.n_ops = 6363; t.n_regs = 72; t.n_choices = 3000;
+    t.input_slots = 3;
+    t.n_groups = 16;
+    for (uint32_t g = 0; g < t.n_groups; g++) t.group[g] = {400, 40, 190};
+    t.n_terms = 64; t.n_top = 63; t.chain = true;
+    return t;
+}
+// What the driver leaves in a RenderSetup for a size^3 frame of that tape (camera: identity; x, y, z on slots 0, 1, 2): render3d_frame's steps
 static RenderSetup facts(const Case& c) {
+    const TapeFacts t = prospero_kind();
+    PlanInputs pin;
+    pin.no_column_inv = c.no_column_inv; pin.no_zrep = c.no_zrep;
     RenderSetup R;
     memset(&R.S, 0, sizeof(R.S));
     FhRender& P = R.S.P;
     P.width = P.height = P.depth = c.size;
-    R.xy_fixed = true; R.root_invariant = !c.no_column_inv;
-    R.column_inv = R.xy_fixed && R.root_invariant && (c.no_zrep == 0 || c.no_zrep == 3);
+    for (int i = 0; i < 4; i++) P.mat[5 * i] = 1.0f;
+    for (uint32_t s = 0; s < FH_MAX_INPUTS; s++) P.in_kind[s] = s < 3 ? s : 3;
+    column_facts(P, t, pin, R);
     const uint32_t size[3] = {c.size, c.size, c.size};
-    const TileChoice T = choose_tiles_3d(nullptr, 0, size, 1, 1, R.column_inv, 4096, c.no_zrep, true);
-    const std::vector<uint32_t>& ts = T.ts;
-    P.n_levels = (uint32_t)ts.size();
-    for (size_t i = 0; i < ts.size(); i++) P.tiles[i] = ts[i];
-    P.max_regs = 72; P.max_choices = 3000;
-    P.roots_x = P.roots_y = (c.size + ts[0] - 1) / ts[0];
-    const uint32_t n_layers = (c.size + ts[0] - 1) / ts[0];
-    const bool prepass_ok = ts.size() >= 2 && n_layers <= FH_MAX_SLABS;
-    uint32_t SL = prepass_ok ? 4 * std::max<uint32_t>(1, 128 / ts[0]) : 1u;      // (option slab_layers = 4; as prepare())
-    while (SL > 1 && (ts[0] * SL / 8 > 64 || SL * 2 > n_layers)) SL >>= 1;
-    P.slab = ts[0] * SL;
-    R.n_slabs = (c.size + P.slab - 1) / P.slab; R.n_layers = n_layers;
-    R.S.pre_levels = prepass_ok ? std::min<uint32_t>(2, (uint32_t)ts.size() - 1) : 0;
-    R.slab_lo = 0; R.slab_hi = prepass_ok ? (n_layers + SL - 1) / SL : n_layers;
-    R.tl = 64; R.split = R.asm_tiles = R.asm_points = R.asm_normals = R.prune1 = R.groups = R.prune2 = true;
-    R.exp_levels = std::min(R.S.pre_levels, 1u);
-    R.root_zrep = R.S.pre_levels > 0 && R.column_inv;
-    R.front_only = R.root_zrep && c.no_zrep == 0;
-    R.slab_stop = R.front_only ? R.slab_hi - 1 : R.slab_lo;
-    R.groups_per_slab = (P.roots_x * P.roots_y + 63) / 64;
-    R.n_footprints = ((c.size + 7) / 8) * ((c.size + 7) / 8);
-    R.table_words = R.n_footprints * (P.slab / 8);
-    R.zrep = R.split && R.S.pre_levels > 0 && R.xy_fixed && !c.no_column_inv && c.no_zrep != 1;
-    R.lds_tiles_big = 89856; R.lds_tiles_mid = 46336; R.lds_tiles_small = 20736; R.lds_points_big = 72 * 64 * 4; R.lds_normals_big = 72 * 64 * 16; R.lds_normals_small = 32 * 64 * 16;
-    R.S.leaf_asm_regs = 40; R.S.norm_asm_regs = 40;
+    const TileChoice T = choose_tiles_3d(nullptr, 0, size, 1, 1, R.column_inv, pin.root32_max, pin.no_zrep, linked_root_tape(t, pin));
+    const PlanStatus ps = plan_frame(t, pin, true, T.ts, PartSpec{}, R);
+    if (ps.status) { fprintf(stderr, "plan refused: %s\n", ps.msg); exit(2); }
+    if (R.groups) plan_linked_prune(t, pin, true, 63, R);
     return R;
 }
 static ScheduleInputs inputs(const Case& c) {

@@ -18,7 +18,7 @@ def schedules():
     out = os.path.join(ROOT, "tests", "host_build", "_build")
     os.makedirs(out, exist_ok=True)
     exe = os.path.join(out, "frame_schedule_host")
-    deps = [SRC] + [os.path.join(CSRC, f) for f in ("frame_schedule.hpp", "render_state.h", "tape_format.h")]
+    deps = [SRC] + [os.path.join(CSRC, f) for f in ("frame_schedule.hpp", "frame_plan.hpp", "render_state.h", "tape_format.h")]
     if not os.path.exists(exe) or any(os.path.getmtime(d) > os.path.getmtime(exe) for d in deps):
         # (plain g++, no HIP headers: the schedule touches no device)
         subprocess.check_call(["g++", "-std=c++17", "-O1", "-Wall", "-Wno-unused-function", "-I", CSRC, SRC, "-o", exe])

@@ -36,4 +36,5 @@ def test_hash_covers_the_render_path_only(tmp_path):
     assert edited("capi_core.hpp", b"FH_ASM_COLUMNS", b"FH_ASM_COLUMNZ") != base
     assert edited("capi_render.hpp", b"upload_frame", b"upload_framf") != base
     assert edited("frame_schedule.hpp", b"schedule_frame", b"schedule_framf") != base
+    assert edited("frame_plan.hpp", b"plan_frame", b"plan_framf") != base
     assert b"fhip_status fhip_mesh_build(" in (dst / "capi_mesh.hpp").read_bytes()
