@@ -23,6 +23,9 @@
 //                 put together in LDS and stored as whole dwords;
 //   k_vox_full / k_vox_leaves / k_vox_slices / k_vox_layer_counts   the inside voxels themselves (fhip_shape_voxels): the octree of occupancy
 //                 written down as a bitmap of 4 x 4 x 4 bricks, and what is made of the bitmap - layer images, voxels per layer;
+//   k_ctr_edges / k_ctr_vertices / k_ctr_cells / k_ctr_segments   the outlines of a 2D slice (fhip_contour2d): marching squares over the
+//                 pixel-perfect distance image render2d leaves in device memory - vertices on the crossing lattice edges, directed segments,
+//                 the link array (contour/contour.hpp);
 //   k_mesh_vertex_grads   the tape's value and gradient at every vertex of a mesh (VmGradSliceEval::eval, vm/mod.rs:1091-1397): one
 //                 vertex per lane, read from the V3 array where the dual walk left it.
 #pragma once
@@ -34,6 +37,7 @@
 #include "mesh_edges.hpp"
 #include "mesh_qef.hpp"
 #include "mesh_vox.hpp"
+#include "contour/contour.hpp"
 // (included by capi.hip after kernels.hip: Regs, step, ballot, uni, ctape_t)
 
 struct FhMeshParams {
@@ -920,5 +924,108 @@ __global__ void __launch_bounds__(256) k_vox_layer_sum(const uint64_t* __restric
     uint64_t s = 0;
     for (uint32_t p = 0; p < n_parts; p++) s += parts[((uint64_t)(k >> 2) * n_parts + p) * 4 + (k & 3)];
     out[k] = s;
+}
+
+// ---- contours of a 2D slice: marching squares over the f32 distance image of a pixel-perfect render2d (contour/contour.hpp) -------------
+// Four passes over the image and nothing else: every kernel takes the image and its size, plus what the passes before it left.  A block
+// of 256 threads takes 256 consecutive lattice edges (cells) at a time and the blocks stride over them, so the grid is bounded.  Edges
+// and cells are numbered along rows: the lanes of a wave read consecutive pixels of a row (broken where a row ends), and the second end
+// of a vertical edge, the upper corners of a cell, are the same reads one row on - lines the pass has just brought into L2.  Every word
+// written has one writer - a ballot word by lane 0 of its wave, a vertex by its edge, a segment by its cell, next[from] by the one
+// segment that leaves `from` - so the stores are plain vector stores and the result is the same in any order.
+constexpr uint32_t FH_CTR_BLOCKS = 4096;
+static_assert(fhctr::EDGE_BLOCK == 256 && WAVE == 64, "k_ctr_*: a block of 256 threads is four ballot words");
+
+// Which edges cross: bits[e / 64] bit e % 64, and per block of 256 edges their number (the scan of these gives every crossing edge its
+// vertex id, fhctr::vertex_id).  Edges beyond the last pad their word with zeros.
+__global__ void __launch_bounds__(256) k_ctr_edges(const float* __restrict__ img, uint32_t W, uint32_t H, uint64_t* __restrict__ bits, uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t part[256 / WAVE];
+    const uint64_t E = fhctr::n_edges(W, H);
+    const uint32_t n_blk = (uint32_t)((E + 255) / 256), lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    for (uint32_t blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+        const uint64_t e = (uint64_t)blk * 256 + threadIdx.x;
+        bool cross = false;
+        if (e < E) {
+            const fhctr::Edge ed = fhctr::edge_at((uint32_t)e, W, H);
+            cross = fhctr::inside(img[fhctr::edge_pixel0(ed, W)]) != fhctr::inside(img[fhctr::edge_pixel1(ed, W)]);
+        }
+        const uint64_t m = ballot(cross);
+        if (lane == 0) { bits[(size_t)blk * 4 + wv] = m; part[wv] = (uint32_t)__popcll(m); }
+        __syncthreads();
+        if (threadIdx.x == 0) cnt[blk] = part[0] + part[1] + part[2] + part[3];
+        __syncthreads();
+    }
+}
+
+// One float2 per crossing edge, and its link cleared.  A wave whose ballot word is zero - nearly all of them - reads that word and
+// nothing else.  (A lane per ballot word walking its set bits was measured and lost: 21 against 7.6 us at 1024^2, 42 against 49 at
+// 4096^2 - the lanes of a wave that do have crossings then work through them one after the other.)
+__global__ void __launch_bounds__(256) k_ctr_vertices(const float* __restrict__ img, uint32_t W, uint32_t H, const uint64_t* __restrict__ bits,
+                                                      const uint32_t* __restrict__ block_off, float2* __restrict__ verts, uint32_t* __restrict__ next) {
+    const uint64_t E = fhctr::n_edges(W, H);
+    const uint32_t n_blk = (uint32_t)((E + 255) / 256);
+    for (uint32_t blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+        const uint64_t e64 = (uint64_t)blk * 256 + threadIdx.x;
+        if (e64 >= E) continue;
+        const uint32_t e = (uint32_t)e64;
+        if (!fhctr::edge_crosses(bits, e)) continue;
+        const fhctr::Edge ed = fhctr::edge_at(e, W, H);
+        float xy[2];
+        fhctr::edge_vertex(ed, img[fhctr::edge_pixel0(ed, W)], img[fhctr::edge_pixel1(ed, W)], xy);
+        const uint32_t id = fhctr::vertex_id(bits, block_off, e);
+        verts[id] = make_float2(xy[0], xy[1]);
+        next[id] = fhctr::NONE;
+    }
+}
+
+// The case of cell c (its segments, packed: fhctr::cell_case), 0 beyond the last cell
+FH_DEV uint32_t ctr_cell_case(const float* __restrict__ img, uint32_t W, uint64_t c, uint64_t n_cells, uint32_t& i, uint32_t& j) {
+    i = j = 0;
+    if (c >= n_cells) return 0u;
+    j = (uint32_t)c / (W - 1); i = (uint32_t)c - j * (W - 1);
+    const float* const p = img + (size_t)j * W + i;
+    const float v00 = p[0], v10 = p[1], v01 = p[W], v11 = p[W + 1];
+    return fhctr::cell_case(fhctr::cell_mask(v00, v10, v11, v01), fhctr::saddle_centre_inside(v00, v10, v11, v01));
+}
+// Segments per block of 256 cells (0, 1 or 2 a cell: two ballots)
+__global__ void __launch_bounds__(256) k_ctr_cells(const float* __restrict__ img, uint32_t W, uint32_t H, uint32_t* __restrict__ cnt) {
+    __shared__ uint32_t part[256 / WAVE];
+    const uint64_t NC = fhctr::n_cells(W, H);
+    const uint32_t n_blk = (uint32_t)((NC + 255) / 256), lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    for (uint32_t blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+        uint32_t i, j;
+        const uint32_t n = fhctr::case_count(ctr_cell_case(img, W, (uint64_t)blk * 256 + threadIdx.x, NC, i, j));
+        const uint32_t s = (uint32_t)__popcll(ballot(n >= 1)) + (uint32_t)__popcll(ballot(n == 2));
+        if (lane == 0) part[wv] = s;
+        __syncthreads();
+        if (threadIdx.x == 0) cnt[blk] = part[0] + part[1] + part[2] + part[3];
+        __syncthreads();
+    }
+}
+// The segments, in cell order: block_off of the cell counts, the waves before this one through LDS, the lanes before this one from the
+// two ballots.  The ids of a segment's two edges come from the edge pass (fhctr::vertex_id); next[from] = to.
+__global__ void __launch_bounds__(256) k_ctr_segments(const float* __restrict__ img, uint32_t W, uint32_t H, const uint64_t* __restrict__ bits,
+                                                      const uint32_t* __restrict__ edge_off, const uint32_t* __restrict__ cell_off, uint2* __restrict__ segs,
+                                                      uint32_t* __restrict__ next) {
+    __shared__ uint32_t part[256 / WAVE];
+    const uint64_t NC = fhctr::n_cells(W, H);
+    const uint32_t n_blk = (uint32_t)((NC + 255) / 256), lane = threadIdx.x & (WAVE - 1), wv = threadIdx.x / WAVE;
+    const uint64_t below = ((uint64_t)1 << lane) - 1;
+    for (uint32_t blk = blockIdx.x; blk < n_blk; blk += gridDim.x) {
+        uint32_t i, j;
+        const uint32_t cs = ctr_cell_case(img, W, (uint64_t)blk * 256 + threadIdx.x, NC, i, j), n = fhctr::case_count(cs);
+        const uint64_t b1 = ballot(n >= 1), b2 = ballot(n == 2);
+        if (lane == 0) part[wv] = (uint32_t)__popcll(b1) + (uint32_t)__popcll(b2);
+        __syncthreads();
+        uint32_t at = cell_off[blk] + (uint32_t)__popcll(b1 & below) + (uint32_t)__popcll(b2 & below);
+        for (uint32_t k = 0; k < wv; k++) at += part[k];
+        for (uint32_t s = 0; s < n; s++) {
+            const uint32_t from = fhctr::vertex_id(bits, edge_off, fhctr::cell_edge(fhctr::case_from(cs, s), i, j, W, H));
+            const uint32_t to = fhctr::vertex_id(bits, edge_off, fhctr::cell_edge(fhctr::case_to(cs, s), i, j, W, H));
+            segs[at + s] = make_uint2(from, to);
+            next[from] = to;
+        }
+        __syncthreads();
+    }
 }
 }  // namespace fhm

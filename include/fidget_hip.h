@@ -382,6 +382,42 @@ fhip_status fhip_shape_voxels(fhip_ctx* ctx, const fhip_tape* tape, uint32_t dep
 fhip_status fhip_voxels_slices(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint32_t k0, uint32_t k1, uint8_t* out, int on_device);
 fhip_status fhip_voxels_layer_counts(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint64_t* out, int on_device);
 
+/* ---- contours of a 2D slice: the outlines of the shape's cross-section at cfg->z, by marching squares ----------
+ * The image is the PIXEL-PERFECT fhip_render2d image of `cfg` (size, z, world_to_model, variables, axis slots; cfg->pixel_perfect is
+ * taken as 1): v[j * W + i], `inside` = v < 0, so NaN is outside.  Coordinates are pixel units: the centre of pixel (i, j) is the point
+ * (float(i), float(j)).
+ * Lattice edges, in index order: horizontal h(i, j) from (i, j) to (i + 1, j), 0 <= i < W - 1, 0 <= j < H, index j * (W - 1) + i; then
+ * vertical u(i, j) from (i, j) to (i, j + 1), 0 <= i < W, 0 <= j < H - 1, index (W - 1) * H + j * W + i.  An edge crosses when `inside`
+ * differs at its ends, and vertex k sits on the k-th crossing edge: with a, b the values at its first and other end,
+ * t = a / (a - b) in f32 (t = 0.5 unless 0 <= t <= 1: NaN and infinite ends), at (float(i) + t, float(j)) or (float(i), float(j) + t).
+ * Cell c(i, j), 0 <= i < W - 1, 0 <= j < H - 1, in the order j * (W - 1) + i, has the mask bit 0 in(i, j), 1 in(i + 1, j),
+ * 2 in(i + 1, j + 1), 3 in(i, j + 1) and the edges B = h(i, j), R = u(i + 1, j), T = h(i, j + 1), L = u(i, j).  Its segments are pairs
+ * of vertex ids {from, to}, the inside on their left (x to the right, j upward):
+ *   1 B-L   2 R-B   4 T-R   8 L-T   3 R-L   6 T-B   14 L-B   13 B-R   11 R-T   7 T-L   12 L-R   9 B-T   (0, 15: none)
+ *   5: B-R, T-L when ((v00 + v10) + (v11 + v01)) * 0.25f < 0, else B-L, T-R;   10: L-B, R-T when it is, else R-B, L-T
+ * in cell order, a saddle's two in the order written.  next[k] is the `to` of the one segment with `from` k, 0xFFFFFFFF where there is
+ * none (only on the image's border); no vertex has more than one segment leaving or arriving.  With W < 2 or H < 2 there are no cells,
+ * so no segments: what is left is the crossing edges of the single row or column, vertices nothing joins; W or H = 0 gives no vertices.
+ * fhip_contour2d: blocking.  The frame and four passes over it run on the context's stream; two totals come back to size the arrays;
+ * vertices, segments and next stay in device memory, owned by the result.  Statuses as fhip_render2d's (FHIP_ERR_MISSING_VAR before
+ * any launch); W * H or the number of edges at 2^32 or above is FHIP_ERR_UNSUPPORTED.
+ * fhip_contours_counts: {vertices, segments, W, H}.  _vertices (2 floats each), _segments (2 ids each), _next (one id per vertex) copy
+ * to host buffers of the caller's; _vertices_dev / _segments_dev are the device arrays (NULL when empty), valid until fhip_contours_free.
+ * fhip_contour_loops: host only, no GPU call.  Follows next[0 .. n - 1] into chains of vertex ids: open chains first - from the
+ * vertices no segment arrives at, in ascending order - then closed loops, each from its smallest id, in ascending order of that.
+ * order: n ids; loop_start: n_loops + 1 offsets into it (at most n + 1); closed: n_loops flags (at most n); each may be NULL - call
+ * once for *n_loops, then again.  FHIP_ERR_UNSUPPORTED: not a link array (an id >= n, two segments arriving at one vertex). */
+/* (the result's handle, a `fhip_contours`, is declared void* here, as fhip_shape_occupancy's `out` is) */
+fhip_status fhip_contour2d(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render2d_config* cfg, void** out);
+void fhip_contours_counts(const void* contours, uint64_t out[4]);
+fhip_status fhip_contours_vertices(const void* contours, float* out);
+fhip_status fhip_contours_segments(const void* contours, uint32_t* out);
+fhip_status fhip_contours_next(const void* contours, uint32_t* out);
+const float* fhip_contours_vertices_dev(const void* contours);
+const uint32_t* fhip_contours_segments_dev(const void* contours);
+void fhip_contours_free(void* contours);
+fhip_status fhip_contour_loops(const uint32_t* next, uint64_t n, uint32_t* order, uint64_t* loop_start, uint8_t* closed, uint64_t* n_loops);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

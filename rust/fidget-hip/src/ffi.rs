@@ -129,6 +129,16 @@ extern "C" {
                              cells: *mut u64) -> fhip_status;
     pub fn fhip_voxels_slices(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, k0: u32, k1: u32, out: *mut u8, on_device: c_int) -> fhip_status;
     pub fn fhip_voxels_layer_counts(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, out: *mut u64, on_device: c_int) -> fhip_status;
+    // the outlines of a 2D slice (marching squares over the pixel-perfect render2d image); the handle - a `fhip_contours` - is void* in the header
+    pub fn fhip_contour2d(ctx: *mut fhip_ctx, tape: *const fhip_tape, cfg: *const fhip_render2d_config, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_contours_counts(contours: *const c_void, out: *mut u64);         // vertices, segments, W, H
+    pub fn fhip_contours_vertices(contours: *const c_void, out: *mut f32) -> fhip_status;
+    pub fn fhip_contours_segments(contours: *const c_void, out: *mut u32) -> fhip_status;
+    pub fn fhip_contours_next(contours: *const c_void, out: *mut u32) -> fhip_status;
+    pub fn fhip_contours_vertices_dev(contours: *const c_void) -> *const f32;
+    pub fn fhip_contours_segments_dev(contours: *const c_void) -> *const u32;
+    pub fn fhip_contours_free(contours: *mut c_void);
+    pub fn fhip_contour_loops(next: *const u32, n: u64, order: *mut u32, loop_start: *mut u64, closed: *mut u8, n_loops: *mut u64) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,
