@@ -25,7 +25,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -54,6 +54,7 @@ EXPORTS = [
     "fhip_tape_var_count", "fhip_tape_output_count", "fhip_tape_ops", "fhip_simplify", "fhip_interval_eval",
     "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads", "fhip_shape_occupancy", "fhip_voxels_words", "fhip_shape_voxels", "fhip_voxels_slices", "fhip_voxels_layer_counts",
     "fhip_contour2d", "fhip_contours_counts", "fhip_contours_vertices", "fhip_contours_segments", "fhip_contours_next", "fhip_contours_vertices_dev", "fhip_contours_segments_dev", "fhip_contours_free", "fhip_contour_loops",
+    "fhip_voxels_components", "fhip_components_counts", "fhip_components_table", "fhip_components_label_slices", "fhip_components_extract", "fhip_components_free",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -185,6 +186,9 @@ def lib():
             "fhip_contour2d": (i32, [vp, vp, vp, vp]), "fhip_contours_counts": (None, [vp, vp]), "fhip_contours_vertices": (i32, [vp, vp]),
             "fhip_contours_segments": (i32, [vp, vp]), "fhip_contours_next": (i32, [vp, vp]), "fhip_contours_vertices_dev": (vp, [vp]),
             "fhip_contours_segments_dev": (vp, [vp]), "fhip_contours_free": (None, [vp]), "fhip_contour_loops": (i32, [vp, u64, vp, vp, vp, vp]),
+            "fhip_voxels_components": (i32, [vp, vp, u32, i32, u32, i32, vp]), "fhip_components_counts": (None, [vp, vp]),
+            "fhip_components_table": (i32, [vp, vp, vp, vp, vp, vp]), "fhip_components_label_slices": (i32, [vp, vp, vp, i32, u32, u32, vp, i32]),
+            "fhip_components_extract": (i32, [vp, vp, vp, i32, vp, u64, vp, i32]), "fhip_components_free": (None, [vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1386,8 +1390,102 @@ class Voxels:
         b = self.bricks.cpu().numpy().view(np.uint64) if self.on_device else self.bricks
         return voxels_unpack(b)
 
+    def components(self, connectivity=6, complement=False):
+        """fhip_voxels_components: the connected parts of the set bits - with `complement` of the clear bits, whose parts away from the
+        grid's border are the enclosed voids - under connectivity 6 (faces) or 26 (faces, edges, corners) -> Components"""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_voxels_components(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(connectivity), int(bool(complement)), C.byref(h)))
+        return Components(self, _ComponentsHandle(h.value), int(connectivity), bool(complement))
+
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
+
+
+class _ComponentsHandle:
+    """owner of an fhip_components, whose device arrays the later calls read"""
+    def __init__(self, h):
+        self.h = h
+        self._free = lib().fhip_components_free      # (held here, as _MeshHandle holds its own)
+
+    def __del__(self):
+        if self.h and self._free is not None:
+            self._free(self.h)
+            self.h = None
+
+
+class Components:
+    """The connected parts of a bitmap (`Voxels.components`), numbered by ascending seed - the voxel of smallest key word * 64 + bit:
+    `.count`, `.nodes` (the bricks' own parts, what the union-find joined), `.n` (foreground voxels); per component `.sizes` uint64
+    [count], `.seeds`, `.lo`, `.hi` uint32 [count, 3] (i, j, k; bounds inclusive), `.border` bool [count] (touches the grid's border:
+    with complement=True the others are the enclosed voids).  It keeps its `Voxels` and hands the bricks to the calls that need them;
+    for bricks on the device those calls are asynchronous on the context's stream, as `Voxels.slices` is."""
+
+    def __init__(self, voxels, owner, connectivity, complement):
+        self.voxels, self._owner, self.connectivity, self.complement = voxels, owner, connectivity, complement
+        self._hip, self.depth, self.grid = voxels._hip, voxels.depth, voxels.grid
+        c = np.zeros(4, np.uint64)
+        lib().fhip_components_counts(owner.h, _p(c))
+        self.count, self.nodes, self.n = int(c[0]), int(c[1]), int(c[2])
+        n = self.count
+        self.sizes, self.seeds, self.lo, self.hi = np.zeros(n, np.uint64), np.zeros((n, 3), np.uint32), np.zeros((n, 3), np.uint32), np.zeros((n, 3), np.uint32)
+        border = np.zeros(n, np.uint8)
+        self._hip.check(lib().fhip_components_table(owner.h, _p(self.sizes), _p(self.seeds), _p(self.lo), _p(self.hi), _p(border)))
+        self.border = border.astype(bool)
+
+    def largest(self):
+        """the id of the largest component (of several, the smallest id)"""
+        if not self.count:
+            raise ValueError("no components")
+        return int(np.argmax(self.sizes))
+
+    def label_slices(self, k0, k1, out=None):
+        """fhip_components_label_slices: int32 [k1 - k0, N, N], [k - k0, j, i] = the component of voxel (i, j, k), -1 for background:
+        numpy for bricks on the host; for bricks on the device a torch CUDA tensor (`out`, contiguous int32 of that size, or a new one)"""
+        v, N = self.voxels, self.grid
+        k0, k1 = int(k0), int(k1)
+        n = max(k1 - k0, 0) * N * N
+        if v.on_device:
+            if out is None:
+                import torch
+                out = torch.empty((max(k1 - k0, 0), N, N), dtype=torch.int32, device=v.bricks.device)
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() >= n
+            self._hip.check(lib().fhip_components_label_slices(self._hip._h, self._owner.h, v._ptr(), 1, k0, k1, _dev_ptr(out), 1))
+            return out
+        assert out is None, "bricks on the host: the images are returned as a numpy array"
+        img = np.zeros((max(k1 - k0, 0), N, N), np.int32)
+        self._hip.check(lib().fhip_components_label_slices(self._hip._h, self._owner.h, v._ptr(), 0, k0, k1, _p(img), 0))
+        return img
+
+    def extract(self, ids, out=None):
+        """fhip_components_extract: the components `ids` as a bitmap of their own -> Voxels (`.cells` None: no octree made it).  `out`
+        as for `voxelize`: a contiguous torch CUDA tensor of at least 8 B^3 bytes, or a contiguous numpy array of that size, written
+        completely; without it a new one where the bricks are - a torch CUDA int64 tensor or a numpy uint64 [B, B, B]."""
+        v = self.voxels
+        ids = np.ascontiguousarray(np.asarray(list(ids) if not isinstance(ids, np.ndarray) else ids, np.int64).reshape(-1))
+        if ((ids < 0) | (ids > 0xFFFFFFFF)).any():
+            raise FidgetHipError(6, "extract: a component id beyond the number of components")
+        ids = ids.astype(np.uint32)
+        B = 1 << self.depth
+        words = B ** 3
+        if out is None and v.on_device:
+            import torch
+            out = torch.empty((B, B, B), dtype=torch.int64, device=v.bricks.device)
+        if out is not None and not isinstance(out, np.ndarray):
+            import torch
+            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
+            ptr, dev = _dev_ptr(out), 1
+            bricks = out.reshape(-1).view(torch.int64)[:words].view(B, B, B)
+        else:
+            if out is None:
+                out = np.zeros((B, B, B), np.uint64)
+            assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
+            ptr, dev = _p(out), 0
+            bricks = out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B)
+        self._hip.check(lib().fhip_components_extract(self._hip._h, self._owner.h, v._ptr(), int(v.on_device), _p(ids), len(ids), ptr, dev))
+        return Voxels(self._hip, bricks, self.depth, None)
+
+    def __repr__(self):
+        return f"Components(count={self.count}, nodes={self.nodes}, n={self.n}, connectivity={self.connectivity}, complement={self.complement})"
 
 
 def voxelize(shape, depth, world_to_model=None, vars=None, out=None):

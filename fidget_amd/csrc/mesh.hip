@@ -23,6 +23,8 @@
 //                 put together in LDS and stored as whole dwords;
 //   k_vox_full / k_vox_leaves / k_vox_slices / k_vox_layer_counts   the inside voxels themselves (fhip_shape_voxels): the octree of occupancy
 //                 written down as a bitmap of 4 x 4 x 4 bricks, and what is made of the bitmap - layer images, voxels per layer;
+//   k_cc_*        the connected parts of such a bitmap (fhip_voxels_components): flood fill inside each brick's word, a lock-free union-find
+//                 over the brick faces (edges, corners), the components numbered by their seeds, their table, label images (mesh_cc.hpp);
 //   k_ctr_edges / k_ctr_vertices / k_ctr_cells / k_ctr_segments   the outlines of a 2D slice (fhip_contour2d): marching squares over the
 //                 pixel-perfect distance image render2d leaves in device memory - vertices on the crossing lattice edges, directed segments,
 //                 the link array (contour/contour.hpp);
@@ -37,6 +39,7 @@
 #include "mesh_edges.hpp"
 #include "mesh_qef.hpp"
 #include "mesh_vox.hpp"
+#include "mesh_cc.hpp"
 #include "contour/contour.hpp"
 // (included by capi.hip after kernels.hip: Regs, step, ballot, uni, ctape_t)
 
@@ -1027,5 +1030,219 @@ __global__ void __launch_bounds__(256) k_ctr_segments(const float* __restrict__ 
         }
         __syncthreads();
     }
+}
+
+// ---- connected components of a voxel bitmap (fhip_voxels_components; the bit arithmetic: mesh_cc.hpp) ------------------------------------
+// Foreground: the word XOR `flip` (0, or all ones for the complement).  A node is one component of one brick taken alone
+// (fhcc::lowest_component walks them in the order of their lowest bits, recomputed where needed: no array of masks, no scratch); node
+// base[brick] + q is the brick's q-th.  Nodes are in the order of the smallest keys (word * 64 + bit) of their voxels, so the smallest
+// node of a component holds its seed, and the components in the order of their seeds are the roots in ascending order.
+//
+// No kernel here waits for another workgroup: no flags, no spinning, no grid barrier.  The only loops over memory that other waves write
+// are cc_find and the retry of cc_unite, and each of their steps moves to a strictly smaller node whatever the other waves do
+// (parent[x] <= x always: it starts as x and only atomicMin changes it while k_cc_merge runs), so both end after at most `x` steps.
+FH_DEV uint32_t cc_load(const uint32_t* p) { return __hip_atomic_load(p, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT); }
+FH_DEV uint32_t cc_find(const uint32_t* parent, uint32_t x) {
+    for (;;) {
+        const uint32_t p = cc_load(parent + x);       // (relaxed, agent scope: past this CU's L1, which other CUs' atomics never refresh)
+        if (p == x) return x;
+        x = p;                                         // p < x
+    }
+}
+// Lock-free union towards the smaller root (Komura; Playne and Hawick): the larger root's parent takes the minimum of itself and the
+// smaller root.  If it was no longer a root - `old` is what another wave linked it to in the meantime - that link may just have been
+// replaced, so old and b remain to be united: go on from there.  a + b falls with every turn.
+FH_DEV void cc_unite(uint32_t* parent, uint32_t a, uint32_t b) {
+    for (;;) {
+        a = cc_find(parent, a);
+        b = cc_find(parent, b);
+        if (a == b) return;
+        if (a < b) { const uint32_t t = a; a = b; b = t; }
+        const uint32_t old = atomicMin(parent + a, b);
+        if (old == a) return;
+        a = old;
+    }
+}
+
+// Nodes per brick, and the totals {nodes, foreground voxels}: one atomic add each per block
+__global__ void __launch_bounds__(256) k_cc_count(const uint64_t* __restrict__ bricks, uint64_t n_words, uint64_t flip, uint32_t conn, uint32_t* __restrict__ cnt,
+                                                  unsigned long long* __restrict__ totals) {
+    __shared__ uint32_t sh[256 / WAVE][2];
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    uint32_t c = 0, v = 0;
+    if (i < n_words) {
+        const uint64_t w = bricks[i] ^ flip;
+        c = fhcc::local_count(w, conn);
+        v = (uint32_t)__popcll(w);
+        cnt[i] = c;
+    }
+    for (int d = WAVE / 2; d > 0; d >>= 1) { c += (uint32_t)__shfl_down((int)c, d); v += (uint32_t)__shfl_down((int)v, d); }
+    if ((threadIdx.x & (WAVE - 1)) == 0) { sh[threadIdx.x / WAVE][0] = c; sh[threadIdx.x / WAVE][1] = v; }
+    __syncthreads();
+    if (threadIdx.x < 2) {
+        uint32_t s = 0;
+        for (int k = 0; k < 256 / WAVE; k++) s += sh[k][threadIdx.x];
+        if (s) atomicAdd(totals + threadIdx.x, (unsigned long long)s);
+    }
+}
+__global__ void __launch_bounds__(256) k_cc_init(uint32_t* __restrict__ parent, uint64_t n_nodes) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n < n_nodes) parent[n] = (uint32_t)n;
+}
+// One lane per brick: its nodes against those of the bricks in the positive directions (3 faces; 13 for connectivity 26 - every pair of
+// neighbouring bricks is seen once, from the brick the direction leaves).  Two nodes are united when the image of one's voxels in the
+// other brick (fhcc::carry) meets the other's.  Full next to full - the inside of a solid - is one union without any flood fill.
+__global__ void __launch_bounds__(256) k_cc_merge(const uint64_t* __restrict__ bricks, uint32_t depth, uint64_t flip, uint32_t conn, const uint32_t* __restrict__ base,
+                                                  uint32_t* parent) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= fhvox::n_words(depth)) return;
+    const uint64_t wa = bricks[i] ^ flip;
+    if (wa == 0) return;
+    const uint32_t B = 1u << depth, bx = (uint32_t)i & (B - 1), by = (uint32_t)(i >> depth) & (B - 1), bz = (uint32_t)(i >> (2 * depth));
+    const uint32_t na = base[i], nd = fhcc::n_dirs(conn);
+    for (uint32_t d = 0; d < nd; d++) {
+        int dx, dy, dz;
+        fhcc::direction(d, dx, dy, dz);
+        const uint32_t x = bx + (uint32_t)dx, y = by + (uint32_t)dy, z = bz + (uint32_t)dz;       // (-1 wraps to above B: nothing lies beyond the grid)
+        if (x >= B || y >= B || z >= B) continue;
+        const uint64_t j = fhvox::word_index(depth, x, y, z);
+        const uint64_t wb = bricks[j] ^ flip;
+        if (wb == 0) continue;
+        const uint32_t nb = base[j];
+        if ((wa & wb) == ~(uint64_t)0) { cc_unite(parent, na, nb); continue; }
+        uint32_t qa = 0;
+        for (uint64_t ra = wa; ra != 0; qa++) {
+            const uint64_t ma = fhcc::lowest_component(ra, wa, conn);
+            ra &= ~ma;
+            uint64_t c = fhcc::carry(ma, dx, dy, dz, conn) & wb;
+            uint32_t qb = 0;
+            for (uint64_t rb = wb; c != 0; qb++) {          // (c is part of wb: every bit of it is in some component of rb)
+                const uint64_t mb = fhcc::lowest_component(rb, wb, conn);
+                rb &= ~mb;
+                if (c & mb) { cc_unite(parent, na + qa, nb + qb); c &= ~mb; }
+            }
+        }
+    }
+}
+// parent[n] = the root of n.  A launch of its own: every union is in.  Other lanes store roots while this one climbs; whatever it reads -
+// the old parent or the root - is an ancestor of the node it read it from, and the roots themselves are not stored to.
+__global__ void __launch_bounds__(256) k_cc_flatten(uint32_t* parent, uint64_t n_nodes) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n >= n_nodes) return;
+    const uint32_t r = cc_find(parent, (uint32_t)n);
+    if (r != (uint32_t)n) __hip_atomic_store(parent + n, r, __ATOMIC_RELAXED, __HIP_MEMORY_SCOPE_AGENT);
+}
+// flag[n] = 1 for a root; after the scan of the flags, comp[n] = the number of roots below n's root (comp may be the flags' array)
+__global__ void __launch_bounds__(256) k_cc_roots(const uint32_t* __restrict__ parent, uint64_t n_nodes, uint32_t* __restrict__ flag) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n < n_nodes) flag[n] = parent[n] == (uint32_t)n ? 1u : 0u;
+}
+__global__ void __launch_bounds__(256) k_cc_number(const uint32_t* __restrict__ parent, const uint32_t* __restrict__ rank, uint64_t n_nodes, uint32_t* comp) {
+    const uint64_t n = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (n < n_nodes) comp[n] = rank[parent[n]];
+}
+// The table: a lane per brick adds each of its nodes to its component.  The lanes of a wave mostly meet in one component - the solid's -
+// so where the nodes of a turn all belong to the same one, the wave adds their voxels up and makes one atomic add; bounds and the border
+// flag are only sent where a look at the current value (never better than the true one: they move one way) says they would change it.
+__global__ void __launch_bounds__(256) k_cc_table(const uint64_t* __restrict__ bricks, uint32_t depth, uint64_t flip, uint32_t conn, const uint32_t* __restrict__ base,
+                                                  const uint32_t* __restrict__ comp_of_node, const uint32_t* __restrict__ parent, unsigned long long* size,
+                                                  uint32_t* lo, uint32_t* hi, uint32_t* border, uint32_t* __restrict__ seed) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    const bool in_grid = i < fhvox::n_words(depth);
+    const uint64_t w = in_grid ? bricks[i] ^ flip : 0;
+    const uint32_t B = 1u << depth, b[3] = {(uint32_t)i & (B - 1), (uint32_t)(i >> depth) & (B - 1), (uint32_t)(i >> (2 * depth))};
+    const uint32_t node0 = w != 0 ? base[i] : 0u;
+    const uint32_t lane = threadIdx.x & (WAVE - 1);
+    uint64_t rest = w;
+    for (uint32_t q = 0; ballot(rest != 0) != 0; q++) {          // (the same number of turns for every lane of the wave)
+        const bool on = rest != 0;
+        uint64_t m = 0;
+        uint32_t comp = 0, cnt = 0;
+        if (on) {
+            m = fhcc::lowest_component(rest, w, conn);
+            rest &= ~m;
+            comp = comp_of_node[node0 + q];
+            cnt = (uint32_t)__popcll(m);
+        }
+        const uint64_t who = ballot(on);
+        const uint32_t c0 = (uint32_t)__shfl((int)comp, (int)__builtin_ctzll(who));
+        if (ballot(on && comp != c0) == 0) {
+            uint32_t s = cnt;
+            for (int d = WAVE / 2; d > 0; d >>= 1) s += (uint32_t)__shfl_down((int)s, d);
+            if (lane == 0) atomicAdd(size + c0, (unsigned long long)s);
+        } else if (on) {
+            atomicAdd(size + comp, (unsigned long long)cnt);
+        }
+        if (on) {
+            uint32_t l[3], h[3];
+            fhcc::local_bounds(m, l, h);
+            for (uint32_t a = 0; a < 3; a++) {
+                const uint32_t vl = 4 * b[a] + l[a], vh = 4 * b[a] + h[a];
+                if (vl < cc_load(lo + 3 * (size_t)comp + a)) atomicMin(lo + 3 * (size_t)comp + a, vl);
+                if (vh > cc_load(hi + 3 * (size_t)comp + a)) atomicMax(hi + 3 * (size_t)comp + a, vh);
+            }
+            if (fhcc::touches_border(m, b[0], b[1], b[2], B) && cc_load(border + comp) == 0) atomicOr(border + comp, 1u);
+            if (parent[node0 + q] == node0 + q) {          // the root: the component's smallest node, whose lowest voxel is the seed
+                uint32_t v[3];
+                fhcc::key_voxel(i * 64 + (uint32_t)__builtin_ctzll(m), depth, v);
+                for (uint32_t a = 0; a < 3; a++) seed[3 * (size_t)comp + a] = v[a];
+            }
+        }
+    }
+}
+// Label images: k_vox_slices' layout - a lane takes a run of `nb` bricks (4; all B of a row where B < 4) of one (k, j) - with an int32 a
+// voxel, one 16-byte store a brick: out[(k - k0) * N * N + j * N + i] = the component of voxel (i, j, k), -1 for background.  The brick's
+// components are walked until the row's four voxels are all placed.
+__global__ void __launch_bounds__(256) k_cc_label_slices(const uint64_t* __restrict__ bricks, uint32_t depth, uint64_t flip, uint32_t conn, const uint32_t* __restrict__ base,
+                                                         const uint32_t* __restrict__ comp_of_node, uint32_t k0, uint32_t k1, int32_t* __restrict__ out) {
+    const uint32_t B = 1u << depth, N = 4u << depth;
+    const uint32_t nb = B < 4 ? B : 4, lg_runs = depth < 2 ? 0 : depth - 2;
+    const uint64_t total = ((uint64_t)(k1 - k0) * N) << lg_runs;
+    for (uint64_t t = (uint64_t)blockIdx.x * 256 + threadIdx.x; t < total; t += (uint64_t)gridDim.x * 256) {
+        const uint32_t g = (uint32_t)t & ((1u << lg_runs) - 1);
+        const uint64_t row = t >> lg_runs;                 // (k - k0) * N + j
+        const uint32_t j = (uint32_t)(row & (N - 1)), k = k0 + (uint32_t)(row >> (depth + 2));
+        const uint32_t shift = 4 * (j & 3) + 16 * (k & 3);
+        const uint64_t first = fhvox::word_index(depth, g * nb, j >> 2, k >> 2);
+        int4* const dst = (int4*)(out + row * N + (size_t)g * 16);
+        for (uint32_t q = 0; q < nb; q++) {
+            const uint64_t w = bricks[first + q] ^ flip;
+            uint64_t want = w & ((uint64_t)0xF << shift);
+            int32_t px[4] = {-1, -1, -1, -1};
+            if (want != 0) {
+                const uint32_t node0 = base[first + q];
+                uint32_t c = 0;
+                for (uint64_t rest = w; want != 0; c++) {
+                    const uint64_t m = fhcc::lowest_component(rest, w, conn);
+                    rest &= ~m;
+                    if (m & want) {
+                        const int32_t id = (int32_t)comp_of_node[node0 + c];
+                        const uint32_t nib = (uint32_t)((m & want) >> shift);
+                        for (uint32_t v = 0; v < 4; v++) if (nib & (1u << v)) px[v] = id;
+                        want &= ~m;
+                    }
+                }
+            }
+            dst[q] = make_int4(px[0], px[1], px[2], px[3]);
+        }
+    }
+}
+// The bricks of the chosen components: the OR of the masks of the nodes whose component is flagged.  Every word is written.
+__global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__ bricks, uint64_t n_words, uint64_t flip, uint32_t conn, const uint32_t* __restrict__ base,
+                                                    const uint32_t* __restrict__ comp_of_node, const uint8_t* __restrict__ chosen, uint64_t* __restrict__ out) {
+    const uint64_t i = (uint64_t)blockIdx.x * 256 + threadIdx.x;
+    if (i >= n_words) return;
+    const uint64_t w = bricks[i] ^ flip;
+    uint64_t o = 0;
+    if (w != 0) {
+        const uint32_t node0 = base[i];
+        uint32_t c = 0;
+        for (uint64_t rest = w; rest != 0; c++) {
+            const uint64_t m = fhcc::lowest_component(rest, w, conn);
+            rest &= ~m;
+            if (chosen[comp_of_node[node0 + c]]) o |= m;
+        }
+    }
+    out[i] = o;
 }
 }  // namespace fhm

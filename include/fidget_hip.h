@@ -418,6 +418,41 @@ const uint32_t* fhip_contours_segments_dev(const void* contours);
 void fhip_contours_free(void* contours);
 fhip_status fhip_contour_loops(const uint32_t* next, uint64_t n, uint32_t* order, uint64_t* loop_start, uint8_t* closed, uint64_t* n_loops);
 
+/* ---- connected components of a voxel bitmap: is the solid one body or several, does it enclose voids ----------
+ * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification.)
+ * The grid is fhip_shape_voxels': B = 1 << depth bricks and N = 4 B voxels per axis, nothing beyond it and no wrap-around.  The
+ * FOREGROUND is the set bits, or with complement != 0 the clear bits.  Two foreground voxels are neighbours when they share a face
+ * (connectivity 6) or a face, an edge or a corner (connectivity 26); any other connectivity is FHIP_ERR_UNSUPPORTED.  A component is a
+ * class of the foreground under "joined by a chain of neighbours".  The key of a voxel is word_index * 64 + bit; a component's seed is
+ * its voxel of smallest key, and the components are numbered 0, 1, ... by ascending seed key.  Per component: size, its number of voxels;
+ * seed (i, j, k); lo, hi, its inclusive bounds per axis; border, 1 when some voxel of it has a coordinate equal to 0 or N - 1.  With
+ * complement, the components with border == 0 are the voids the solid encloses.
+ * fhip_voxels_components: blocking.  on_device != 0: `bricks` is a device pointer (8-byte aligned), otherwise a host buffer of
+ * fhip_voxels_words(depth) words, staged.  Every brick's word is split into its own components (its nodes), which a lock-free union-find
+ * joins across the bricks' faces (edges and corners); no pass waits for another workgroup.  depth > 10 is FHIP_ERR_UNSUPPORTED, more
+ * than 2^32 - 2 nodes FHIP_ERR_OVERFLOW; an empty foreground gives 0 components and FHIP_OK.  The result owns two device arrays (a
+ * brick's first node, a node's component) and the table; it records connectivity, complement and depth.
+ * fhip_components_counts: {components, nodes, foreground voxels, depth}.
+ * fhip_components_table: copies the table to host arrays of the caller's - size [c], seed, lo, hi [c][3], border [c]; any may be NULL.
+ * The two calls below take the bitmap again: it MUST be the one that was labelled, unchanged (the result holds no copy of it).
+ * fhip_components_label_slices: label images for k0 <= k < k1, out[((k - k0) * N + j) * N + i] = the component of voxel (i, j, k), -1
+ * for background.  k0 > k1, k1 > N and more than 2^31 - 1 components are FHIP_ERR_UNSUPPORTED; k0 == k1 writes nothing.
+ * fhip_components_extract: the bitmap of the components ids[0 .. n_ids - 1] (a host array; an id >= the number of components is
+ * FHIP_ERR_UNSUPPORTED): fhip_voxels_words words, all of them written, their set bits the voxels of those components - of the foreground,
+ * so with complement the voids come out as set bits.  `out` must not overlap `bricks`.
+ * Buffers follow fhip_voxels_slices' convention, separately for the bitmap and the output: a device pointer (bricks 8-byte, label
+ * images 16-byte aligned; the call is then asynchronous on the context's stream) or a host buffer. */
+/* (the result's handle, a `fhip_components`, is declared void* here, as fhip_contour2d's is) */
+fhip_status fhip_voxels_components(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t connectivity, int complement,
+                                   void** out);
+void fhip_components_counts(const void* comps, uint64_t out[4]);
+fhip_status fhip_components_table(const void* comps, uint64_t* size, uint32_t* seed, uint32_t* lo, uint32_t* hi, uint8_t* border);
+fhip_status fhip_components_label_slices(fhip_ctx* ctx, const void* comps, const uint64_t* bricks, int bricks_on_device, uint32_t k0,
+                                         uint32_t k1, int32_t* out, int out_on_device);
+fhip_status fhip_components_extract(fhip_ctx* ctx, const void* comps, const uint64_t* bricks, int bricks_on_device, const uint32_t* ids,
+                                    uint64_t n_ids, uint64_t* out, int out_on_device);
+void fhip_components_free(void* comps);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

@@ -139,6 +139,16 @@ extern "C" {
     pub fn fhip_contours_segments_dev(contours: *const c_void) -> *const u32;
     pub fn fhip_contours_free(contours: *mut c_void);
     pub fn fhip_contour_loops(next: *const u32, n: u64, order: *mut u32, loop_start: *mut u64, closed: *mut u8, n_loops: *mut u64) -> fhip_status;
+    // the connected parts of a voxel bitmap (6- or 26-connectivity, of the set or of the clear bits); the handle - a `fhip_components` - is void* in the header
+    pub fn fhip_voxels_components(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, connectivity: u32, complement: c_int,
+                                  out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_components_counts(comps: *const c_void, out: *mut u64);         // components, nodes, foreground voxels, depth
+    pub fn fhip_components_table(comps: *const c_void, size: *mut u64, seed: *mut u32, lo: *mut u32, hi: *mut u32, border: *mut u8) -> fhip_status;
+    pub fn fhip_components_label_slices(ctx: *mut fhip_ctx, comps: *const c_void, bricks: *const u64, bricks_on_device: c_int, k0: u32, k1: u32,
+                                        out: *mut i32, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_components_extract(ctx: *mut fhip_ctx, comps: *const c_void, bricks: *const u64, bricks_on_device: c_int, ids: *const u32, n_ids: u64,
+                                   out: *mut u64, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_components_free(comps: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

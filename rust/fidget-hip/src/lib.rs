@@ -10,6 +10,7 @@
 //! is exercised by that repository's ctypes binding and C11 caller, and `src/ffi.rs` is held against the header by a test there.
 #![warn(missing_docs)]
 
+pub mod components;
 pub mod contours;
 pub mod ffi;
 pub mod mesh;
