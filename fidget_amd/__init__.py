@@ -15,6 +15,7 @@ there is NO CPU fallback: importing works without a GPU (so the build and symbol
 checks run anywhere), but creating a context without a HIP device raises.
 """
 import ctypes as C
+import math
 import os
 import re
 import subprocess
@@ -25,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -55,6 +56,7 @@ EXPORTS = [
     "fhip_point_eval", "fhip_float_eval", "fhip_grad_eval", "fhip_solve", "fhip_render2d", "fhip_render3d", "fhip_render3d_shard", "fhip_render3d_block", "fhip_merge_depth", "fhip_denoise_normals", "fhip_compute_ssao", "fhip_blur_ssao", "fhip_apply_shading", "fhip_to_rgba", "fhip_mesh_sample", "fhip_mesh_build", "fhip_mesh_vertices", "fhip_mesh_triangles", "fhip_mesh_vertices_ptr", "fhip_mesh_triangles_ptr", "fhip_mesh_free", "fhip_mesh_counts", "fhip_mesh_leaves", "fhip_mesh_sample_part", "fhip_mesh_part_bytes", "fhip_mesh_part_export", "fhip_mesh_merge", "fhip_mesh_vertices_dev", "fhip_mesh_triangles_dev", "fhip_mesh_stl_bytes", "fhip_mesh_stl", "fhip_mesh_vertex_grads", "fhip_shape_occupancy", "fhip_voxels_words", "fhip_shape_voxels", "fhip_voxels_slices", "fhip_voxels_layer_counts",
     "fhip_contour2d", "fhip_contours_counts", "fhip_contours_vertices", "fhip_contours_segments", "fhip_contours_next", "fhip_contours_vertices_dev", "fhip_contours_segments_dev", "fhip_contours_free", "fhip_contour_loops",
     "fhip_voxels_components", "fhip_components_counts", "fhip_components_table", "fhip_components_label_slices", "fhip_components_extract", "fhip_components_free",
+    "fhip_voxels_distance", "fhip_distance_info", "fhip_distance_slices", "fhip_distance_dev", "fhip_distance_threshold", "fhip_distance_free",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -189,6 +191,8 @@ def lib():
             "fhip_voxels_components": (i32, [vp, vp, u32, i32, u32, i32, vp]), "fhip_components_counts": (None, [vp, vp]),
             "fhip_components_table": (i32, [vp, vp, vp, vp, vp, vp]), "fhip_components_label_slices": (i32, [vp, vp, vp, i32, u32, u32, vp, i32]),
             "fhip_components_extract": (i32, [vp, vp, vp, i32, vp, u64, vp, i32]), "fhip_components_free": (None, [vp]),
+            "fhip_voxels_distance": (i32, [vp, vp, u32, i32, i32, vp]), "fhip_distance_info": (None, [vp, vp]), "fhip_distance_slices": (i32, [vp, vp, u32, u32, vp, i32]),
+            "fhip_distance_dev": (vp, [vp]), "fhip_distance_threshold": (i32, [vp, vp, u32, i32, vp, i32]), "fhip_distance_free": (None, [vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1397,8 +1401,129 @@ class Voxels:
         self._hip.check(lib().fhip_voxels_components(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(connectivity), int(bool(complement)), C.byref(h)))
         return Components(self, _ComponentsHandle(h.value), int(connectivity), bool(complement))
 
+    def distance(self, complement=False):
+        """fhip_voxels_distance: the exact squared Euclidean distance, in voxels, from every voxel to the nearest set bit - with
+        `complement` to the nearest clear bit -> DistanceField"""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_voxels_distance(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(bool(complement)), C.byref(h)))
+        return DistanceField(self, _DistanceHandle(h.value), bool(complement))
+
+    def offset(self, r, out=None):
+        """the solid grown by a ball of radius r >= 0 - `distance().within(r)` - or shrunk by one of radius -r -
+        `distance(complement=True).beyond(-r)`: what stays is farther than |r| from the nearest clear voxel, so offset(-1) keeps the
+        voxels at distance 1 and removes nothing; to take the surface layer off, use beyond(squared=1) -> Voxels (`out` as for `within`)"""
+        if r >= 0:
+            return self.distance().within(r, out=out)
+        return self.distance(complement=True).beyond(-r, out=out)
+
+    def opened(self, r):
+        """shrunk by r, then grown by r: drops what no ball of that radius fits into (specks, thin walls)"""
+        return self.offset(-r).offset(r)
+
+    def closed(self, r):
+        """grown by r, then shrunk by r: fills what no ball of that radius fits into (pinholes, thin gaps)"""
+        return self.offset(r).offset(-r)
+
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
+
+
+class _DistanceHandle:
+    """owner of an fhip_distance, whose field in device memory the later calls read"""
+    def __init__(self, h):
+        self.h = h
+        self._free = lib().fhip_distance_free      # (held here, as _MeshHandle holds its own)
+
+    def __del__(self):
+        if self.h and self._free is not None:
+            self._free(self.h)
+            self.h = None
+
+
+class DistanceField:
+    """The exact Euclidean distance transform of a bitmap (`Voxels.distance`): per voxel the squared distance to the nearest foreground
+    voxel, a uint32 - 0 on the foreground, 0xFFFFFFFF ("no distance"; -1 as int32) everywhere when there is no foreground.
+    `.max_squared` the largest finite value, `.argmax` the voxel (i, j, k) of smallest index k N^2 + j N + i that has it (None without
+    foreground), `.n` foreground voxels, `.depth`, `.grid`.  The field stays in device memory; results land where the bricks are - for
+    bricks on the device those calls are asynchronous on the context's stream, as `Voxels.slices` is."""
+
+    def __init__(self, voxels, owner, complement):
+        self.voxels, self._owner, self.complement = voxels, owner, complement
+        self._hip, self.depth, self.grid = voxels._hip, voxels.depth, voxels.grid
+        c = np.zeros(4, np.uint64)
+        lib().fhip_distance_info(owner.h, _p(c))
+        self.max_squared, self.n = int(c[0]), int(c[2])
+        N, idx = self.grid, int(c[1])
+        self.argmax = None if idx == 0xFFFFFFFFFFFFFFFF else (idx % N, idx // N % N, idx // (N * N))
+
+    def slices(self, k0, k1, out=None):
+        """fhip_distance_slices: [k1 - k0, N, N], [k - k0, j, i] = the squared distance of voxel (i, j, k): numpy uint32 for bricks on the
+        host; for bricks on the device a torch CUDA int32 tensor (`out`, contiguous, 4-byte elements, of that size, or a new one)"""
+        v, N = self.voxels, self.grid
+        k0, k1 = int(k0), int(k1)
+        n = max(k1 - k0, 0) * N * N
+        if v.on_device:
+            if out is None:
+                import torch
+                out = torch.empty((max(k1 - k0, 0), N, N), dtype=torch.int32, device=v.bricks.device)
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() >= n
+            self._hip.check(lib().fhip_distance_slices(self._hip._h, self._owner.h, k0, k1, _dev_ptr(out), 1))
+            return out
+        assert out is None, "bricks on the host: the layers are returned as a numpy array"
+        img = np.zeros((max(k1 - k0, 0), N, N), np.uint32)
+        self._hip.check(lib().fhip_distance_slices(self._hip._h, self._owner.h, k0, k1, _p(img), 0))
+        return img
+
+    @property
+    def squared_device(self):
+        """the whole field where it is: uint32 [N, N, N] indexed [k, j, i], as `__cuda_array_interface__`"""
+        N = self.grid
+        return _DeviceArray(self._owner, lib().fhip_distance_dev(self._owner.h), (N, N, N), "<u4")
+
+    def _threshold(self, r, squared, beyond, out):
+        if (r is None) == (squared is None):
+            raise ValueError("give exactly one of r and squared")
+        if r is not None:
+            if r < 0:
+                raise ValueError("a radius is not negative")
+            squared = math.floor(r * r)
+        squared = int(squared)
+        if squared < 0 or squared > 0xFFFFFFFF:
+            raise FidgetHipError(6, "distance threshold: t at most 0xFFFFFFFE")
+        v = self.voxels
+        B = 1 << self.depth
+        words = B ** 3
+        if out is None and v.on_device:
+            import torch
+            out = torch.empty((B, B, B), dtype=torch.int64, device=v.bricks.device)
+        if out is not None and not isinstance(out, np.ndarray):
+            import torch
+            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words
+            ptr, dev = _dev_ptr(out), 1
+        else:
+            if out is None:
+                out = np.zeros((B, B, B), np.uint64)
+            assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
+            ptr, dev = _p(out), 0
+        self._hip.check(lib().fhip_distance_threshold(self._hip._h, self._owner.h, squared, int(beyond), ptr, dev))
+        if dev:
+            bricks = out.reshape(-1).view(torch.uint8)[:8 * words].view(torch.int64).view(B, B, B)
+        else:
+            bricks = out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B)
+        return Voxels(self._hip, bricks, self.depth, None)
+
+    def within(self, r=None, squared=None, out=None):
+        """fhip_distance_threshold: the voxels with d2 <= t as a bitmap -> Voxels (`.cells` None).  Exactly one of `r` - a radius in
+        voxels, t = floor(r * r) - and `squared` - t itself.  `out` as for `Components.extract`: a contiguous torch CUDA tensor of at
+        least 8 B^3 bytes, or a contiguous numpy array of that size, written completely; without it a new one where the bricks are."""
+        return self._threshold(r, squared, 0, out)
+
+    def beyond(self, r=None, squared=None, out=None):
+        """... the voxels with d2 > t; "no distance" is beyond every t"""
+        return self._threshold(r, squared, 1, out)
+
+    def __repr__(self):
+        return f"DistanceField(depth={self.depth}, grid={self.grid}, max_squared={self.max_squared}, argmax={self.argmax}, n={self.n}, complement={self.complement})"
 
 
 class _ComponentsHandle:

@@ -1760,3 +1760,6 @@ fhip_status fhip_components_extract(fhip_ctx* ctx, const void* h, const uint64_t
     return st.finish();
 }
 void fhip_components_free(void* h) { delete (fhip_components*)h; }
+
+// the distance transform of a voxel bitmap (fhip_voxels_distance): a fragment of its own, with the helpers above
+#include "capi_edt.hpp"

@@ -1246,3 +1246,6 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
     out[i] = o;
 }
 }  // namespace fhm
+
+// k_edt_*: the exact distance transform of such a bitmap (fhip_voxels_distance) - its own file
+#include "edt.hip"

@@ -453,6 +453,37 @@ fhip_status fhip_components_extract(fhip_ctx* ctx, const void* comps, const uint
                                     uint64_t n_ids, uint64_t* out, int out_on_device);
 void fhip_components_free(void* comps);
 
+/* ---- exact Euclidean distance transform of a voxel bitmap: how far, in voxels, from the nearest foreground voxel ----------
+ * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification.  A shape's own value is no
+ * distance - min, max, scaling and mix all break |grad f| = 1 - but between voxel centres the squared distance is an integer.)
+ * The grid is fhip_shape_voxels': N = 4 << depth voxels per axis, voxel (i, j, k) bit lx + 4 ly + 16 lz of bricks[bz][by][bx].  The
+ * FOREGROUND is the set bits, or with complement != 0 the clear bits.  The field d2 is N^3 uint32, d2[(k * N + j) * N + i] = the minimum
+ * over the foreground voxels (i', j', k') of (i - i')^2 + (j - j')^2 + (k - k')^2: 0 on the foreground itself.  Outside the grid there is
+ * nothing, neither foreground nor background.  Without any foreground voxel every value is 0xFFFFFFFF, "no distance" (-1 as an int32).
+ * fhip_voxels_distance: blocking.  on_device != 0: `bricks` is a device pointer (8-byte aligned), otherwise a host buffer of
+ * fhip_voxels_words(depth) words, staged.  Three separable passes, exact in integers: along i from the rows' bit masks, then along j and
+ * along k the lower envelope of the parabolas f(q) + (p - q)^2; no pass waits for another workgroup.  depth > 8 is FHIP_ERR_UNSUPPORTED,
+ * refused before anything is allocated: at depth 8 the field is 4 GiB, and the call holds a workspace of up to 1 GiB beside it while it
+ * runs.  The result owns the field in device memory and records depth and complement; it keeps no reference to the bitmap.
+ * fhip_distance_info: {the largest finite d2, the smallest index (k * N + j) * N + i that has it, foreground voxels, depth}.  With every
+ * voxel foreground: 0 at index 0.  Without foreground: 0 and, for the index, UINT64_MAX ("none").
+ * fhip_distance_slices: the layers k0 <= k < k1, out[((k - k0) * N + j) * N + i] = d2 of voxel (i, j, k).  k0 > k1 and k1 > N are
+ * FHIP_ERR_UNSUPPORTED; k0 == k1 writes nothing.  Only these layers are copied to a host buffer.
+ * fhip_distance_dev: the device pointer of the whole field, N^3 uint32, valid until fhip_distance_free.
+ * fhip_distance_threshold: a bitmap of fhip_voxels_words(depth) words, all of them written: with beyond == 0 a bit is set where
+ * d2 <= t ("within"), otherwise where d2 > t ("beyond").  t <= 0xFFFFFFFE, 0xFFFFFFFF is FHIP_ERR_UNSUPPORTED: "no distance" is never
+ * within and always beyond.  Within t of the set bits is the solid grown by a ball of radius sqrt(t); beyond t of the clear bits
+ * (complement) is the solid shrunk by it.
+ * Output buffers follow fhip_voxels_slices' convention: a device pointer (a bitmap 8-byte, layers 16-byte aligned; the call is then
+ * asynchronous on the context's stream) or a host buffer, filled when the call returns. */
+/* (the result's handle, a `fhip_distance`, is declared void* here, as fhip_voxels_components' is) */
+fhip_status fhip_voxels_distance(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, int complement, void** out);
+void fhip_distance_info(const void* dist, uint64_t out[4]);
+fhip_status fhip_distance_slices(fhip_ctx* ctx, const void* dist, uint32_t k0, uint32_t k1, uint32_t* out, int out_on_device);
+const uint32_t* fhip_distance_dev(const void* dist);
+fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* dist, uint32_t t, int beyond, uint64_t* out_bricks, int out_on_device);
+void fhip_distance_free(void* dist);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

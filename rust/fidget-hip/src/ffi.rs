@@ -149,6 +149,13 @@ extern "C" {
     pub fn fhip_components_extract(ctx: *mut fhip_ctx, comps: *const c_void, bricks: *const u64, bricks_on_device: c_int, ids: *const u32, n_ids: u64,
                                    out: *mut u64, out_on_device: c_int) -> fhip_status;
     pub fn fhip_components_free(comps: *mut c_void);
+    // the exact Euclidean distance transform of a voxel bitmap (squared distances, uint32); the handle - a `fhip_distance` - is void* in the header
+    pub fn fhip_voxels_distance(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, complement: c_int, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_distance_info(dist: *const c_void, out: *mut u64);         // largest finite d2, its smallest index, foreground voxels, depth
+    pub fn fhip_distance_slices(ctx: *mut fhip_ctx, dist: *const c_void, k0: u32, k1: u32, out: *mut u32, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_distance_dev(dist: *const c_void) -> *const u32;
+    pub fn fhip_distance_threshold(ctx: *mut fhip_ctx, dist: *const c_void, t: u32, beyond: c_int, out_bricks: *mut u64, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_distance_free(dist: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,
