@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -57,6 +57,7 @@ EXPORTS = [
     "fhip_contour2d", "fhip_contours_counts", "fhip_contours_vertices", "fhip_contours_segments", "fhip_contours_next", "fhip_contours_vertices_dev", "fhip_contours_segments_dev", "fhip_contours_free", "fhip_contour_loops",
     "fhip_voxels_components", "fhip_components_counts", "fhip_components_table", "fhip_components_label_slices", "fhip_components_extract", "fhip_components_free",
     "fhip_voxels_distance", "fhip_distance_info", "fhip_distance_slices", "fhip_distance_dev", "fhip_distance_threshold", "fhip_distance_free",
+    "fhip_voxels_surface", "fhip_voxels_mesh",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -193,6 +194,7 @@ def lib():
             "fhip_components_extract": (i32, [vp, vp, vp, i32, vp, u64, vp, i32]), "fhip_components_free": (None, [vp]),
             "fhip_voxels_distance": (i32, [vp, vp, u32, i32, i32, vp]), "fhip_distance_info": (None, [vp, vp]), "fhip_distance_slices": (i32, [vp, vp, u32, u32, vp, i32]),
             "fhip_distance_dev": (vp, [vp]), "fhip_distance_threshold": (i32, [vp, vp, u32, i32, vp, i32]), "fhip_distance_free": (None, [vp]),
+            "fhip_voxels_surface": (i32, [vp, vp, u32, i32, vp]), "fhip_voxels_mesh": (i32, [vp, vp, u32, i32, vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1408,6 +1410,29 @@ class Voxels:
         self._hip.check(lib().fhip_voxels_distance(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(bool(complement)), C.byref(h)))
         return DistanceField(self, _DistanceHandle(h.value), bool(complement))
 
+    def mesh(self):
+        """fhip_voxels_mesh: the boundary of the set voxels -> Mesh.  Every exposed face of a voxel is two triangles, counter-clockwise
+        seen from outside, in the order (brick word, direction -x +x -y +y -z +z, bit); the vertices are the lattice corners the faces
+        use, one each, at float(2 a - N) / N in the cube [-1, 1]^3 the bitmap was sampled in.  The arrays are resident on the device
+        (`.stl()`, `.vertex_grads()`, `.vertices_device()`, `.triangles_device()`) and copied to the host (`.triangles`, `.vertices`);
+        `.counts` holds the octree's counters, all 0 here.  Overflow: 2^32 triangles or vertices and more."""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_voxels_mesh(self._hip._h, self._ptr(), self.depth, int(self.on_device), C.byref(h)))
+        owner = _MeshHandle(h.value)
+        c = np.zeros(8, np.uint64)
+        lib().fhip_mesh_counts(owner.h, _p(c))
+        counts = {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
+        verts = owner.view(lib().fhip_mesh_vertices_ptr(owner.h), (int(c[6]), 3), np.float32)
+        tris = owner.view(lib().fhip_mesh_triangles_ptr(owner.h), (int(c[7]), 3), np.uint64)
+        return Mesh(owner, self._hip, tris, verts, counts)
+
+    def surface(self):
+        """fhip_voxels_surface: the counting pass of `mesh()` alone -> Surface: exposed faces per direction, used lattice corners and
+        edges, and from them the area and the Euler number"""
+        out = np.zeros(10, np.uint64)
+        self._hip.check(lib().fhip_voxels_surface(self._hip._h, self._ptr(), self.depth, int(self.on_device), _p(out)))
+        return Surface(self.grid, out)
+
     def offset(self, r, out=None):
         """the solid grown by a ball of radius r >= 0 - `distance().within(r)` - or shrunk by one of radius -r -
         `distance(complement=True).beyond(-r)`: what stays is farther than |r| from the nearest clear voxel, so offset(-1) keeps the
@@ -1426,6 +1451,22 @@ class Voxels:
 
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
+
+
+class Surface:
+    """The surface summary of a bitmap (`Voxels.surface`): `.faces` the exposed faces per direction -x, +x, -y, +y, -z, +z; `.vertices`
+    the lattice corners whose eight voxels are not all equal; `.edges` the lattice edges whose four voxels are not all equal; `.n` the
+    set voxels.  `.n_faces` their sum over the directions, `.area` = n_faces h^2 with h = 2 / N, in the cube [-1, 1]^3; `.euler` =
+    vertices - edges + n_faces: 2 for a solid without handles or voids, 2 more for every void, 2 fewer for every handle, 1 more where
+    two parts touch along an edge or at a corner only.  Outside the grid is clear: the surface is closed."""
+    def __init__(self, grid, raw):
+        raw = [int(v) for v in raw]
+        self.grid, self.faces, self.vertices, self.edges, self.n_faces, self.n = int(grid), tuple(raw[:6]), raw[6], raw[7], raw[8], raw[9]
+        self.area = self.n_faces * (2.0 / self.grid) ** 2
+        self.euler = self.vertices - self.edges + self.n_faces
+
+    def __repr__(self):
+        return f"Surface(grid={self.grid}, faces={self.faces}, vertices={self.vertices}, edges={self.edges}, area={self.area:.6g}, euler={self.euler})"
 
 
 class _DistanceHandle:

@@ -1763,3 +1763,5 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 
 // the distance transform of a voxel bitmap (fhip_voxels_distance): a fragment of its own, with the helpers above
 #include "capi_edt.hpp"
+// the boundary mesh of a voxel bitmap (fhip_voxels_mesh, fhip_voxels_surface): likewise
+#include "capi_vmesh.hpp"

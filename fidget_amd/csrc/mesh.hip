@@ -1249,3 +1249,5 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 
 // k_edt_*: the exact distance transform of such a bitmap (fhip_voxels_distance) - its own file
 #include "edt.hip"
+// k_vm_*: the boundary mesh of such a bitmap (fhip_voxels_mesh, fhip_voxels_surface) - its own file
+#include "vmesh.hip"

@@ -484,6 +484,35 @@ const uint32_t* fhip_distance_dev(const void* dist);
 fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* dist, uint32_t t, int beyond, uint64_t* out_bricks, int out_on_device);
 void fhip_distance_free(void* dist);
 
+/* ---- boundary mesh of a voxel bitmap: the solid's faces as triangles, its surface area, its Euler number ----------
+ * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification, exact and in integers.)
+ * GRID.  fhip_shape_voxels': B = 1 << depth bricks and N = 4 B voxels per axis, voxel (i, j, k) bit lx + 4 ly + 16 lz of word
+ * (bz B + by) B + bx.  Outside the grid every voxel counts as clear: faces on the grid's border exist and the surface is closed.
+ * FACE.  A set voxel and a direction d = 0 .. 5 = -x, +x, -y, +y, -z, +z in which its neighbour is clear; its axis is a = d / 2.  With
+ * (u, v) the unit vectors of the next two axes cyclically (x -> y, z; y -> z, x; z -> x, y), its four lattice corners, counter-clockwise
+ * seen from outside, are o, o + u, o + u + v, o + v with o = (i, j, k) + e_a on the + side, and o, o + v, o + u + v, o + u with
+ * o = (i, j, k) on the - side.  Faces are ordered by brick word index, then d, then the voxel's bit in its brick.  Face f gives the
+ * triangles 2 f = (c0, c1, c2) and 2 f + 1 = (c0, c2, c3), so that the STL normal (b - a) x (c - a) points from set to clear.
+ * VERTEX.  A lattice corner (a, b, c), 0 <= a, b, c <= N, is used iff the eight voxels around it are not all equal - the same set as
+ * the corners of all faces.  One vertex per used corner, shared by every face there, also where the surface pinches (voxels touching
+ * only along an edge or at a corner).  Vertices are numbered ascending by corner brick ((c >> 2) (B + 1) + (b >> 2)) (B + 1) + (a >> 2),
+ * then by local bit (a & 3) + 4 (b & 3) + 16 (c & 3).  A coordinate is float(2 a - N) * (1.0f / N), exact in f32: the frame is the
+ * cube [-1, 1]^3 that the bitmap was sampled in.
+ * EDGE.  A lattice edge is used iff the four voxels around it are not all equal.
+ * fhip_voxels_surface: the counting pass alone; blocking.  out = {faces per direction [6], V used corners, E used edges, F = the sum of
+ * the six, n set voxels}, a host array.  The area is F h^2 with h = 2 / N, and V - E + F the Euler number of the surface complex.
+ * fhip_voxels_mesh: blocking.  The counting pass, two prefix sums, one pass that writes the vertices and one that writes the faces;
+ * no pass waits for another workgroup.  The result is a fhip_mesh like fhip_mesh_build's: vertices (3 f32 each) and triangles (3 u64
+ * each) resident in device memory and copied to the host, so that fhip_mesh_counts (entries 6 and 7; the octree's counters are 0),
+ * _vertices(_ptr, _dev), _triangles(_ptr, _dev), _stl_bytes, _stl, _vertex_grads and _free apply unchanged.  An empty bitmap gives an
+ * empty mesh (no device arrays) and FHIP_OK.
+ * Both: on_device != 0: `bricks` is a device pointer (8-byte aligned), otherwise a host buffer of fhip_voxels_words(depth) words,
+ * staged.  A NULL argument, a misaligned device pointer and depth > 10 are refused before any launch.  2^32 triangles or more, or
+ * 2^32 vertices or more, are FHIP_ERR_OVERFLOW, decided from the counting pass's 64-bit totals before an array of the result is
+ * allocated or written; a failed allocation is FHIP_ERR_HIP. */
+fhip_status fhip_voxels_surface(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint64_t out[10]);
+fhip_status fhip_voxels_mesh(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, fhip_mesh** out);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

@@ -156,6 +156,9 @@ extern "C" {
     pub fn fhip_distance_dev(dist: *const c_void) -> *const u32;
     pub fn fhip_distance_threshold(ctx: *mut fhip_ctx, dist: *const c_void, t: u32, beyond: c_int, out_bricks: *mut u64, out_on_device: c_int) -> fhip_status;
     pub fn fhip_distance_free(dist: *mut c_void);
+    // the boundary mesh of a voxel bitmap - a fhip_mesh like fhip_mesh_build's - and its surface summary {faces [6], V, E, F, n}
+    pub fn fhip_voxels_surface(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, out: *mut u64) -> fhip_status;
+    pub fn fhip_voxels_mesh(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, out: *mut *mut fhip_mesh) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,
