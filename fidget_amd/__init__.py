@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -58,6 +58,7 @@ EXPORTS = [
     "fhip_voxels_components", "fhip_components_counts", "fhip_components_table", "fhip_components_label_slices", "fhip_components_extract", "fhip_components_free",
     "fhip_voxels_distance", "fhip_distance_info", "fhip_distance_slices", "fhip_distance_dev", "fhip_distance_threshold", "fhip_distance_free",
     "fhip_voxels_surface", "fhip_voxels_mesh",
+    "fhip_voxels_flow", "fhip_voxels_overhangs", "fhip_voxels_heights",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -195,6 +196,8 @@ def lib():
             "fhip_voxels_distance": (i32, [vp, vp, u32, i32, i32, vp]), "fhip_distance_info": (None, [vp, vp]), "fhip_distance_slices": (i32, [vp, vp, u32, u32, vp, i32]),
             "fhip_distance_dev": (vp, [vp]), "fhip_distance_threshold": (i32, [vp, vp, u32, i32, vp, i32]), "fhip_distance_free": (None, [vp]),
             "fhip_voxels_surface": (i32, [vp, vp, u32, i32, vp]), "fhip_voxels_mesh": (i32, [vp, vp, u32, i32, vp]),
+            "fhip_voxels_flow": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, i32]), "fhip_voxels_overhangs": (i32, [vp, vp, u32, i32, u32, u32, i32, vp, i32]),
+            "fhip_voxels_heights": (i32, [vp, vp, u32, i32, u32, vp, i32]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1448,6 +1451,95 @@ class Voxels:
     def closed(self, r):
         """grown by r, then shrunk by r: fills what no ball of that radius fits into (pinholes, thin gaps)"""
         return self.offset(r).offset(-r)
+
+    # ---- along a direction: d = 0 .. 5 = -x, +x, -y, +y, -z, +z, e(d) its unit vector, d ^ 1 its opposite --------------------------
+    def _bitmap_out(self, out):
+        """`out` as for `DistanceField.within` -> (out, pointer, on the device?): a contiguous torch CUDA tensor of at least 8 B^3 bytes or
+        a contiguous numpy array of that size; without it a new one where the bricks are"""
+        B = 1 << self.depth
+        if out is None and self.on_device:
+            import torch
+            out = torch.empty((B, B, B), dtype=torch.int64, device=self.bricks.device)
+        if out is not None and not isinstance(out, np.ndarray):
+            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * B ** 3
+            return out, _dev_ptr(out), 1
+        if out is None:
+            out = np.zeros((B, B, B), np.uint64)
+        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * B ** 3
+        return out, _p(out), 0
+
+    def _bitmap_of(self, out, dev):
+        B = 1 << self.depth
+        if dev:
+            import torch
+            bricks = out.reshape(-1).view(torch.uint8)[:8 * B ** 3].view(torch.int64).view(B, B, B)
+        else:
+            bricks = out.reshape(-1).view(np.uint8)[:8 * B ** 3].view(np.uint64).reshape(B, B, B)
+        return Voxels(self._hip, bricks, self.depth, None)
+
+    def flow(self, dir, blockers=None, with_seeds=False, out=None):
+        """fhip_voxels_flow: these voxels as seeds S flowing towards direction `dir` past the blockers K (a Voxels of the same depth, in
+        the same place as these; None: none) -> Voxels R (`.cells` None) with R(p) = (R(p - e) | S(p - e)) & ~K(p), R and S false
+        outside the grid: R(p) holds iff there is t >= 1 with S(p - t e) and no blocker at p - s e for all 0 <= s < t.  A seed that is
+        itself blocked still emits; a blocked voxel is never in R.  `with_seeds`: R | S.  `out` as for `DistanceField.within`, not
+        the seeds' or the blockers' own array.  The space trapped along an axis - reachable from neither side, an undercut of a
+        two-part mould - is the AND of the two opposite shadows: `a.shadow(4).bricks & a.shadow(5).bricks`."""
+        if blockers is not None:
+            if not isinstance(blockers, Voxels) or blockers.depth != self.depth:
+                raise ValueError("blockers: a Voxels of the same depth")
+            if blockers.on_device != self.on_device:
+                raise ValueError("seeds and blockers live in the same place: both on the host or both on the device")
+        out, ptr, dev = self._bitmap_out(out)
+        self._hip.check(lib().fhip_voxels_flow(self._hip._h, self._ptr(), None if blockers is None else blockers._ptr(), self.depth, int(self.on_device),
+                                               int(dir), 1 if with_seeds else 0, ptr, dev))
+        return self._bitmap_of(out, dev)
+
+    def shadow(self, dir, out=None):
+        """the clear voxels with a set voxel behind them, seen towards `dir`: `flow(dir, blockers=self)`"""
+        return self.flow(dir, blockers=self, out=out)
+
+    def swept(self, dir, out=None):
+        """the solid swept towards `dir` to the grid's border - the shadow and the solid: `flow(dir, with_seeds=True)`"""
+        return self.flow(dir, with_seeds=True, out=out)
+
+    def overhangs(self, up=5, reach2=1, bed=True, out=None):
+        """fhip_voxels_overhangs: the set voxels that are not supported when the part is built towards `up` -> Voxels.  p is supported iff
+        there is a set q one layer below, (q - p) . e(up) = -1, whose squared perpendicular offset is at most `reach2` (0 .. 16): a
+        Euclidean disc - 0 straight below only, 1 a plus of five, 2 the 3 x 3 square.  For p in the first layer every q counts as set
+        iff `bed`, and as clear otherwise.  `out` as for `flow`."""
+        out, ptr, dev = self._bitmap_out(out)
+        self._hip.check(lib().fhip_voxels_overhangs(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(up), int(reach2), int(bool(bed)), ptr, dev))
+        return self._bitmap_of(out, dev)
+
+    def supports(self, up=5, reach2=1, bed=True, out=None):
+        """the clear columns under every overhanging voxel, down to the next set voxel or the grid's border:
+        `overhangs(up, reach2, bed).flow(up ^ 1, blockers=self)`.  On the device the calls are asynchronous on the context's stream: a
+        bitmap handed to them must stay allocated until that stream has passed them - with a context on a stream other than torch's
+        current one, keep the tensors (or synchronise) before dropping them."""
+        over = self.overhangs(up, reach2, bed)
+        res = over.flow(int(up) ^ 1, blockers=self, out=out)
+        res._seeds = over          # (on the device the flow may still be reading them: they live as long as the result)
+        return res
+
+    def heights(self, axis=2, out=None):
+        """fhip_voxels_heights: int32 [3, N, N] over the columns along `axis`, indexed by the two remaining coordinates, the lower axis
+        fastest - axis 2 gives [j][i], 1 [k][i], 0 [k][j].  Plane 0: the smallest coordinate along the axis of a set voxel in the
+        column, -1 in an empty column; plane 1: the largest, -1 likewise; plane 2: the number of set voxels.  numpy, or a torch CUDA
+        int32 tensor for bricks on the device; `out`: a contiguous array of either kind with 4-byte elements and that size."""
+        N = self.grid
+        if out is None and self.on_device:
+            import torch
+            out = torch.empty((3, N, N), dtype=torch.int32, device=self.bricks.device)
+        if out is not None and not isinstance(out, np.ndarray):
+            assert out.is_cuda and out.is_contiguous() and out.element_size() == 4 and out.numel() >= 3 * N * N
+            ptr, dev = _dev_ptr(out), 1
+        else:
+            if out is None:
+                out = np.zeros((3, N, N), np.int32)
+            assert out.flags.c_contiguous and out.flags.writeable and out.itemsize == 4 and out.size >= 3 * N * N
+            ptr, dev = _p(out), 0
+        self._hip.check(lib().fhip_voxels_heights(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(axis), ptr, dev))
+        return out
 
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"

@@ -1765,3 +1765,5 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 #include "capi_edt.hpp"
 // the boundary mesh of a voxel bitmap (fhip_voxels_mesh, fhip_voxels_surface): likewise
 #include "capi_vmesh.hpp"
+// a voxel bitmap along a direction (fhip_voxels_flow, fhip_voxels_overhangs, fhip_voxels_heights): likewise
+#include "capi_flow.hpp"

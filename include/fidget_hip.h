@@ -513,6 +513,42 @@ void fhip_distance_free(void* dist);
 fhip_status fhip_voxels_surface(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint64_t out[10]);
 fhip_status fhip_voxels_mesh(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, fhip_mesh** out);
 
+/* ---- a voxel bitmap along a direction: shadows, overhangs, supports, heights ---------------------------------------
+ * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification, exact and in integers.)
+ * GRID.  fhip_shape_voxels': B = 1 << depth bricks and N = 4 B voxels per axis, depth <= 10, voxel (i, j, k) bit lx + 4 ly + 16 lz of
+ * word (bz B + by) B + bx.  Outside the grid every bitmap is clear.
+ * DIRECTION.  d = 0 .. 5 is -x, +x, -y, +y, -z, +z, the numbering of fhip_voxels_mesh's faces; e(d) is its unit vector and d ^ 1 its
+ * opposite.  An axis a = 0, 1, 2 is x, y, z.
+ * FLOW.  Given seeds S, blockers K and a direction d, the flow is the bitmap R with R(p) = (R(p - e) | S(p - e)) & ~K(p), R and S false
+ * outside the grid; a NULL K means none.  Equivalently R(p) holds iff there is t >= 1 with S(p - t e) and ~K(p - s e) for all
+ * 0 <= s < t: a seed that is itself blocked still emits, and a blocked voxel is never in R.  With FHIP_FLOW_WITH_SEEDS (bit 0 of
+ * `flags`) the result is R | S.  The shadow of a solid A towards d is flow(S = A, K = A, d), the clear voxels with a set voxel behind
+ * them; the solid swept to the border is flow(A, none, d, WITH_SEEDS); the space trapped along an axis - reachable from neither side,
+ * an undercut of a two-part mould - is the AND of the two opposite shadows, which the caller takes.
+ * OVERHANGS.  Given a solid A, a build direction `up`, an integer reach2 in 0 .. 16 and a flag `bed`: p is supported iff there is a set
+ * q one layer below, (q - p) . e(up) = -1, whose squared perpendicular offset - the squared length of q - p projected on the two other
+ * axes - is at most reach2: a Euclidean disc, reach2 = 0 straight below only, 1 a plus of five, 2 the 3 x 3 square.  For p in the first
+ * layer (p - e(up) outside the grid) every q counts as set iff `bed`, and as clear otherwise.  The overhangs are the set voxels that
+ * are not supported.  With reach2 <= 16 every q lies in p's brick or in a brick adjacent to it: hence the limit.
+ * SUPPORTS are flow(S = overhangs, K = A, d = up ^ 1): the clear columns under every overhanging voxel, down to the next set voxel or
+ * the grid's border - two calls.
+ * HEIGHTS.  Given an axis a, the result is int32 [3][N][N], indexed by the two remaining coordinates, the lower axis fastest: a = 2
+ * gives [j][i], a = 1 [k][i], a = 0 [k][j].  Plane 0: the smallest coordinate along a of a set voxel in that column, -1 in an empty
+ * column; plane 1: the largest, -1 likewise; plane 2: the number of set voxels in the column.
+ * All three: one launch on the context's stream.  on_device != 0: the inputs are device pointers (8-byte aligned) - `seeds` and
+ * `blockers` live in the same place - and otherwise host buffers of fhip_voxels_words(depth) words, staged; out_on_device likewise
+ * for `out`, which is written completely: fhip_voxels_words(depth) words, or 3 N N int32.  With device pointers throughout the call
+ * is asynchronous, as fhip_voxels_slices is; with a host `out` it returns when `out` is filled.  Refused before any launch, `out`
+ * untouched: a NULL context or `out` (FHIP_ERR_BAD_TAPE); a NULL input, depth > 10, dir or up > 5, axis > 2, reach2 > 16, unknown flag
+ * bits, a misaligned device pointer, an `out` that is the same pointer as an input (FHIP_ERR_UNSUPPORTED). */
+#define FHIP_FLOW_WITH_SEEDS 1u
+fhip_status fhip_voxels_flow(fhip_ctx* ctx, const uint64_t* seeds, const uint64_t* blockers /* NULL: none */, uint32_t depth,
+                             int on_device, uint32_t dir, uint32_t flags, uint64_t* out, int out_on_device);
+fhip_status fhip_voxels_overhangs(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t up,
+                                  uint32_t reach2, int bed, uint64_t* out, int out_on_device);
+fhip_status fhip_voxels_heights(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t axis,
+                                int32_t* out, int out_on_device);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */
