@@ -6,7 +6,8 @@
 // (blas.rs dotx, the 3-row special case), norm = sqrt(0 + dot(v, v)) (norm.rs norm_squared),
 // normalize = each component / norm (unscale), Matrix3 * Vector3 by columns: col0*x0, then
 // col_j*x_j + acc (blas.rs gemv).  PARITY: the reference has no test or golden image for this file;
-// these functions are pinned only by hand-checked small cases in tests/test_effects.py.
+// these functions are pinned by hand-checked small cases in tests/test_effects.py and, since the device kernels are this
+// same text, by an independent numpy restatement of effects.rs (tests/effects_ref.py, tests/test_effects_ref.py).
 #pragma once
 #include <cmath>
 #include <cstdint>
