@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -57,6 +57,7 @@ EXPORTS = [
     "fhip_contour2d", "fhip_contours_counts", "fhip_contours_vertices", "fhip_contours_segments", "fhip_contours_next", "fhip_contours_vertices_dev", "fhip_contours_segments_dev", "fhip_contours_free", "fhip_contour_loops",
     "fhip_voxels_components", "fhip_components_counts", "fhip_components_table", "fhip_components_label_slices", "fhip_components_extract", "fhip_components_free",
     "fhip_voxels_distance", "fhip_distance_info", "fhip_distance_slices", "fhip_distance_dev", "fhip_distance_threshold", "fhip_distance_free",
+    "fhip_distance_thickness", "fhip_thickness_info", "fhip_thickness_thin", "fhip_thickness_histogram",
     "fhip_voxels_surface", "fhip_voxels_mesh",
     "fhip_voxels_flow", "fhip_voxels_overhangs", "fhip_voxels_heights",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
@@ -195,6 +196,8 @@ def lib():
             "fhip_components_extract": (i32, [vp, vp, vp, i32, vp, u64, vp, i32]), "fhip_components_free": (None, [vp]),
             "fhip_voxels_distance": (i32, [vp, vp, u32, i32, i32, vp]), "fhip_distance_info": (None, [vp, vp]), "fhip_distance_slices": (i32, [vp, vp, u32, u32, vp, i32]),
             "fhip_distance_dev": (vp, [vp]), "fhip_distance_threshold": (i32, [vp, vp, u32, i32, vp, i32]), "fhip_distance_free": (None, [vp]),
+            "fhip_distance_thickness": (i32, [vp, vp, vp]), "fhip_thickness_info": (None, [vp, vp]), "fhip_thickness_thin": (i32, [vp, vp, u32, vp, i32]),
+            "fhip_thickness_histogram": (i32, [vp, vp, vp, u32, vp, i32]),
             "fhip_voxels_surface": (i32, [vp, vp, u32, i32, vp]), "fhip_voxels_mesh": (i32, [vp, vp, u32, i32, vp]),
             "fhip_voxels_flow": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, i32]), "fhip_voxels_overhangs": (i32, [vp, vp, u32, i32, u32, u32, i32, vp, i32]),
             "fhip_voxels_heights": (i32, [vp, vp, u32, i32, u32, vp, i32]),
@@ -1413,6 +1416,11 @@ class Voxels:
         self._hip.check(lib().fhip_voxels_distance(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(bool(complement)), C.byref(h)))
         return DistanceField(self, _DistanceHandle(h.value), bool(complement))
 
+    def thickness(self, complement=False):
+        """the local thickness of the solid's walls - `distance(complement=True).thickness()` - or with `complement` the local width of
+        the empty space - `distance().thickness()` -> ThicknessField"""
+        return self.distance(complement=not complement).thickness()
+
     def mesh(self):
         """fhip_voxels_mesh: the boundary of the set voxels -> Mesh.  Every exposed face of a voxel is two triangles, counter-clockwise
         seen from outside, in the order (brick word, direction -x +x -y +y -z +z, bit); the vertices are the lattice corners the faces
@@ -1638,7 +1646,10 @@ class DistanceField:
                 out = np.zeros((B, B, B), np.uint64)
             assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
             ptr, dev = _p(out), 0
-        self._hip.check(lib().fhip_distance_threshold(self._hip._h, self._owner.h, squared, int(beyond), ptr, dev))
+        if beyond == 2:          # (ThicknessField.thin)
+            self._hip.check(lib().fhip_thickness_thin(self._hip._h, self._owner.h, squared, ptr, dev))
+        else:
+            self._hip.check(lib().fhip_distance_threshold(self._hip._h, self._owner.h, squared, int(beyond), ptr, dev))
         if dev:
             bricks = out.reshape(-1).view(torch.uint8)[:8 * words].view(torch.int64).view(B, B, B)
         else:
@@ -1655,8 +1666,69 @@ class DistanceField:
         """... the voxels with d2 > t; "no distance" is beyond every t"""
         return self._threshold(r, squared, 1, out)
 
+    def thickness(self):
+        """fhip_distance_thickness: per voxel the squared radius of the largest ball that holds it and no foreground voxel of this field
+        -> ThicknessField.  Refused for a field without foreground."""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_distance_thickness(self._hip._h, self._owner.h, C.byref(h)))
+        return ThicknessField(self.voxels, _DistanceHandle(h.value), self.complement)
+
     def __repr__(self):
         return f"DistanceField(depth={self.depth}, grid={self.grid}, max_squared={self.max_squared}, argmax={self.argmax}, n={self.n}, complement={self.complement})"
+
+
+class ThicknessField(DistanceField):
+    """The local thickness of a distance field (`DistanceField.thickness`, `Voxels.thickness`): per voxel T = the largest F(c) over the
+    centres c with F(c) > |p - c|^2, the squared radius of the largest ball that fits beside the field's foreground and holds the
+    voxel; 0 on that foreground.  A uint32 in squared voxels, exact.  Of `distance(complement=True)` it is the wall thickness of the
+    solid: a slab w voxels thick reads ceil(w / 2)^2 - 14 gives 49, 17 gives 81 - so 2 sqrt(T) is the wall in voxels, rounded up to even.
+    Of `distance()` it is the local width of the empty space: pores, channels, clearance.
+    `.max_squared`, `.argmax` the largest value and the voxel (i, j, k) of smallest index k N^2 + j N + i that has it; `.min_squared`,
+    `.argmin` the smallest positive one likewise (None when nothing is covered); `.n` the voxels with T > 0; `.balls` how many balls
+    were painted, of `.centres` candidates; `.complement` that of the distance field.  `slices`, `squared_device`, `within` and
+    `beyond` are DistanceField's, on T."""
+
+    def __init__(self, voxels, owner, complement):
+        super().__init__(voxels, owner, complement)
+        c = np.zeros(8, np.uint64)
+        lib().fhip_thickness_info(owner.h, _p(c))
+        N = self.grid
+
+        def voxel(idx):
+            return None if idx == 0xFFFFFFFFFFFFFFFF else (idx % N, idx // N % N, idx // (N * N))
+        self.max_squared, self.argmax, self.n, self.centres, self.balls = int(c[0]), voxel(int(c[1])), int(c[4]), int(c[6]), int(c[7])
+        self.min_squared, self.argmin = (int(c[2]), voxel(int(c[3]))) if self.n else (None, None)
+
+    def thin(self, r=None, squared=None, out=None):
+        """fhip_thickness_thin: the voxels with 0 < T <= t - what no ball larger than that reaches, the walls thinner than about
+        2 sqrt(t) -> Voxels.  `r`, `squared` and `out` as for `within`."""
+        return self._threshold(r, squared, 2, out)
+
+    def histogram(self, edges_squared):
+        """fhip_thickness_histogram: the voxels with e[b] <= T < e[b + 1] for 2 to 1024 ascending edges in squared voxels: numpy uint64
+        [len(edges) - 1], or a torch CUDA int64 tensor for bricks on the device"""
+        edges = np.ascontiguousarray(edges_squared, dtype=np.int64).reshape(-1)
+        if len(edges) < 2 or len(edges) > 1024 or edges.min() < 0 or edges.max() > 0xFFFFFFFF or (np.diff(edges) < 0).any():
+            raise ValueError("histogram: 2 to 1024 ascending edges, each a uint32")
+        edges = edges.astype(np.uint32)
+        if self.voxels.on_device:
+            import torch
+            dev = self.voxels.bricks.device
+            d_edges = torch.from_numpy(edges.view(np.int32)).to(dev)
+            out = torch.empty(len(edges) - 1, dtype=torch.int64, device=dev)
+            self._hip.check(lib().fhip_thickness_histogram(self._hip._h, self._owner.h, _dev_ptr(d_edges), len(edges), _dev_ptr(out), 1))
+            out._edges = d_edges          # (the call is asynchronous and reads them: they live as long as the result)
+            return out
+        out = np.zeros(len(edges) - 1, np.uint64)
+        self._hip.check(lib().fhip_thickness_histogram(self._hip._h, self._owner.h, _p(edges), len(edges), _p(out), 0))
+        return out
+
+    def thickness(self):
+        raise FidgetHipError(6, "thickness: of a distance field, not of a thickness")
+
+    def __repr__(self):
+        return (f"ThicknessField(depth={self.depth}, grid={self.grid}, max_squared={self.max_squared}, argmax={self.argmax}, min_squared={self.min_squared}, "
+                f"argmin={self.argmin}, n={self.n}, balls={self.balls}, complement={self.complement})")
 
 
 class _ComponentsHandle:

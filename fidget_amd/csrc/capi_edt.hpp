@@ -7,6 +7,9 @@ struct fhip_distance {
     uint32_t depth = 0;
     int complement = 0, device = 0;
     uint32_t* d_field = nullptr;          // [N][N][N], [k][j][i]
+    // a local thickness (capi_thick.hpp) is a field like this one - max_d2, arg and n_fg its largest value, where, and its zeros - with more to say
+    int thickness = 0;
+    uint64_t min_d2 = 0, arg_min = ~(uint64_t)0, n_positive = 0, n_centres = 0, n_balls = 0;
     ~fhip_distance() { if (d_field) (void)hipFree(d_field); }
 };
 fhip_status fhip_voxels_distance(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, int complement, void** out) {
@@ -97,7 +100,8 @@ fhip_status fhip_distance_slices(fhip_ctx* ctx, const void* h, uint32_t k0, uint
     HIP_TRY(ctx, hipGetLastError());
     return FHIP_OK;
 }
-fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* h, uint32_t t, int beyond, uint64_t* out_bricks, int out_on_device) {
+// mode: k_edt_threshold's - 0 within, 1 beyond, 2 thin (fhip_thickness_thin)
+static fhip_status distance_threshold(fhip_ctx* ctx, const void* h, uint32_t t, uint32_t mode, uint64_t* out_bricks, int out_on_device) {
     const fhip_distance* const d = (const fhip_distance*)h;
     if (!ctx || !d) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_distance_threshold: context and distance field");
     if (ctx->device != d->device) return fail(ctx, FHIP_ERR_UNSUPPORTED, "distance: computed on another device");
@@ -109,7 +113,10 @@ fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* h, uint32_t t, in
     const uint64_t n_words = fhvox::n_words(d->depth);
     hipError_t e = hipSuccess;
     uint64_t* const d_out = (uint64_t*)st.out(ctx->io_b, out_bricks, (size_t)n_words * 8, e); HIP_TRY(ctx, e);
-    hipLaunchKernelGGL(fhm::k_edt_threshold, cc_grid(n_words), dim3(256), 0, ctx->stream, (const uint32_t*)d->d_field, d->depth, t, beyond ? 1u : 0u, d_out);
+    hipLaunchKernelGGL(fhm::k_edt_threshold, cc_grid(n_words), dim3(256), 0, ctx->stream, (const uint32_t*)d->d_field, d->depth, t, mode, d_out);
     return st.finish();
+}
+fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* h, uint32_t t, int beyond, uint64_t* out_bricks, int out_on_device) {
+    return distance_threshold(ctx, h, t, beyond ? 1u : 0u, out_bricks, out_on_device);
 }
 void fhip_distance_free(void* h) { delete (fhip_distance*)h; }

@@ -1763,6 +1763,8 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 
 // the distance transform of a voxel bitmap (fhip_voxels_distance): a fragment of its own, with the helpers above
 #include "capi_edt.hpp"
+// the local thickness of such a distance field (fhip_distance_thickness): likewise
+#include "capi_thick.hpp"
 // the boundary mesh of a voxel bitmap (fhip_voxels_mesh, fhip_voxels_surface): likewise
 #include "capi_vmesh.hpp"
 // a voxel bitmap along a direction (fhip_voxels_flow, fhip_voxels_overhangs, fhip_voxels_heights): likewise

@@ -7,7 +7,7 @@
 //   k_edt_cols       along j, then along k, in place: a lane takes a column and the lanes of a wave consecutive i, so every load and
 //                    store of the field is a wave-wide run along i.  The lower envelope's stack - 8 bytes an entry, N entries a column -
 //                    is laid out [entry][lane]: in LDS up to N = 64 (32 KiB a wave), in a device workspace above
-//   k_edt_threshold  64 voxels of the field -> one word of a bitmap (d2 <= t, or d2 > t)
+//   k_edt_threshold  64 voxels of the field -> one word of a bitmap (d2 <= t, d2 > t, or 0 < d2 <= t)
 //   k_edt_reduce, k_edt_reduce_sum   the largest finite d2, the smallest index that has it, the number of zeros: per-block partials, then one block
 //   k_edt_copy       layers of the field into a buffer of the caller's
 // No kernel waits for another workgroup; every word written has one writer; integers throughout, so the field is the same in any order.
@@ -95,9 +95,13 @@ __global__ void __launch_bounds__(FH_EDT_LANES) k_edt_cols(uint32_t* __restrict_
     }
 }
 
-// One word of the bitmap per thread: bit lx + 4 ly + 16 lz = (d2 > t) == beyond at voxel (4 bx + lx, 4 by + ly, 4 bz + lz).  Per
+// One word of the bitmap per thread: bit lx + 4 ly + 16 lz = edt_passes at voxel (4 bx + lx, 4 by + ly, 4 bz + lz).  Per
 // (ly, lz) one 16-byte load, a wave's loads a run of 1 KiB along i.  NONE is above every t <= 0xFFFFFFFE: never within, always beyond.
-__global__ void __launch_bounds__(256) k_edt_threshold(const uint32_t* __restrict__ field, uint32_t depth, uint32_t t, uint32_t beyond, uint64_t* __restrict__ out) {
+// mode 0: d2 <= t ("within"); 1: d2 > t ("beyond"); 2: 0 < d2 <= t (the thin parts of a thickness field, thick.hip)
+__device__ __forceinline__ uint32_t edt_passes(uint32_t v, uint32_t t, uint32_t mode) {
+    return mode == 2 ? (uint32_t)(v != 0 && v <= t) : (uint32_t)((v > t) == (mode != 0));
+}
+__global__ void __launch_bounds__(256) k_edt_threshold(const uint32_t* __restrict__ field, uint32_t depth, uint32_t t, uint32_t mode, uint64_t* __restrict__ out) {
     const uint64_t n_words = (uint64_t)1 << (3 * depth), w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
     if (w >= n_words) return;
     const uint32_t N = 4u << depth, Bm = (1u << depth) - 1;
@@ -106,8 +110,7 @@ __global__ void __launch_bounds__(256) k_edt_threshold(const uint32_t* __restric
     for (uint32_t r = 0; r < 16; r++) {
         const uint32_t j = 4 * by + (r & 3), k = 4 * bz + (r >> 2);
         const uint4 v = *(const uint4*)(field + ((size_t)k * N + j) * N + 4 * bx);
-        const uint32_t nib = (uint32_t)((v.x > t) == (beyond != 0)) | ((uint32_t)((v.y > t) == (beyond != 0)) << 1) | ((uint32_t)((v.z > t) == (beyond != 0)) << 2) |
-                             ((uint32_t)((v.w > t) == (beyond != 0)) << 3);
+        const uint32_t nib = edt_passes(v.x, t, mode) | (edt_passes(v.y, t, mode) << 1) | (edt_passes(v.z, t, mode) << 2) | (edt_passes(v.w, t, mode) << 3);
         word |= (uint64_t)nib << (4 * r);
     }
     out[w] = word;

@@ -1249,6 +1249,8 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 
 // k_edt_*: the exact distance transform of such a bitmap (fhip_voxels_distance) - its own file
 #include "edt.hip"
+// k_lt_*: the local thickness of such a distance field (fhip_distance_thickness) - its own file
+#include "thick.hip"
 // k_vm_*: the boundary mesh of such a bitmap (fhip_voxels_mesh, fhip_voxels_surface) - its own file
 #include "vmesh.hip"
 // k_flow_*, k_overhangs, k_heights*: such a bitmap along a direction (fhip_voxels_flow, _overhangs, _heights) - its own file

@@ -484,6 +484,31 @@ const uint32_t* fhip_distance_dev(const void* dist);
 fhip_status fhip_distance_threshold(fhip_ctx* ctx, const void* dist, uint32_t t, int beyond, uint64_t* out_bricks, int out_on_device);
 void fhip_distance_free(void* dist);
 
+/* ---- local thickness of a distance field: per voxel the largest ball that fits and holds it ----------
+ * (Hildebrand & Rueegsegger's local thickness, BoneJ's Tb.Th.  No counterpart in the reference; the definition below is the specification.)
+ * Let F be a finished field of fhip_voxels_distance.  For every voxel p of the grid T(p) = max { F(c) : c a voxel of the grid,
+ * F(c) > |p - c|^2 }, and 0 where there is no such c: the open ball of squared radius F(c) around c holds no foreground voxel, so
+ * T(p) > 0 exactly where F(p) > 0, and there T(p) >= F(p).  T is in squared voxels like F.  Balls that poke out of the grid are clipped;
+ * outside the grid there is neither foreground nor a centre.  Of the field to the clear bits (complement != 0) T is the wall thickness of
+ * the solid - a slab w voxels thick reads ceil(w / 2)^2, so 2 sqrt(T) is the wall in voxels, rounded up to even; of the field to the set
+ * bits it is the local width of the empty space.
+ * fhip_distance_thickness: blocking.  The result is a distance handle whose field is T: fhip_distance_slices, _threshold, _dev, _free
+ * and _info ({largest T, its smallest index, voxels with T == 0, depth}) apply unchanged.  It allocates one more field of N^3 uint32 and,
+ * while it runs, N^3 / 8 bytes of flags and three tables of max F + 1 words.  A centre whose ball lies inside the ball of one of its 26
+ * neighbours is not painted - that leaves T as it is; the kept balls are scattered with integer atomic maxima, so T does not depend on
+ * the order of arrival.  FHIP_ERR_UNSUPPORTED: a field on another device, a field without foreground (all 0xFFFFFFFF: no bounded
+ * ball), a field that is itself a thickness.
+ * fhip_thickness_info: {largest T, its smallest index (k * N + j) * N + i, smallest positive T, its smallest index, voxels with T > 0,
+ * depth, centres (F > 0), balls painted}.  With T all 0: {0, 0, 0, UINT64_MAX, 0, ...}.  A null handle: zeros and UINT64_MAX twice.
+ * fhip_thickness_thin: fhip_distance_threshold's bitmap of the voxels with 0 < T <= t, the parts thinner than 2 sqrt(t).
+ * fhip_thickness_histogram: counts[b] = the voxels with edges[b] <= T < edges[b + 1] for b < n_edges - 1; 2 <= n_edges <= 1024, the
+ * edges ascending (equal neighbours make an empty bin; on the host this is checked).  on_device != 0: edges (4-byte aligned) and counts
+ * (8-byte aligned) are device pointers and the call is asynchronous on the context's stream. */
+fhip_status fhip_distance_thickness(fhip_ctx* ctx, const void* dist, void** out);
+void fhip_thickness_info(const void* thick, uint64_t out[8]);
+fhip_status fhip_thickness_thin(fhip_ctx* ctx, const void* thick, uint32_t t, uint64_t* out_bricks, int out_on_device);
+fhip_status fhip_thickness_histogram(fhip_ctx* ctx, const void* thick, const uint32_t* edges, uint32_t n_edges, uint64_t* counts, int on_device);
+
 /* ---- boundary mesh of a voxel bitmap: the solid's faces as triangles, its surface area, its Euler number ----------
  * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification, exact and in integers.)
  * GRID.  fhip_shape_voxels': B = 1 << depth bricks and N = 4 B voxels per axis, voxel (i, j, k) bit lx + 4 ly + 16 lz of word

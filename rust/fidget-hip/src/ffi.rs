@@ -156,6 +156,11 @@ extern "C" {
     pub fn fhip_distance_dev(dist: *const c_void) -> *const u32;
     pub fn fhip_distance_threshold(ctx: *mut fhip_ctx, dist: *const c_void, t: u32, beyond: c_int, out_bricks: *mut u64, out_on_device: c_int) -> fhip_status;
     pub fn fhip_distance_free(dist: *mut c_void);
+    // the local thickness of such a field: the result is a distance handle again, served by the functions above
+    pub fn fhip_distance_thickness(ctx: *mut fhip_ctx, dist: *const c_void, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_thickness_info(thick: *const c_void, out: *mut u64);       // largest T, its index, smallest positive T, its index, voxels with T > 0, depth, centres, balls painted
+    pub fn fhip_thickness_thin(ctx: *mut fhip_ctx, thick: *const c_void, t: u32, out_bricks: *mut u64, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_thickness_histogram(ctx: *mut fhip_ctx, thick: *const c_void, edges: *const u32, n_edges: u32, counts: *mut u64, on_device: c_int) -> fhip_status;
     // the boundary mesh of a voxel bitmap - a fhip_mesh like fhip_mesh_build's - and its surface summary {faces [6], V, E, F, n}
     pub fn fhip_voxels_surface(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, out: *mut u64) -> fhip_status;
     pub fn fhip_voxels_mesh(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, out: *mut *mut fhip_mesh) -> fhip_status;
