@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -60,6 +60,7 @@ EXPORTS = [
     "fhip_distance_thickness", "fhip_thickness_info", "fhip_thickness_thin", "fhip_thickness_histogram",
     "fhip_voxels_surface", "fhip_voxels_mesh",
     "fhip_voxels_flow", "fhip_voxels_overhangs", "fhip_voxels_heights",
+    "fhip_triangles_voxels", "fhip_mesh_voxels",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -201,6 +202,7 @@ def lib():
             "fhip_voxels_surface": (i32, [vp, vp, u32, i32, vp]), "fhip_voxels_mesh": (i32, [vp, vp, u32, i32, vp]),
             "fhip_voxels_flow": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, i32]), "fhip_voxels_overhangs": (i32, [vp, vp, u32, i32, u32, u32, i32, vp, i32]),
             "fhip_voxels_heights": (i32, [vp, vp, u32, i32, u32, vp, i32]),
+            "fhip_triangles_voxels": (i32, [vp, vp, u64, vp, u64, i32, vp, u32, vp, i32, vp]), "fhip_mesh_voxels": (i32, [vp, vp, vp, u32, vp, i32, vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -263,7 +265,7 @@ class HipContext:
         self.check(lib().fhip_ctx_sync(self._h))
 
     def trim(self):
-        """fhip_ctx_trim: memory kept between calls for speed alone (mesh leaf records, frame lanes) goes back to the device"""
+        """fhip_ctx_trim: memory kept between calls for speed alone (mesh leaf records and the scratch of `voxelize_mesh` in the same buffer, frame lanes) goes back to the device"""
         self.check(lib().fhip_ctx_trim(self._h))
 
     def reserve_arena(self, megabytes):
@@ -1141,6 +1143,10 @@ class Mesh:
         self._hip.check(st)
         return res
 
+    def voxelize(self, depth, out=None):
+        """`voxelize_mesh(self, depth, out=out)`: the solid this mesh encloses as a Voxels, from the resident arrays where there are any"""
+        return voxelize_mesh(self, depth, out=out)
+
     def vertices_device(self):
         """The vertices where the dual walk left them in device memory ([m, 3] float32), as an object carrying
         `__cuda_array_interface__` that keeps the mesh alive - `torch.as_tensor(obj, device="cuda")` views it; None when the
@@ -1850,6 +1856,102 @@ def voxelize(shape, depth, world_to_model=None, vars=None, out=None):
         raise ValueError("MissingVar")
     hip.check(st)
     return Voxels(hip, bricks(), depth, dict(zip(("cells", "full", "empty", "leaf_cells"), (int(v) for v in cells))))
+
+
+# ---- a triangle mesh back into the library: binary STL in, voxel bitmap out (fhip_triangles_voxels, fhip_mesh_voxels) ------------
+def read_stl(path_or_bytes):
+    """A binary STL file -> its triangles, float32 [T, 3, 3] (triangle, corner, xyz), read on the host; the file's normals and
+    attribute words are ignored.  `path_or_bytes`: a path, or the file's bytes (bytes, bytearray, memoryview, a numpy uint8 array such
+    as `Mesh.stl()` returns).  ASCII STL is refused with a ValueError."""
+    if isinstance(path_or_bytes, (str, os.PathLike)):
+        with open(path_or_bytes, "rb") as f:
+            data = f.read()
+    elif isinstance(path_or_bytes, np.ndarray):
+        data = np.ascontiguousarray(path_or_bytes).view(np.uint8).tobytes()
+    else:
+        data = bytes(path_or_bytes)
+    n = int.from_bytes(data[80:84], "little") if len(data) >= 84 else -1
+    if n < 0 or len(data) != 84 + 50 * n:
+        if data.lstrip()[:5].lower() == b"solid":
+            raise ValueError("read_stl: this is an ASCII STL file; only binary STL is read")
+        raise ValueError(f"read_stl: not a binary STL file: {len(data)} bytes, but its header counts {n} triangles" if n >= 0 else "read_stl: not a binary STL file: shorter than its header")
+    rec = np.frombuffer(data, np.uint8, 50 * n, 84).reshape(n, 50)
+    return np.ascontiguousarray(rec[:, 12:48]).view("<f4").astype(np.float32).reshape(n, 3, 3)
+
+
+MESH_INFO = ("triangles", "rejected", "flat", "crossings", "clipped", "open_rows", "set_voxels", "W")
+
+
+def voxelize_mesh(mesh, depth, mesh_to_world=None, out=None, hip=None):
+    """fhip_triangles_voxels / fhip_mesh_voxels: the solid a closed triangle mesh encloses, on the grid of 4 << depth voxels per axis
+    over [-1, 1]^3, by parity counting along +x (even-odd: nested sheets make cavities) -> Voxels; the definition, exact in integers
+    after the vertices are snapped to 1/256 voxel, stands in include/fidget_hip.h.  `mesh`: a `Mesh` (its resident device arrays are
+    read where they are); float32 [T, 3, 3] triangles as `read_stl` returns them, a numpy array or a torch CUDA tensor; or a pair
+    (vertices [V, 3] float32, triangles [T, 3] indices), both numpy or both torch CUDA (indices int64).  `mesh_to_world`: a 3 x 4
+    matrix (or 4 x 4, whose first three rows are used), applied in float64 before the snap.  `out` as for `voxelize`.  `hip`: the context for
+    arrays (default: `default_context()`; a `Mesh` brings its own).  A pair may be a tuple or a list of the two arrays.  The result's
+    `.cells` are all zeros and `.mesh_info` = {triangles, rejected, flat, crossings, clipped, open_rows, set_voxels, W}: open_rows > 0 shows
+    a mesh that is not closed.  ValueError when triangles were rejected: a vertex not finite or outside [-1.5, 1.5], or an index
+    beyond the vertices."""
+    depth = int(depth)
+    m2w = None
+    if mesh_to_world is not None:
+        m2w = np.ascontiguousarray(np.asarray(mesh_to_world, np.float64).reshape(-1)[:12])
+        assert m2w.size == 12, "mesh_to_world: 3 x 4 or 4 x 4"
+    keep = None          # what the pointers point into, until the call returns
+    if isinstance(mesh, Mesh):
+        hip = mesh._hip
+    else:
+        hip = hip or default_context()
+        # a pair is a tuple or a list of two arrays; a nested list of numbers is the [T, 3, 3] form
+        pair = isinstance(mesh, (tuple, list)) and len(mesh) == 2 and all(hasattr(a, "shape") for a in mesh)
+        if isinstance(mesh, (tuple, list)) and not pair and any(hasattr(a, "shape") for a in mesh):
+            raise TypeError("voxelize_mesh: a mesh is a Mesh, [T, 3, 3] triangles, or a pair (vertices [V, 3], triangles [T, 3]) of two arrays")
+        verts, tris = mesh if pair else (mesh, None)
+        if isinstance(verts, np.ndarray) or not hasattr(verts, "is_cuda"):
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+            vp, dev = _p(verts), 0
+            if tris is not None:
+                tris = np.ascontiguousarray(tris, np.uint64).reshape(-1, 3)
+            tp = _p(tris)
+        else:
+            assert verts.is_cuda and verts.element_size() == 4 and verts.is_floating_point(), "vertices on the device: a float32 CUDA tensor"
+            verts = verts.contiguous().reshape(-1, 3)
+            vp, dev = _dev_ptr(verts), 1
+            if tris is not None:
+                assert tris.is_cuda and tris.element_size() == 8 and not tris.is_floating_point(), "triangles on the device: an int64 CUDA tensor"
+                tris = tris.contiguous().reshape(-1, 3)
+            tp = _dev_ptr(tris)
+        n_verts = int(verts.shape[0])
+        n_tris = int(tris.shape[0]) if tris is not None else n_verts // 3
+        keep = (verts, tris)
+    B = 1 << depth
+    words = int(lib().fhip_voxels_words(depth))       # (0 beyond depth 10: the call below refuses before it touches `out`)
+    if out is not None and not isinstance(out, np.ndarray):
+        import torch
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
+        ptr, out_dev = _dev_ptr(out), 1
+        bricks = (lambda: out.reshape(-1).view(torch.int64)[:words].view(B, B, B))
+    else:
+        if out is None:
+            out = np.zeros((B, B, B) if words else 0, np.uint64)
+        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
+        ptr, out_dev = _p(out), 0
+        bricks = (lambda: out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B))
+    info = np.zeros(8, np.uint64)
+    if isinstance(mesh, Mesh):
+        st = lib().fhip_mesh_voxels(hip._h, mesh._owner.h, _p(m2w), depth, ptr, out_dev, _p(info))
+    else:
+        st = lib().fhip_triangles_voxels(hip._h, vp, n_verts, tp, n_tris, dev, _p(m2w), depth, ptr, out_dev, _p(info))
+    del keep
+    hip.check(st)
+    res = Voxels(hip, bricks(), depth, {"cells": 0, "full": 0, "empty": 0, "leaf_cells": 0})
+    res.mesh_info = dict(zip(MESH_INFO, (int(v) for v in info)))
+    res._n = res.mesh_info["set_voxels"]
+    if res.mesh_info["rejected"]:
+        raise ValueError(f"voxelize_mesh: {res.mesh_info['rejected']} of {res.mesh_info['triangles']} triangles rejected: a vertex that is not finite or "
+                         "lies outside [-1.5, 1.5] after mesh_to_world, or an index beyond the vertices")
+    return res
 
 
 # ---- contours of a 2D slice: vertices on the crossing lattice edges, directed segments, loops, SVG (fhip_contour2d) -----------

@@ -1769,3 +1769,5 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 #include "capi_vmesh.hpp"
 // a voxel bitmap along a direction (fhip_voxels_flow, fhip_voxels_overhangs, fhip_voxels_heights): likewise
 #include "capi_flow.hpp"
+// a triangle mesh to a voxel bitmap (fhip_triangles_voxels, fhip_mesh_voxels): likewise
+#include "capi_trivox.hpp"

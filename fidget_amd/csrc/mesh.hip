@@ -1255,3 +1255,5 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 #include "vmesh.hip"
 // k_flow_*, k_overhangs, k_heights*: such a bitmap along a direction (fhip_voxels_flow, _overhangs, _heights) - its own file
 #include "flow.hip"
+// k_tv_*: a triangle mesh to such a bitmap (fhip_triangles_voxels, fhip_mesh_voxels) - its own file
+#include "trivox.hip"

@@ -47,7 +47,8 @@ void fhip_ctx_destroy(fhip_ctx* ctx);
 const char* fhip_last_error(const fhip_ctx* ctx);
 fhip_status fhip_ctx_sync(fhip_ctx* ctx);
 /* Gives back the device and pinned memory a context keeps between calls for speed alone: the mesher's leaf records (17 GB after a
- * depth-10 build), its landing area, the frame lanes (child contexts with buffers of their own - up to four, each a context's worth of
+ * depth-10 build) - the same buffer holds the scratch of fhip_triangles_voxels, 64 bytes per triangle of the largest mesh so far -
+ * its landing area, the frame lanes (child contexts with buffers of their own - up to four, each a context's worth of
  * buffers: option frame_lanes).  Waits for the context's work; whatever is needed again is made again by the call that needs it. */
 fhip_status fhip_ctx_trim(fhip_ctx* ctx);
 /* The tape arena of a buffer set is sized by need: 128 MB, or about a byte per voxel for a 3D frame whose root tape reads an input that
@@ -573,6 +574,54 @@ fhip_status fhip_voxels_overhangs(fhip_ctx* ctx, const uint64_t* bricks, uint32_
                                   uint32_t reach2, int bed, uint64_t* out, int out_on_device);
 fhip_status fhip_voxels_heights(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t axis,
                                 int32_t* out, int out_on_device);
+
+/* ---- a triangle mesh to a voxel bitmap: solid voxelization by parity along +x --------------------------------------
+ * (No counterpart in the reference, which has no voxel bitmap: the definition below is the specification, exact and in integers after
+ * the snap, and the result is the same from run to run and under any order of the triangles - XOR commutes.)
+ * GRID.  fhip_shape_voxels': B = 1 << depth bricks and N = 4 B voxels per axis over [-1, 1]^3, depth <= 10, voxel (i, j, k) bit
+ * lx + 4 ly + 16 lz of word (bz B + by) B + bx.  Each triangle writes one toggle bit per column (j, k) it covers; a prefix XOR along x
+ * turns the toggles into the solid (even-odd: two nested closed sheets enclose a cavity).
+ * SNAP.  A vertex coordinate v (float32) goes through the optional `mesh_to_world`, a row-major 3 x 4 matrix of doubles (NULL: the
+ * identity), evaluated in binary64 as ((m0 x + m1 y) + m2 z) + m3 with no contraction: w.  q = llrint(w (128 N) + 128 N), rounding to
+ * nearest-even, in lattice units of 1/256 voxel: voxel i has its centre at 256 i + 128, and a vertex that fhip_voxels_mesh makes at
+ * float(2 a - N) / N snaps to exactly 256 a.
+ * REJECTED.  A triangle is skipped, and counted in `rejected`, if any vertex coordinate w is not finite or lies outside [-1.5, 1.5] -
+ * decided on w, before any conversion to an integer - or if one of its indices is at or beyond n_vertices, which is never read.
+ * FLAT.  Projected to the yz plane, D = (b.y - a.y)(c.z - a.z) - (b.z - a.z)(c.y - a.y).  D == 0: the triangle is edge-on or
+ * degenerate, skipped and counted in `flat`.  D < 0: b and c change places and D its sign, so that the inside lies to the left of
+ * every edge.
+ * COVER.  Column (j, k) is the point P = (256 j + 128, 256 k + 128).  For each directed edge p -> r of (b -> c, c -> a, a -> b),
+ * e = (r.y - p.y)(P.z - p.z) - (r.z - p.z)(P.y - p.y).  P is covered iff every e > 0, or e == 0 and the edge owns its points: an edge
+ * owns its points when r.y - p.y > 0, or when r.y - p.y == 0 and r.z - p.z < 0 - the rasterizer's fill rule: a point on an edge or a
+ * vertex that two or more triangles share is counted once per sheet.  Only columns with 0 <= j, k < N are visited.
+ * CROSSING.  With the three e as weights (w_a = e(b -> c), w_b = e(c -> a), w_c = e(a -> b), sum = D), xmin = min(a.x, b.x, c.x) and
+ * num = w_a (a.x - xmin) + w_b (b.x - xmin) + w_c (c.x - xmin), the crossing lies at xmin + num / D and toggles every voxel whose centre
+ * is at or beyond it: i* = ceil((num - (128 - xmin) D) / (256 D)), the exact quotient rounded up.  i* <= 0 toggles voxel (0, j, k);
+ * i* >= N toggles the column's bit in an exit plane of N x N bits and counts the crossing in `clipped`; otherwise (i*, j, k).
+ * FILL.  inside(i, j, k) = the XOR of the toggles at (0 .. i, j, k).  `open_rows` is the number of columns where inside(N - 1, j, k)
+ * XOR the exit plane's bit is 1: a row with an odd number of crossings shows that the mesh is not closed.  A closed mesh gives 0, also
+ * where it pokes out of the cube.
+ * BIT BUDGET.  Everything in int64: coordinates in [-64 N, 320 N], spans at most 384 N = 1.5 2^20 at depth 10, D <= span^2 < 2^41.2,
+ * edge values off the triangle below 2^42.2, num <= span^3 < 2^61.8, |(128 - xmin) D| < 2^61.5, their difference below 2^63, the
+ * divisor 256 D below 2^50.  The division is made once per covered column.
+ * fhip_triangles_voxels: `vertices` 3 f32 each; `triangles` 3 u64 indices each, or NULL for a soup in which every three vertices are
+ * a triangle.  on_device != 0: both are device pointers (4- and 8-byte aligned), otherwise host arrays, which get device memory of
+ * their own for the call.  `out`: fhip_voxels_words(depth) words, written completely - a device pointer (8-byte aligned) with
+ * out_on_device != 0, otherwise a host buffer, staged.  info = {triangles, rejected, flat, crossings (covered columns, clipped ones
+ * included), clipped, open_rows, set voxels, W = the columns under the triangles' boxes, the items of work}, a host array: the call
+ * blocks.  n_triangles == 0 gives an all-zero bitmap.  A set-up pass, prefix sums, a pass over the W (triangle, column) items with one
+ * 64-bit atomic XOR per covered column, the fill; no pass waits for another workgroup.  Refused before `out` is touched: a NULL
+ * context, `out` or `info` (FHIP_ERR_BAD_TAPE); depth > 10, NULL vertices with triangles to read, a misaligned device pointer
+ * (FHIP_ERR_UNSUPPORTED); n_triangles >= 2^32 (FHIP_ERR_OVERFLOW).  W >= 2^40 is FHIP_ERR_OVERFLOW too, decided after the set-up: a
+ * device `out` has then been cleared to zeros and holds no result, a host `out` has not been written.  The call's scratch, 64 bytes
+ * per triangle, stays with the context afterwards, in the buffer of the mesher's leaf records: fhip_ctx_trim gives it back.
+ * fhip_mesh_voxels: the same for a fhip_mesh, from its device arrays where they are resident (fhip_mesh_vertices_dev), otherwise
+ * from its host arrays. */
+fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t n_vertices, const uint64_t* triangles /* NULL: a soup */,
+                                  uint64_t n_triangles, int on_device, const double* mesh_to_world /* 3 x 4 or NULL */, uint32_t depth,
+                                  uint64_t* out, int out_on_device, uint64_t info[8]);
+fhip_status fhip_mesh_voxels(fhip_ctx* ctx, const fhip_mesh* mesh, const double* mesh_to_world, uint32_t depth,
+                             uint64_t* out, int out_on_device, uint64_t info[8]);
 
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's

@@ -167,6 +167,11 @@ extern "C" {
     pub fn fhip_voxels_flow(ctx: *mut fhip_ctx, seeds: *const u64, blockers: *const u64, depth: u32, on_device: c_int, dir: u32, flags: u32, out: *mut u64, out_on_device: c_int) -> fhip_status;
     pub fn fhip_voxels_overhangs(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, up: u32, reach2: u32, bed: c_int, out: *mut u64, out_on_device: c_int) -> fhip_status;
     pub fn fhip_voxels_heights(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, axis: u32, out: *mut i32, out_on_device: c_int) -> fhip_status;
+    // a triangle mesh to a voxel bitmap by parity along +x; info = {triangles, rejected, flat, crossings, clipped, open_rows, set voxels, W}
+    pub fn fhip_triangles_voxels(ctx: *mut fhip_ctx, vertices: *const f32, n_vertices: u64, triangles: *const u64, n_triangles: u64, on_device: c_int,
+                                 mesh_to_world: *const f64, depth: u32, out: *mut u64, out_on_device: c_int, info: *mut u64) -> fhip_status;
+    pub fn fhip_mesh_voxels(ctx: *mut fhip_ctx, mesh: *const fhip_mesh, mesh_to_world: *const f64, depth: u32, out: *mut u64, out_on_device: c_int,
+                            info: *mut u64) -> fhip_status;
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

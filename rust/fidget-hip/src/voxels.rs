@@ -65,3 +65,41 @@ pub fn voxelize(b: &BoundShape<HipFunction, f32>, settings: &Settings) -> Option
     });
     if st != 0 { None } else { Some(Voxels { bricks, depth, cells }) }
 }
+
+/// What a mesh's voxelization reports: `[triangles, rejected, flat, crossings, clipped, open_rows, set voxels, W]`; `open_rows > 0`
+/// shows a mesh that is not closed
+pub type MeshInfo = [u64; 8];
+
+/// The solid a closed triangle mesh encloses (`fhip_triangles_voxels`: parity counting along +x, exact in integers after the vertices
+/// are snapped to 1/256 voxel) on the grid of `4 << depth` voxels per axis over `[-1, 1]^3`.  `triangles`: vertex indices, or `None`
+/// for a soup in which every three vertices are a triangle; `mesh_to_world`: a row-major 3 x 4 matrix.  The bitmap's `cells` are zeros.
+/// `None` when the call is refused.
+pub fn voxelize_triangles(vertices: &[[f32; 3]], triangles: Option<&[[u64; 3]]>, mesh_to_world: Option<&[f64; 12]>, depth: u32) -> Option<(Voxels, MeshInfo)> {
+    let words = unsafe { ffi::fhip_voxels_words(depth) } as usize;
+    if words == 0 {
+        return None;
+    }
+    let mut bricks = vec![0u64; words];
+    let mut info = [0u64; 8];
+    let n_triangles = triangles.map_or(vertices.len() / 3, |t| t.len()) as u64;
+    let st = CTX.with(|c| unsafe {
+        ffi::fhip_triangles_voxels(c.raw(), vertices.as_ptr() as *const f32, vertices.len() as u64, triangles.map_or(std::ptr::null(), |t| t.as_ptr() as *const u64),
+                                   n_triangles, 0, mesh_to_world.map_or(std::ptr::null(), |m| m.as_ptr()), depth, bricks.as_mut_ptr(), 0, info.as_mut_ptr())
+    });
+    if st != 0 { None } else { Some((Voxels { bricks, depth, cells: [0; 4] }, info)) }
+}
+
+/// The same for a mesh the library built (`fhip_mesh_voxels`), read from its device arrays where they are resident.
+///
+/// # Safety
+/// `mesh` must be a live `fhip_mesh` of this library.
+pub unsafe fn voxelize_built_mesh(mesh: *const ffi::fhip_mesh, mesh_to_world: Option<&[f64; 12]>, depth: u32) -> Option<(Voxels, MeshInfo)> {
+    let words = ffi::fhip_voxels_words(depth) as usize;
+    if words == 0 {
+        return None;
+    }
+    let mut bricks = vec![0u64; words];
+    let mut info = [0u64; 8];
+    let st = CTX.with(|c| ffi::fhip_mesh_voxels(c.raw(), mesh, mesh_to_world.map_or(std::ptr::null(), |m| m.as_ptr()), depth, bricks.as_mut_ptr(), 0, info.as_mut_ptr()));
+    if st != 0 { None } else { Some((Voxels { bricks, depth, cells: [0; 4] }, info)) }
+}
