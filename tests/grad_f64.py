@@ -5,7 +5,7 @@ Nothing here reads the product's tapes, the oracle, or their models of the refer
 taken AT a non-differentiable point - follows the reference, and each such convention names the line it restates (fidget-core/src/types/grad.rs).
 
   Rec      wraps any backend's Context (oracle, fidget_amd, or None), forwards each call and keeps its own tree, so that one expression
-           exists on the backend and here.
+           exists on the backend and here.  Inputs are x, y, z (keys 0, 1, 2 of `evaluate`'s inputs) and var(i) (key ("v", i)).
   read_vm  the .vm text format of models/ into a Rec.
   D        a value and P partials per point, float64.
   evaluate a Rec node at seeded inputs; also reports which points lie within `tol` of a tie or a step.
@@ -242,6 +242,7 @@ class Rec:
     def x(self): return self._new(("in", 0), self._fwd("x"))
     def y(self): return self._new(("in", 1), self._fwd("y"))
     def z(self): return self._new(("in", 2), self._fwd("z"))
+    def var(self, index): return self._new(("in", ("v", int(index))), self._fwd("var", int(index)))   # Var::V(index); input key ("v", index)
     def constant(self, f): return self._new(("const", float(np.float32(f))), self._fwd("constant", f))
 
     def unary(self, op, a):

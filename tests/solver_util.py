@@ -234,6 +234,16 @@ def quadratic_ok(mat, sol, x):  # lib.rs:595-612
     return linear_ok(mat, sol, quadratic_col(np.asarray(x, np.float32)))
 
 
+def trans_system(be):
+    """sin, cos, exp, ln (the device's restated libm routines) and min / max (the gradient picked by value)"""
+    c = be.Context()
+    x, y = c.x(), c.y()
+    a = c.sub(c.add(c.sin(x), c.cos(c.mul(y, c.constant(0.7)))), c.constant(0.5))
+    b = c.sub(c.add(c.exp(c.mul(x, c.constant(0.3))), c.ln(c.add(c.square(y), c.constant(1.5)))), c.constant(2.0))
+    m = c.sub(c.max(c.min(x, c.mul(y, c.constant(0.5))), c.sub(y, c.constant(3.0))), c.constant(0.25))
+    return [_shape(be, c, a), _shape(be, c, b), _shape(be, c, m)], ["x", "y"], [True, True]
+
+
 KATS = {"basic_solver": basic_solver, "four_vars_at_once": four_vars_at_once, "four_vars_independent": four_vars_independent,
         "xy_nonlinear": xy_nonlinear, "one_var_no_solution": one_var_no_solution, "banana_0": banana((0.0, 0.0)),
         "banana_1": banana((1.0, 1.0)), "circle_0": circle((0.0, 0.0)), "circle_1": circle((1.0, 1.5))}

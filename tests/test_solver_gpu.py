@@ -98,14 +98,7 @@ def test_reference_quadratic_bit_for_bit(n, count):
     assert sum(U.quadratic_ok(mats[i], sols[i], outs[i]) for i in range(count)) >= count * 9 // 10
 
 
-def trans_system(be):
-    """sin, cos, exp, ln (the device's restated libm routines) and min / max (the gradient picked by value)"""
-    c = be.Context()
-    x, y = c.x(), c.y()
-    a = c.sub(c.add(c.sin(x), c.cos(c.mul(y, c.constant(0.7)))), c.constant(0.5))
-    b = c.sub(c.add(c.exp(c.mul(x, c.constant(0.3))), c.ln(c.add(c.square(y), c.constant(1.5)))), c.constant(2.0))
-    m = c.sub(c.max(c.min(x, c.mul(y, c.constant(0.5))), c.sub(y, c.constant(3.0))), c.constant(0.25))
-    return [be.Shape(c, a), be.Shape(c, b), be.Shape(c, m)], ["x", "y"], [True, True]
+trans_system = U.trans_system
 
 
 def test_transcendental_and_min_max_constraints_bit_for_bit():
