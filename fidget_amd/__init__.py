@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -61,6 +61,8 @@ EXPORTS = [
     "fhip_voxels_surface", "fhip_voxels_mesh",
     "fhip_voxels_flow", "fhip_voxels_overhangs", "fhip_voxels_heights",
     "fhip_triangles_voxels", "fhip_mesh_voxels",
+    "fhip_triangles_topology", "fhip_mesh_topology", "fhip_topology_counts", "fhip_topology_vertex_rows", "fhip_topology_vertices", "fhip_topology_triangles", "fhip_topology_triangle_shells",
+    "fhip_topology_vertices_dev", "fhip_topology_triangles_dev", "fhip_topology_triangle_shells_dev", "fhip_topology_shells", "fhip_topology_edges", "fhip_topology_free",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -203,6 +205,11 @@ def lib():
             "fhip_voxels_flow": (i32, [vp, vp, vp, u32, i32, u32, u32, vp, i32]), "fhip_voxels_overhangs": (i32, [vp, vp, u32, i32, u32, u32, i32, vp, i32]),
             "fhip_voxels_heights": (i32, [vp, vp, u32, i32, u32, vp, i32]),
             "fhip_triangles_voxels": (i32, [vp, vp, u64, vp, u64, i32, vp, u32, vp, i32, vp]), "fhip_mesh_voxels": (i32, [vp, vp, vp, u32, vp, i32, vp]),
+            "fhip_triangles_topology": (i32, [vp, vp, u64, vp, u64, i32, i32, u32, vp]), "fhip_mesh_topology": (i32, [vp, vp, i32, u32, vp]),
+            "fhip_topology_counts": (None, [vp, vp]), "fhip_topology_vertex_rows": (u64, [vp]), "fhip_topology_vertices": (i32, [vp, vp]),
+            "fhip_topology_triangles": (i32, [vp, vp]), "fhip_topology_triangle_shells": (i32, [vp, vp]), "fhip_topology_vertices_dev": (vp, [vp]),
+            "fhip_topology_triangles_dev": (vp, [vp]), "fhip_topology_triangle_shells_dev": (vp, [vp]),
+            "fhip_topology_shells": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]), "fhip_topology_edges": (i32, [vp, vp, u32, vp, i32]), "fhip_topology_free": (None, [vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1147,6 +1154,10 @@ class Mesh:
         """`voxelize_mesh(self, depth, out=out)`: the solid this mesh encloses as a Voxels, from the resident arrays where there are any"""
         return voxelize_mesh(self, depth, out=out)
 
+    def topology(self, weld=None):
+        """`mesh_topology(self, weld)`: what kind of mesh this is - edges, shells, volume - from the resident arrays where there are any"""
+        return mesh_topology(self, weld)
+
     def vertices_device(self):
         """The vertices where the dual walk left them in device memory ([m, 3] float32), as an object carrying
         `__cuda_array_interface__` that keeps the mesh alive - `torch.as_tensor(obj, device="cuda")` views it; None when the
@@ -1951,6 +1962,151 @@ def voxelize_mesh(mesh, depth, mesh_to_world=None, out=None, hip=None):
     if res.mesh_info["rejected"]:
         raise ValueError(f"voxelize_mesh: {res.mesh_info['rejected']} of {res.mesh_info['triangles']} triangles rejected: a vertex that is not finite or "
                          "lies outside [-1.5, 1.5] after mesh_to_world, or an index beyond the vertices")
+    return res
+
+
+# ---- the check of a triangle mesh: weld, edges, shells, volume (fhip_triangles_topology, fhip_mesh_topology) ----------------------
+TOPOLOGY_COUNTS = ("triangles", "rejected", "degenerate", "vertices", "edges", "boundary", "flipped", "nonmanifold", "unbalanced", "shells", "vertex_slots", "edge_slots")
+EDGE_KINDS = ("boundary", "flipped", "nonmanifold", "unbalanced")
+
+
+class _TopologyHandle:
+    """owner of an fhip_topology whose device arrays the views borrow"""
+    def __init__(self, h):
+        self.h = h
+        self._free = lib().fhip_topology_free      # (held here, as _MeshHandle holds its own)
+
+    def __del__(self):
+        if self.h and self._free is not None:
+            self._free(self.h)
+            self.h = None
+
+
+class Topology:
+    """What `mesh_topology` found.  `.counts`: {triangles, rejected, degenerate, vertices, edges, boundary, flipped, nonmanifold,
+    unbalanced, shells, vertex_slots, edge_slots}; `.closed`: no unbalanced edge - what parity filling needs; `.manifold`: no boundary,
+    flipped or nonmanifold edge; `.euler` = vertices - edges + (triangles - degenerate).  `.vertices` [V, 3] float32 and `.triangles`
+    [T, 3] uint64: the indexed mesh - welded, or as given - which goes straight into `voxelize_mesh` as the pair
+    `(t.vertices, t.triangles)`; `.triangle_shell` [T] uint32, 0xFFFFFFFF for a degenerate triangle; `.shells`: a dict of arrays, one
+    row per shell in the order of their first triangles - triangles, first, unbalanced, lo, hi, volume6, area2; a shell with volume6 < 0
+    is an inward-facing cavity.  `.volume` = sum(volume6) / 6 and `.area` = sum(area2) / 2, added on the host in shell order.  The
+    host arrays are copied from the device when first asked for.  Every integer is the same from run to run; volume6 and area2 are
+    float64 sums of the same terms in an order of arrival that may differ from run to run, and they alone."""
+    def __init__(self, owner, hip):
+        self._owner, self._hip = owner, hip
+        c = np.zeros(16, np.uint64)
+        lib().fhip_topology_counts(owner.h, _p(c))
+        self.counts = dict(zip(TOPOLOGY_COUNTS, (int(v) for v in c)))
+        n = self.counts["shells"]
+        self.shells = {"triangles": np.zeros(n, np.uint64), "first": np.zeros(n, np.uint32), "unbalanced": np.zeros(n, np.uint64), "lo": np.zeros((n, 3), np.float32),
+                       "hi": np.zeros((n, 3), np.float32), "volume6": np.zeros(n, np.float64), "area2": np.zeros(n, np.float64)}
+        hip.check(lib().fhip_topology_shells(owner.h, *(_p(self.shells[k]) for k in ("triangles", "first", "unbalanced", "lo", "hi", "volume6", "area2"))))
+        self._host = {}
+
+    closed = property(lambda self: self.counts["unbalanced"] == 0)
+    manifold = property(lambda self: self.counts["boundary"] == self.counts["flipped"] == self.counts["nonmanifold"] == 0)
+    euler = property(lambda self: self.counts["vertices"] - self.counts["edges"] + self.counts["triangles"] - self.counts["degenerate"])
+    volume = property(lambda self: float(sum(float(v) for v in self.shells["volume6"])) / 6.0)
+    area = property(lambda self: float(sum(float(v) for v in self.shells["area2"])) / 2.0)
+
+    def _shape(self, what):
+        T = self.counts["triangles"]
+        return {"vertices": ((int(lib().fhip_topology_vertex_rows(self._owner.h)), 3), np.float32, "<f4"), "triangles": ((T, 3), np.uint64, "<u8"),
+                "triangle_shells": ((T,), np.uint32, "<u4")}[what]
+
+    def _array(self, what):
+        if what not in self._host:
+            shape, dtype, _ = self._shape(what)
+            a = np.zeros(shape, dtype)
+            self._hip.check(getattr(lib(), "fhip_topology_" + what)(self._owner.h, _p(a)))
+            self._host[what] = a
+        return self._host[what]
+
+    def _device(self, what):
+        ptr = getattr(lib(), f"fhip_topology_{what}_dev")(self._owner.h)
+        shape, _, typestr = self._shape(what)
+        return _DeviceArray(self._owner, ptr, shape, typestr) if ptr else None
+
+    vertices = property(lambda self: self._array("vertices"))
+    triangles = property(lambda self: self._array("triangles"))
+    triangle_shell = property(lambda self: self._array("triangle_shells"))
+
+    def vertices_device(self):
+        """`.vertices` where they are in device memory, as `Mesh.vertices_device` gives a mesh's; None for a mesh without triangles"""
+        return self._device("vertices")
+
+    def triangles_device(self):
+        """... `.triangles` ("<u8": see `Mesh.triangles_device`)"""
+        return self._device("triangles")
+
+    def triangle_shell_device(self):
+        """... and `.triangle_shell` ("<u4")"""
+        return self._device("triangle_shells")
+
+    def edges(self, kind, device=False):
+        """fhip_topology_edges: the edges of one class - "boundary" (where the holes are), "flipped", "nonmanifold", "unbalanced" - as
+        [n, 2] uint32 vertex pairs (a, b), a < b, in the order of the first corners that use them: a numpy array, or with `device` a
+        torch CUDA tensor (int32: the bits of the uint32 pairs)."""
+        k = EDGE_KINDS.index(kind)
+        n = self.counts[kind]
+        if device:
+            import torch
+            out = torch.empty((n, 2), dtype=torch.int32, device="cuda")
+            self._hip.check(lib().fhip_topology_edges(self._hip._h, self._owner.h, k, _dev_ptr(out) if n else None, 1))
+            self._hip.sync()
+            return out
+        out = np.zeros((n, 2), np.uint32)
+        self._hip.check(lib().fhip_topology_edges(self._hip._h, self._owner.h, k, _p(out), 0))
+        return out
+
+
+def mesh_topology(mesh, weld=None, hip=None, table_log2=0):
+    """fhip_triangles_topology / fhip_mesh_topology: what kind of triangle mesh this is -> Topology: the welded indexed mesh, the class
+    of every edge (boundary, flipped, nonmanifold, unbalanced), the shells - edge-connected parts - with their triangles, bounds, volume
+    and area; the definitions stand in include/fidget_hip.h.  `mesh`: as for `voxelize_mesh` - a `Mesh` (its resident device arrays are
+    read where they are), float32 [T, 3, 3] triangles (numpy or a torch CUDA tensor), or a pair (vertices [V, 3] float32, triangles
+    [T, 3] indices), both numpy or both torch CUDA.  `weld`: make one vertex of all corners with equal coordinates (-0 equals +0);
+    default on for a soup, where it cannot be turned off, and off for a pair or a `Mesh`, whose indices then are the vertices.
+    `table_log2`: 0, or the size of both hash tables as a power of two (tests; a table too small raises FidgetHipError Overflow).
+    ValueError when triangles were rejected: a coordinate that is not finite, or an index beyond the vertices.  All integer results
+    are the same from run to run; the shells' volume6 and area2 - float64 sums in an order of arrival - alone may differ in their last
+    bits."""
+    keep = None          # what the pointers point into, until the call returns
+    h = C.c_void_p()
+    if isinstance(mesh, Mesh):
+        hip = mesh._hip
+        st = lib().fhip_mesh_topology(hip._h, mesh._owner.h, int(bool(weld)), int(table_log2), C.byref(h))
+    else:
+        hip = hip or default_context()
+        pair = isinstance(mesh, (tuple, list)) and len(mesh) == 2 and all(hasattr(a, "shape") for a in mesh)
+        if isinstance(mesh, (tuple, list)) and not pair and any(hasattr(a, "shape") for a in mesh):
+            raise TypeError("mesh_topology: a mesh is a Mesh, [T, 3, 3] triangles, or a pair (vertices [V, 3], triangles [T, 3]) of two arrays")
+        verts, tris = mesh if pair else (mesh, None)
+        if tris is None and weld is not None and not weld:
+            raise ValueError("mesh_topology: a soup of triangles has no vertices until it is welded: weld=False needs a pair or a Mesh")
+        if isinstance(verts, np.ndarray) or not hasattr(verts, "is_cuda"):
+            verts = np.ascontiguousarray(verts, np.float32).reshape(-1, 3)
+            vp, dev = _p(verts), 0
+            if tris is not None:
+                tris = np.ascontiguousarray(tris, np.uint64).reshape(-1, 3)
+            tp = _p(tris)
+        else:
+            assert verts.is_cuda and verts.element_size() == 4 and verts.is_floating_point(), "vertices on the device: a float32 CUDA tensor"
+            verts = verts.contiguous().reshape(-1, 3)
+            vp, dev = _dev_ptr(verts), 1
+            if tris is not None:
+                assert tris.is_cuda and tris.element_size() == 8 and not tris.is_floating_point(), "triangles on the device: an int64 CUDA tensor"
+                tris = tris.contiguous().reshape(-1, 3)
+            tp = _dev_ptr(tris)
+        n_verts = int(verts.shape[0])
+        n_tris = int(tris.shape[0]) if tris is not None else n_verts // 3
+        keep = (verts, tris)
+        st = lib().fhip_triangles_topology(hip._h, vp, n_verts, tp, n_tris, dev, int(tris is None if weld is None else bool(weld)), int(table_log2), C.byref(h))
+    del keep
+    hip.check(st)
+    res = Topology(_TopologyHandle(h.value), hip)
+    if res.counts["rejected"]:
+        raise ValueError(f"mesh_topology: {res.counts['rejected']} of {res.counts['triangles']} triangles rejected: a coordinate that is not finite, or an index beyond the vertices")
     return res
 
 

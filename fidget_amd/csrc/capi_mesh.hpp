@@ -1771,3 +1771,5 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 #include "capi_flow.hpp"
 // a triangle mesh to a voxel bitmap (fhip_triangles_voxels, fhip_mesh_voxels): likewise
 #include "capi_trivox.hpp"
+// the check of a triangle mesh (fhip_triangles_topology, fhip_mesh_topology): likewise
+#include "capi_topo.hpp"

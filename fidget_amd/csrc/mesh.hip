@@ -1257,3 +1257,5 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 #include "flow.hip"
 // k_tv_*: a triangle mesh to such a bitmap (fhip_triangles_voxels, fhip_mesh_voxels) - its own file
 #include "trivox.hip"
+// k_mt_*: the check of a triangle mesh - weld, edges, shells (fhip_triangles_topology, fhip_mesh_topology) - its own file
+#include "topo.hip"

@@ -623,6 +623,65 @@ fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t
 fhip_status fhip_mesh_voxels(fhip_ctx* ctx, const fhip_mesh* mesh, const double* mesh_to_world, uint32_t depth,
                              uint64_t* out, int out_on_device, uint64_t info[8]);
 
+/* ---- the check of a triangle mesh: weld, edges, shells, volume ------------------------------------------------------
+ * (No counterpart in the reference, which never asks what kind of mesh it made: the definition below is the specification.  Every
+ * integer result is the same bits from run to run and does not depend on how the hardware orders the threads; the two float64 sums per
+ * shell, volume6 and area2, add the same terms in an order of arrival that may differ from run to run, and nothing else does.)
+ * INPUT.  As fhip_triangles_voxels takes it: `vertices` 3 f32 each; `triangles` 3 u64 indices each, or NULL for a soup in which every
+ * three vertices are a triangle.  Corner c = 3 t + k is corner k of triangle t.  A triangle is REJECTED if a coordinate of one of its
+ * corners is not finite, or one of its indices is at or beyond n_vertices (never read).  With any triangle rejected the call makes
+ * no arrays: it returns FHIP_OK and a handle whose counts hold `triangles` and `rejected` alone.
+ * WELD.  weld != 0: two corners are the same vertex iff their three coordinates are equal as floats after x + 0.0f (-0 equals +0; no
+ * NaN gets here).  The welded vertices are numbered in the order of their first corners, vertices[v] holds that first corner's
+ * coordinates, bits unchanged, and a vertex that no triangle uses does not appear.  weld == 0 (indexed meshes only; a soup is refused):
+ * a vertex is its index, and the vertex array is handed through as given, all n_vertices rows of it.  Either way `triangles` holds
+ * every triangle in the order given, as vertex ids, and counts[3] is the number of distinct vertices that a triangle uses.
+ * DEGENERATE.  A triangle with two equal vertex ids: counted, kept in `triangles`, no part of edges or shells, its shell 0xFFFFFFFF.
+ * EDGES.  An edge is a set {a, b}, a < b, used by the triangles that are not degenerate: f uses in the direction a -> b, r in b -> a.
+ * boundary: f + r == 1; flipped: f + r == 2 and f != r; nonmanifold: f + r >= 3; unbalanced: f != r.  A mesh is closed iff no edge is
+ * unbalanced - its triangles form a cycle, what parity filling needs - and manifold iff no edge is boundary, flipped or nonmanifold;
+ * its Euler number is vertices - edges + (triangles - degenerate).  fhip_topology_edges: the edges of one class (kind 0 boundary, 1
+ * flipped, 2 nonmanifold, 3 unbalanced) as counts[5 + kind] pairs (a, b) of u32, in the order of the first corners that use them.
+ * SHELLS.  Two triangles that are not degenerate are in the same shell iff a chain of shared edges, of any class, joins them.  Shells
+ * are numbered in the order of their first (smallest) triangles; triangle_shells[t] is a triangle's shell.  Per shell: `triangles`;
+ * `first`, its first triangle; `unbalanced`, its unbalanced edges - an edge lies in one shell, so the shell is closed iff this is 0;
+ * lo, hi [3]: the exact minimum and maximum of its corners, -0 taken as +0; volume6 and area2, each the sum over the shell's
+ * triangles of a binary64 term of the corners a, b, c - rows of `vertices` - converted to binary64, evaluated in the order written,
+ * no contraction: with n = (b.y c.z - b.z c.y, b.z c.x - b.x c.z, b.x c.y - b.y c.x) the term of volume6 is (a.x n.x + a.y n.y) + a.z n.z;
+ * with u = b - a, v = c - a and m = u x v in the same component order the term of area2 is sqrt((m.x m.x + m.y m.y) + m.z m.z).  A
+ * shell with volume6 < 0 is an inward-facing cavity; the mesh's volume is the sum of volume6 over 6, its area that of area2 over 2.
+ * THE PASSES.  Three lock-free tables.  Vertices: open addressing over u32 slots that hold the corner that claimed them (CAS from
+ * empty); a corner that meets a claimed slot compares its key with the claimant's, read from the input - it never waits for another
+ * thread's data - and a second word per slot takes the minimum of the corners: the first.  Edges: slots of a key a << 32 | b claimed
+ * by a 64-bit CAS, the two counts in one 64-bit word (an add of 1 or 1 << 32), the first corner by a minimum.  Shells: a union-find
+ * over the triangles that links towards the smaller root, every triangle united with the first triangle of each of its edges.  The
+ * lists and numbers come from flags and prefix sums over the corners and triangles, never from the order of the slots.  A probe
+ * sequence visits every slot at most once; one that finds no room makes the call return FHIP_ERR_OVERFLOW.  No pass waits for
+ * another workgroup.  table_log2 == 0: the library sizes the tables (the least power of two at or above 4 T slots each; 8 bytes a
+ * vertex slot, 32 an edge slot); otherwise both get exactly 1 << table_log2 slots (at most 32).  The scratch stays with the context in
+ * the buffer of the mesher's leaf records, as fhip_triangles_voxels' does: fhip_ctx_trim gives it back.
+ * Limits: 3 n_triangles <= 2^32 - 2 and, indexed, n_vertices <= 2^32 - 2, beyond them FHIP_ERR_OVERFLOW.  n_triangles == 0 is valid:
+ * all counts zero, no arrays.  The calls block.  counts = {triangles, rejected, degenerate, vertices, edges, boundary, flipped,
+ * nonmanifold, unbalanced, shells, vertex-table slots, edge-table slots, 0, 0, 0, 0}.  The getters copy to host arrays of the sizes the
+ * counts give (`vertices`: fhip_topology_vertex_rows rows - counts[3] welded, n_vertices otherwise); the _dev getters return the
+ * handle's device arrays, NULL where there are none; any array pointer of fhip_topology_shells may be NULL.  fhip_mesh_topology: the
+ * same for a fhip_mesh, from its device arrays where they are resident. */
+fhip_status fhip_triangles_topology(fhip_ctx* ctx, const float* vertices, uint64_t n_vertices, const uint64_t* triangles /* NULL: a soup */,
+                                    uint64_t n_triangles, int on_device, int weld, uint32_t table_log2, void** out);
+fhip_status fhip_mesh_topology(fhip_ctx* ctx, const fhip_mesh* mesh, int weld, uint32_t table_log2, void** out);
+void fhip_topology_counts(const void* topo, uint64_t out[16]);
+uint64_t fhip_topology_vertex_rows(const void* topo);
+fhip_status fhip_topology_vertices(const void* topo, float* out);
+fhip_status fhip_topology_triangles(const void* topo, uint64_t* out);
+fhip_status fhip_topology_triangle_shells(const void* topo, uint32_t* out);
+const float* fhip_topology_vertices_dev(const void* topo);
+const uint64_t* fhip_topology_triangles_dev(const void* topo);
+const uint32_t* fhip_topology_triangle_shells_dev(const void* topo);
+fhip_status fhip_topology_shells(const void* topo, uint64_t* triangles, uint32_t* first, uint64_t* unbalanced, float* lo, float* hi,
+                                 double* volume6, double* area2);
+fhip_status fhip_topology_edges(fhip_ctx* ctx, const void* topo, uint32_t kind, uint32_t* out, int out_on_device);
+void fhip_topology_free(void* topo);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

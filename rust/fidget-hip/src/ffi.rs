@@ -172,6 +172,22 @@ extern "C" {
                                  mesh_to_world: *const f64, depth: u32, out: *mut u64, out_on_device: c_int, info: *mut u64) -> fhip_status;
     pub fn fhip_mesh_voxels(ctx: *mut fhip_ctx, mesh: *const fhip_mesh, mesh_to_world: *const f64, depth: u32, out: *mut u64, out_on_device: c_int,
                             info: *mut u64) -> fhip_status;
+    // the check of a triangle mesh: weld, edges, shells (the handle is a void* in the header)
+    pub fn fhip_triangles_topology(ctx: *mut fhip_ctx, vertices: *const f32, n_vertices: u64, triangles: *const u64, n_triangles: u64, on_device: c_int,
+                                   weld: c_int, table_log2: u32, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_mesh_topology(ctx: *mut fhip_ctx, mesh: *const fhip_mesh, weld: c_int, table_log2: u32, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_topology_counts(topo: *const c_void, out: *mut u64);
+    pub fn fhip_topology_vertex_rows(topo: *const c_void) -> u64;
+    pub fn fhip_topology_vertices(topo: *const c_void, out: *mut f32) -> fhip_status;
+    pub fn fhip_topology_triangles(topo: *const c_void, out: *mut u64) -> fhip_status;
+    pub fn fhip_topology_triangle_shells(topo: *const c_void, out: *mut u32) -> fhip_status;
+    pub fn fhip_topology_vertices_dev(topo: *const c_void) -> *const f32;
+    pub fn fhip_topology_triangles_dev(topo: *const c_void) -> *const u64;
+    pub fn fhip_topology_triangle_shells_dev(topo: *const c_void) -> *const u32;
+    pub fn fhip_topology_shells(topo: *const c_void, triangles: *mut u64, first: *mut u32, unbalanced: *mut u64, lo: *mut f32, hi: *mut f32, volume6: *mut f64,
+                                area2: *mut f64) -> fhip_status;
+    pub fn fhip_topology_edges(ctx: *mut fhip_ctx, topo: *const c_void, kind: u32, out: *mut u32, out_on_device: c_int) -> fhip_status;
+    pub fn fhip_topology_free(topo: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

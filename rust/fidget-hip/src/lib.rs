@@ -16,6 +16,7 @@ pub mod ffi;
 pub mod mesh;
 pub mod occupancy;
 pub mod render;
+pub mod topology;
 pub mod voxels;
 
 use std::ops::Deref;
