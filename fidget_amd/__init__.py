@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -63,6 +63,8 @@ EXPORTS = [
     "fhip_triangles_voxels", "fhip_mesh_voxels",
     "fhip_triangles_topology", "fhip_mesh_topology", "fhip_topology_counts", "fhip_topology_vertex_rows", "fhip_topology_vertices", "fhip_topology_triangles", "fhip_topology_triangle_shells",
     "fhip_topology_vertices_dev", "fhip_topology_triangles_dev", "fhip_topology_triangle_shells_dev", "fhip_topology_shells", "fhip_topology_edges", "fhip_topology_free",
+    "fhip_voxels_outlines", "fhip_outlines_counts", "fhip_outlines_layers", "fhip_outlines_vertices", "fhip_outlines_loops", "fhip_outlines_xy_dev", "fhip_outlines_next_dev",
+    "fhip_outlines_loop_dev", "fhip_outlines_free",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -210,6 +212,9 @@ def lib():
             "fhip_topology_triangles": (i32, [vp, vp]), "fhip_topology_triangle_shells": (i32, [vp, vp]), "fhip_topology_vertices_dev": (vp, [vp]),
             "fhip_topology_triangles_dev": (vp, [vp]), "fhip_topology_triangle_shells_dev": (vp, [vp]),
             "fhip_topology_shells": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]), "fhip_topology_edges": (i32, [vp, vp, u32, vp, i32]), "fhip_topology_free": (None, [vp]),
+            "fhip_voxels_outlines": (i32, [vp, vp, u32, i32, u32, u32, u32, vp]), "fhip_outlines_counts": (None, [vp, vp]), "fhip_outlines_layers": (i32, [vp, vp, vp, vp, vp]),
+            "fhip_outlines_vertices": (i32, [vp, u64, u64, vp, vp, vp]), "fhip_outlines_loops": (i32, [vp, u64, u64, vp, vp, vp, vp, vp, vp]),
+            "fhip_outlines_xy_dev": (vp, [vp]), "fhip_outlines_next_dev": (vp, [vp]), "fhip_outlines_loop_dev": (vp, [vp]), "fhip_outlines_free": (None, [vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1566,8 +1571,152 @@ class Voxels:
         self._hip.check(lib().fhip_voxels_heights(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(axis), ptr, dev))
         return out
 
+    def outlines(self, k0, k1, connectivity=4):
+        """fhip_voxels_outlines: the boundary loops of every layer k0 <= k < k1 (layers along z, as for `slices`) -> Outlines.  The
+        loops are closed rectilinear polygons over the corners (a, b), 0 <= a, b <= N, of the layer image P(i, j) = voxel (i, j, k),
+        clear outside the grid; directed with the inside on the left, so an outer boundary runs counter-clockwise (area2 > 0) and a
+        hole clockwise (area2 < 0); vertices only where the outline turns.  `connectivity` 4: pixels that touch at a corner alone
+        are separate, 8: they are joined - it decides how the two vertices of a saddle corner pair up.  One blocking call, run where
+        the bricks are; the vertices' arrays stay in device memory.  Integers throughout: the same bits from run to run."""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_voxels_outlines(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(k0), int(k1), int(connectivity), C.byref(h)))
+        return Outlines(_OutlinesHandle(h.value), self._hip)
+
+    def outline(self, k, connectivity=4):
+        """the loops of the one layer k: `outlines(k, k + 1)`"""
+        return self.outlines(k, int(k) + 1, connectivity)
+
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
+
+
+class _OutlinesHandle:
+    """owner of an fhip_outlines whose device arrays the views borrow"""
+    def __init__(self, h):
+        self.h = h
+        self._free = lib().fhip_outlines_free      # (held here, as _MeshHandle holds its own)
+
+    def __del__(self):
+        if self.h and self._free is not None:
+            self._free(self.h)
+            self.h = None
+
+
+class Outlines:
+    """The loops of `Voxels.outlines(k0, k1)`.  `.grid` = N, `.k0`, `.k1`, `.connectivity`, `.n_vertices`, `.n_loops`, `.n_layers`.
+    Per layer (index k - k0): `.vertex_start` and `.loop_start` uint64 [K + 1], the ranges of the layer's vertices and loops - ids are
+    global, layers ascending; `.layer_area2` int64 [K] = twice the layer's set voxels; `.layer_perimeter` uint64 [K] = its unit
+    boundary edges.  Per vertex: `.xy()` uint16 [n, 2] the corner (a, b); `.next()` uint32 [n] the next vertex along the loop, a
+    permutation inside each layer; `.loop_of()` uint32 [n].  Per loop (`.table()`): leader - its smallest vertex id; loops are numbered
+    by ascending leader - n_vertices, area2 (int64 shoelace sum: > 0 an outer boundary, < 0 a hole), perimeter, lo and hi [., 2].
+    The vertices' arrays stay in device memory (`.xy_device()` ...); host copies are made when first asked for."""
+
+    def __init__(self, owner, hip):
+        self._owner, self._hip = owner, hip
+        c = np.zeros(8, np.uint64)
+        lib().fhip_outlines_counts(owner.h, _p(c))
+        self.n_vertices, self.n_loops, self.n_layers, self.grid, self.k0, self.connectivity = (int(v) for v in c[:6])
+        self.k1 = self.k0 + self.n_layers
+        K = self.n_layers
+        self.vertex_start, self.loop_start = np.zeros(K + 1, np.uint64), np.zeros(K + 1, np.uint64)
+        self.layer_area2, self.layer_perimeter = np.zeros(K, np.int64), np.zeros(K, np.uint64)
+        hip.check(lib().fhip_outlines_layers(owner.h, _p(self.vertex_start), _p(self.loop_start), _p(self.layer_area2), _p(self.layer_perimeter)))
+        self._host = None
+        self._table = None
+
+    def _layer(self, k, start):
+        """the range of layer k in `start`, or everything"""
+        if k is None:
+            return 0, int(start[-1])
+        k = int(k)
+        if not self.k0 <= k < self.k1:
+            raise IndexError(f"layer {k} is not among {self.k0} .. {self.k1 - 1}")
+        return int(start[k - self.k0]), int(start[k - self.k0 + 1])
+
+    def _vertices(self):
+        if self._host is None:
+            n = self.n_vertices
+            xy, nxt, loop = np.zeros((n, 2), np.uint16), np.zeros(n, np.uint32), np.zeros(n, np.uint32)
+            self._hip.check(lib().fhip_outlines_vertices(self._owner.h, 0, n, _p(xy), _p(nxt), _p(loop)))
+            self._host = (xy, nxt, loop)
+        return self._host
+
+    def xy(self, k=None):
+        """uint16 [n, 2]: the corners (a, b) of all vertices, or of layer k's"""
+        lo, hi = self._layer(k, self.vertex_start)
+        return self._vertices()[0][lo:hi]
+
+    def next(self, k=None):
+        """uint32 [n]: every vertex's successor; for one layer the ids stay global - subtract `vertex_start[k - k0]`"""
+        lo, hi = self._layer(k, self.vertex_start)
+        return self._vertices()[1][lo:hi]
+
+    def loop_of(self, k=None):
+        """uint32 [n]: every vertex's loop; global ids likewise"""
+        lo, hi = self._layer(k, self.vertex_start)
+        return self._vertices()[2][lo:hi]
+
+    def table(self, k=None):
+        """{"leader", "n_vertices", "area2", "perimeter", "lo", "hi"}: a row per loop, of all layers or of layer k"""
+        if self._table is None:
+            n = self.n_loops
+            t = {"leader": np.zeros(n, np.uint32), "n_vertices": np.zeros(n, np.uint32), "area2": np.zeros(n, np.int64), "perimeter": np.zeros(n, np.uint64),
+                 "lo": np.zeros((n, 2), np.uint16), "hi": np.zeros((n, 2), np.uint16)}
+            self._hip.check(lib().fhip_outlines_loops(self._owner.h, 0, n, *(_p(t[key]) for key in ("leader", "n_vertices", "area2", "perimeter", "lo", "hi"))))
+            self._table = t
+        lo, hi = self._layer(k, self.loop_start)
+        return {key: a[lo:hi] for key, a in self._table.items()}
+
+    def polygons(self, k):
+        """layer k's loops as int arrays [m, 2] of corners, each from its leader on, in loop order: walked along `next` on the host"""
+        xy, nxt, _ = self._vertices()
+        t = self.table(k)
+        out = []
+        for leader, m in zip(t["leader"], t["n_vertices"]):
+            ids, v = np.zeros(int(m), np.int64), int(leader)
+            for q in range(int(m)):
+                ids[q] = v
+                v = int(nxt[v])
+            out.append(xy[ids].astype(np.int64))
+        return out
+
+    def world(self, k):
+        """-> (polygons as float32 [m, 2] in the cube [-1, 1]^3 - corner a at float(2 a - N) / N, as `Voxels.mesh` places it - and the
+        layer's z, its centre float(2 k + 1 - N) / N)"""
+        N = self.grid
+        return [((2 * p - N).astype(np.float32) / np.float32(N)) for p in self.polygons(k)], float(np.float32(2 * int(k) + 1 - N) / np.float32(N))
+
+    def svg(self, k, path=None):
+        """Layer k as one <path fill-rule="evenodd"> per loop, `M x y L x y ... Z`, in `world`'s coordinates with y negated - SVG's y
+        grows downward - and the cube's square as the viewBox, like `Contours.svg`.  Returns the text; written to `path` when given."""
+        polys, _ = self.world(k)
+        paths = "".join('<path fill-rule="evenodd" d="M ' + " L ".join(f"{float(x):.9g} {-float(y):.9g}" for x, y in p) + ' Z"/>\n' for p in polys)
+        text = f'<svg xmlns="http://www.w3.org/2000/svg" viewBox="-1 -1 2 2">\n{paths}</svg>\n'
+        if path is not None:
+            with open(path, "w") as f:
+                f.write(text)
+        return text
+
+    def _device(self, what, shape, typestr):
+        ptr = getattr(lib(), f"fhip_outlines_{what}_dev")(self._owner.h)
+        return _DeviceArray(self._owner, ptr, shape, typestr) if ptr else None
+
+    def xy_device(self):
+        """`.xy()` where it is in device memory ([n, 2] "<i2": the bits of the uint16 corners, which stay below 2^15) as an object
+        carrying `__cuda_array_interface__` that keeps the result alive; None when there are no vertices"""
+        return self._device("xy", (self.n_vertices, 2), "<i2")
+
+    def next_device(self):
+        """... `.next()` ("<i4": the bits of the uint32 ids, as `Contours.segments_device` gives its)"""
+        return self._device("next", (self.n_vertices,), "<i4")
+
+    def loop_of_device(self):
+        """... and `.loop_of()` ("<i4")"""
+        return self._device("loop", (self.n_vertices,), "<i4")
+
+    def __repr__(self):
+        return (f"Outlines(grid={self.grid}, layers={self.k0}..{self.k1}, connectivity={self.connectivity}, vertices={self.n_vertices}, "
+                f"loops={self.n_loops})")
 
 
 class Surface:

@@ -1773,3 +1773,5 @@ void fhip_components_free(void* h) { delete (fhip_components*)h; }
 #include "capi_trivox.hpp"
 // the check of a triangle mesh (fhip_triangles_topology, fhip_mesh_topology): likewise
 #include "capi_topo.hpp"
+// the outlines of a voxel bitmap's layers (fhip_voxels_outlines): likewise
+#include "capi_outline.hpp"

@@ -1259,3 +1259,5 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 #include "trivox.hip"
 // k_mt_*: the check of a triangle mesh - weld, edges, shells (fhip_triangles_topology, fhip_mesh_topology) - its own file
 #include "topo.hip"
+// k_ol_*: the outlines of such a bitmap's layers - vertices, successors, loops (fhip_voxels_outlines) - its own file
+#include "outline.hip"

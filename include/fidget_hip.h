@@ -682,6 +682,51 @@ fhip_status fhip_topology_shells(const void* topo, uint64_t* triangles, uint32_t
 fhip_status fhip_topology_edges(fhip_ctx* ctx, const void* topo, uint32_t kind, uint32_t* out, int out_on_device);
 void fhip_topology_free(void* topo);
 
+/* ---- the outlines of a voxel bitmap's layers: closed rectilinear loops per layer ------------------------------------
+ * (No counterpart in the reference, which has no voxel bitmap: the definitions below are the specification, exact and in integers,
+ * and the result is the same from run to run.)
+ * LAYER IMAGE.  Layers are along z, as for fhip_voxels_slices.  Layer k is the image P(i, j) = voxel (i, j, k), 0 <= i, j < N = 4 << depth,
+ * clear outside the grid: every loop is closed and the grid's borders produce edges.
+ * CORNERS (a, b), 0 <= a, b <= N.  The corner mask is m = P(a-1, b-1) | P(a, b-1) << 1 | P(a, b) << 2 | P(a-1, b) << 3.
+ * UNIT BOUNDARY EDGES separate a set pixel from a clear one and are directed with the inside on the left, x to the right and y upward:
+ * the bottom side of a set pixel runs +x and its top -x, its right side runs +y and its left side -y.  Headings are numbered as the
+ * directions of fhip_voxels_flow: 0 = -x, 1 = +x, 2 = -y, 3 = +y.
+ * VERTICES lie only where the outline turns.  As (incoming heading, outgoing heading) a corner holds: m = 0, 15, 3, 6, 9, 12: none (the
+ * last four are straight runs); m = 1: (3, 0); m = 2: (0, 2); m = 4: (2, 1); m = 8: (1, 3); m = 7: (2, 0); m = 11: (0, 3); m = 13: (3, 1);
+ * m = 14: (1, 2).  The saddles m = 5 and m = 10 hold two vertices, in ascending order of the outgoing heading.  With connectivity 4
+ * diagonal pixels are separate and both loops turn left: m = 5: (3, 0), (2, 1); m = 10: (0, 2), (1, 3).  With connectivity 8 diagonal
+ * pixels are joined and both loops turn right: m = 5: (2, 0), (3, 1); m = 10: (1, 2), (0, 3).  Any other connectivity is
+ * FHIP_ERR_UNSUPPORTED.
+ * NUMBERING.  Layers ascend; inside a layer the corners are in the order b (N + 1) + a; a saddle's two vertices in the order above.  Ids
+ * are global uint32; vertex_start[K + 1] (K = k1 - k0) gives each layer's range.  2^32 vertices or more is FHIP_ERR_OVERFLOW, decided
+ * from the counting pass's 64-bit totals before anything is written.
+ * xy[v] is the corner as two uint16 (a, b).  next[v] is the id of the first vertex met from v along its outgoing heading: the nearest
+ * corner on that lattice line that holds a vertex with that incoming heading - everything between is a straight corner.  next is a
+ * permutation inside each layer: every vertex has exactly one successor and one predecessor.
+ * LOOPS.  A loop's leader is its smallest vertex id; loops are numbered by ascending leader, so a layer's loops are contiguous:
+ * loop_start[K + 1] gives each layer's range and loop_of[v] each vertex's loop.  The loop table holds per loop: leader and n_vertices;
+ * area2, the int64 shoelace sum of x_v y_next - x_next y_v over its vertices, positive for an outer boundary and negative for a hole;
+ * perimeter, its Manhattan length; lo[2] and hi[2], its corner bounds.  Per layer, area2 is the sum over the layer's loops, which
+ * equals twice the layer's count of set voxels (fhip_voxels_layer_counts), and perimeter the number of its unit boundary edges.
+ * WORLD.  Corner a is at float(2 a - N) / N, as fhip_voxels_mesh places it; a layer's z is its centre float(2 k + 1 - N) / N.
+ * on_device != 0: `bricks` is a device pointer (8-byte aligned), read in place; otherwise a host buffer of fhip_voxels_words(depth)
+ * words, staged.  The call blocks, as fhip_contour2d does: the counting pass's totals come back to size the arrays.  xy, next and
+ * loop_of stay in device memory, owned by the handle (the _dev getters; NULL where there are no vertices); the getters copy ranges to
+ * the host, any output pointer may be NULL, and a range beyond the counts is FHIP_ERR_UNSUPPORTED.  counts = {vertices, loops, layers,
+ * N, k0, connectivity, 0, 0}.  Refused before any launch: k0 > k1, k1 > N, depth > 10 (FHIP_ERR_UNSUPPORTED).  k0 == k1 is FHIP_OK
+ * with an empty result.  No kernel waits for another workgroup; the sums are integer atomics. */
+fhip_status fhip_voxels_outlines(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t k0, uint32_t k1,
+                                 uint32_t connectivity, void** out);
+void fhip_outlines_counts(const void* outlines, uint64_t out[8]);
+fhip_status fhip_outlines_layers(const void* outlines, uint64_t* vertex_start, uint64_t* loop_start, int64_t* area2, uint64_t* perimeter);
+fhip_status fhip_outlines_vertices(const void* outlines, uint64_t first, uint64_t count, uint16_t* xy, uint32_t* next, uint32_t* loop_of);
+fhip_status fhip_outlines_loops(const void* outlines, uint64_t first, uint64_t count, uint32_t* leader, uint32_t* n_vertices,
+                                int64_t* area2, uint64_t* perimeter, uint16_t* lo, uint16_t* hi);
+const uint16_t* fhip_outlines_xy_dev(const void* outlines);
+const uint32_t* fhip_outlines_next_dev(const void* outlines);
+const uint32_t* fhip_outlines_loop_dev(const void* outlines);
+void fhip_outlines_free(void* outlines);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

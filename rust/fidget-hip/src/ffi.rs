@@ -188,6 +188,18 @@ extern "C" {
                                 area2: *mut f64) -> fhip_status;
     pub fn fhip_topology_edges(ctx: *mut fhip_ctx, topo: *const c_void, kind: u32, out: *mut u32, out_on_device: c_int) -> fhip_status;
     pub fn fhip_topology_free(topo: *mut c_void);
+    // the outlines of a voxel bitmap's layers: vertices where the outline turns, their successors, the loops and their table
+    pub fn fhip_voxels_outlines(ctx: *mut fhip_ctx, bricks: *const u64, depth: u32, on_device: c_int, k0: u32, k1: u32, connectivity: u32,
+                                out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_outlines_counts(outlines: *const c_void, out: *mut u64);
+    pub fn fhip_outlines_layers(outlines: *const c_void, vertex_start: *mut u64, loop_start: *mut u64, area2: *mut i64, perimeter: *mut u64) -> fhip_status;
+    pub fn fhip_outlines_vertices(outlines: *const c_void, first: u64, count: u64, xy: *mut u16, next: *mut u32, loop_of: *mut u32) -> fhip_status;
+    pub fn fhip_outlines_loops(outlines: *const c_void, first: u64, count: u64, leader: *mut u32, n_vertices: *mut u32, area2: *mut i64, perimeter: *mut u64,
+                               lo: *mut u16, hi: *mut u16) -> fhip_status;
+    pub fn fhip_outlines_xy_dev(outlines: *const c_void) -> *const u16;
+    pub fn fhip_outlines_next_dev(outlines: *const c_void) -> *const u32;
+    pub fn fhip_outlines_loop_dev(outlines: *const c_void) -> *const u32;
+    pub fn fhip_outlines_free(outlines: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

@@ -5,7 +5,7 @@ with the frame driver, headers) except the files only the mesh path uses (MESH_O
 change there cannot alter a render kernel or how a frame is launched."""
 import glob, hashlib, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MESH_ONLY = ("mesh.hip", "mesh_collapse.hpp", "mesh_qef.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "capi_mesh.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp")
+MESH_ONLY = ("mesh.hip", "mesh_collapse.hpp", "mesh_qef.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "capi_mesh.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp")
 
 
 def source_hash(root=ROOT):
