@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_bound.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_mesh_util.hpp", "capi_voxels.hpp", "capi_contour.hpp", "capi_cc.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -1076,17 +1076,21 @@ def libm_probe():
     return int(n), buf.value.decode()
 
 
-class _MeshHandle:
-    """owner of an fhip_mesh whose arrays numpy views borrow"""
-    def __init__(self, h):
+class _Handle:
+    """owner of one of the library's handles (a mesh, contours, components, a distance field, a topology, outlines), whose arrays the
+    views and the later calls borrow: `.h`, freed with `free` when the last of them lets go"""
+    def __init__(self, h, free):
         self.h = h
-        self._free = lib().fhip_mesh_free      # (held here: at interpreter shutdown the module's globals may be gone before the last view)
+        self._free = free      # (held here: at interpreter shutdown the module's globals may be gone before the last view)
 
     def __del__(self):
         if self.h and self._free is not None:
             self._free(self.h)
             self.h = None
 
+
+class _MeshHandle(_Handle):
+    """owner of an fhip_mesh whose arrays numpy views borrow"""
     def view(self, ptr, shape, dtype):
         n = int(np.prod(shape)) * np.dtype(dtype).itemsize
         if not n or not ptr:
@@ -1262,7 +1266,7 @@ def mesh_sample(shape, depth, world_to_model=None, vars=None, _build=False, _own
         counts = {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
         if _build:
             # the arrays where the mesh holds them, no copy: numpy views whose base keeps the handle (freed with the last of them)
-            owner = _MeshHandle(h)
+            owner = _MeshHandle(h, lib().fhip_mesh_free)
             h = None
             verts = owner.view(lib().fhip_mesh_vertices_ptr(owner.h), (int(c[6]), 3), np.float32)
             tris = owner.view(lib().fhip_mesh_triangles_ptr(owner.h), (int(c[7]), 3), np.uint64)
@@ -1366,6 +1370,36 @@ def voxels_unpack(bricks):
     return bits.reshape(B, B, B, 4, 4, 4).transpose(2, 5, 1, 4, 0, 3).reshape(4 * B, 4 * B, 4 * B).astype(bool)
 
 
+def _bitmap_out(depth, out, device=None, aligned=False):
+    """Where a call writes a result bitmap of this depth -> (out, pointer, on the device?).  `out`: a contiguous torch CUDA tensor of at
+    least 8 B^3 bytes, B = 1 << depth, or a contiguous writeable numpy array of that size; without it a new one - a torch int64
+    [B, B, B] on `device`, or with no device a numpy uint64 [B, B, B].  `aligned`: a tensor that is not 8-byte aligned fails the
+    assertion here; otherwise it is left to the library's error."""
+    B = 1 << depth
+    words = int(lib().fhip_voxels_words(depth))       # (0 beyond depth 10: the call refuses before it touches `out`)
+    if out is None and device is not None:
+        import torch
+        out = torch.empty((B, B, B), dtype=torch.int64, device=device)
+    if out is not None and not isinstance(out, np.ndarray):
+        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and (not aligned or out.data_ptr() % 8 == 0)
+        return out, _dev_ptr(out), 1
+    if out is None:
+        out = np.zeros((B, B, B) if words else 0, np.uint64)
+    assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
+    return out, _p(out), 0
+
+
+def _bitmap_of(hip, out, dev, depth, cells=None):
+    """the bitmap a call wrote into `out` (`_bitmap_out`) -> Voxels: the first 8 B^3 bytes as [B, B, B] bricks"""
+    B = 1 << depth
+    if dev:
+        import torch
+        bricks = out.reshape(-1).view(torch.uint8)[:8 * B ** 3].view(torch.int64).view(B, B, B)
+    else:
+        bricks = out.reshape(-1).view(np.uint8)[:8 * B ** 3].view(np.uint64).reshape(B, B, B)
+    return Voxels(hip, bricks, depth, cells)
+
+
 class Voxels:
     """The bitmap of `voxelize`: `.bricks` [B, B, B] (numpy uint64, or a view of the caller's torch CUDA tensor as int64), `.depth`,
     `.grid` = N = 4 B, `.cells` = {"cells", "full", "empty", "leaf_cells"} as Occupancy's, `.n` = the number of inside voxels.  What is
@@ -1429,14 +1463,14 @@ class Voxels:
         grid's border are the enclosed voids - under connectivity 6 (faces) or 26 (faces, edges, corners) -> Components"""
         h = C.c_void_p()
         self._hip.check(lib().fhip_voxels_components(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(connectivity), int(bool(complement)), C.byref(h)))
-        return Components(self, _ComponentsHandle(h.value), int(connectivity), bool(complement))
+        return Components(self, _Handle(h.value, lib().fhip_components_free), int(connectivity), bool(complement))
 
     def distance(self, complement=False):
         """fhip_voxels_distance: the exact squared Euclidean distance, in voxels, from every voxel to the nearest set bit - with
         `complement` to the nearest clear bit -> DistanceField"""
         h = C.c_void_p()
         self._hip.check(lib().fhip_voxels_distance(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(bool(complement)), C.byref(h)))
-        return DistanceField(self, _DistanceHandle(h.value), bool(complement))
+        return DistanceField(self, _Handle(h.value, lib().fhip_distance_free), bool(complement))
 
     def thickness(self, complement=False):
         """the local thickness of the solid's walls - `distance(complement=True).thickness()` - or with `complement` the local width of
@@ -1451,7 +1485,7 @@ class Voxels:
         `.counts` holds the octree's counters, all 0 here.  Overflow: 2^32 triangles or vertices and more."""
         h = C.c_void_p()
         self._hip.check(lib().fhip_voxels_mesh(self._hip._h, self._ptr(), self.depth, int(self.on_device), C.byref(h)))
-        owner = _MeshHandle(h.value)
+        owner = _MeshHandle(h.value, lib().fhip_mesh_free)
         c = np.zeros(8, np.uint64)
         lib().fhip_mesh_counts(owner.h, _p(c))
         counts = {"cells": int(c[0]), "full": int(c[1]), "empty": int(c[2]), "leaf_cells": int(c[3]), "levels": int(c[5])}
@@ -1483,29 +1517,9 @@ class Voxels:
         return self.offset(r).offset(-r)
 
     # ---- along a direction: d = 0 .. 5 = -x, +x, -y, +y, -z, +z, e(d) its unit vector, d ^ 1 its opposite --------------------------
-    def _bitmap_out(self, out):
-        """`out` as for `DistanceField.within` -> (out, pointer, on the device?): a contiguous torch CUDA tensor of at least 8 B^3 bytes or
-        a contiguous numpy array of that size; without it a new one where the bricks are"""
-        B = 1 << self.depth
-        if out is None and self.on_device:
-            import torch
-            out = torch.empty((B, B, B), dtype=torch.int64, device=self.bricks.device)
-        if out is not None and not isinstance(out, np.ndarray):
-            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * B ** 3
-            return out, _dev_ptr(out), 1
-        if out is None:
-            out = np.zeros((B, B, B), np.uint64)
-        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * B ** 3
-        return out, _p(out), 0
-
-    def _bitmap_of(self, out, dev):
-        B = 1 << self.depth
-        if dev:
-            import torch
-            bricks = out.reshape(-1).view(torch.uint8)[:8 * B ** 3].view(torch.int64).view(B, B, B)
-        else:
-            bricks = out.reshape(-1).view(np.uint8)[:8 * B ** 3].view(np.uint64).reshape(B, B, B)
-        return Voxels(self._hip, bricks, self.depth, None)
+    def _out_device(self):
+        """where a new result bitmap goes (`_bitmap_out`): the bricks' device, or None for the host"""
+        return self.bricks.device if self.on_device else None
 
     def flow(self, dir, blockers=None, with_seeds=False, out=None):
         """fhip_voxels_flow: these voxels as seeds S flowing towards direction `dir` past the blockers K (a Voxels of the same depth, in
@@ -1519,10 +1533,10 @@ class Voxels:
                 raise ValueError("blockers: a Voxels of the same depth")
             if blockers.on_device != self.on_device:
                 raise ValueError("seeds and blockers live in the same place: both on the host or both on the device")
-        out, ptr, dev = self._bitmap_out(out)
+        out, ptr, dev = _bitmap_out(self.depth, out, self._out_device())
         self._hip.check(lib().fhip_voxels_flow(self._hip._h, self._ptr(), None if blockers is None else blockers._ptr(), self.depth, int(self.on_device),
                                                int(dir), 1 if with_seeds else 0, ptr, dev))
-        return self._bitmap_of(out, dev)
+        return _bitmap_of(self._hip, out, dev, self.depth)
 
     def shadow(self, dir, out=None):
         """the clear voxels with a set voxel behind them, seen towards `dir`: `flow(dir, blockers=self)`"""
@@ -1537,9 +1551,9 @@ class Voxels:
         there is a set q one layer below, (q - p) . e(up) = -1, whose squared perpendicular offset is at most `reach2` (0 .. 16): a
         Euclidean disc - 0 straight below only, 1 a plus of five, 2 the 3 x 3 square.  For p in the first layer every q counts as set
         iff `bed`, and as clear otherwise.  `out` as for `flow`."""
-        out, ptr, dev = self._bitmap_out(out)
+        out, ptr, dev = _bitmap_out(self.depth, out, self._out_device())
         self._hip.check(lib().fhip_voxels_overhangs(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(up), int(reach2), int(bool(bed)), ptr, dev))
-        return self._bitmap_of(out, dev)
+        return _bitmap_of(self._hip, out, dev, self.depth)
 
     def supports(self, up=5, reach2=1, bed=True, out=None):
         """the clear columns under every overhanging voxel, down to the next set voxel or the grid's border:
@@ -1580,7 +1594,7 @@ class Voxels:
         the bricks are; the vertices' arrays stay in device memory.  Integers throughout: the same bits from run to run."""
         h = C.c_void_p()
         self._hip.check(lib().fhip_voxels_outlines(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(k0), int(k1), int(connectivity), C.byref(h)))
-        return Outlines(_OutlinesHandle(h.value), self._hip)
+        return Outlines(_Handle(h.value, lib().fhip_outlines_free), self._hip)
 
     def outline(self, k, connectivity=4):
         """the loops of the one layer k: `outlines(k, k + 1)`"""
@@ -1588,18 +1602,6 @@ class Voxels:
 
     def __repr__(self):
         return f"Voxels(depth={self.depth}, grid={self.grid}, cells={self.cells}, on_device={self.on_device})"
-
-
-class _OutlinesHandle:
-    """owner of an fhip_outlines whose device arrays the views borrow"""
-    def __init__(self, h):
-        self.h = h
-        self._free = lib().fhip_outlines_free      # (held here, as _MeshHandle holds its own)
-
-    def __del__(self):
-        if self.h and self._free is not None:
-            self._free(self.h)
-            self.h = None
 
 
 class Outlines:
@@ -1735,18 +1737,6 @@ class Surface:
         return f"Surface(grid={self.grid}, faces={self.faces}, vertices={self.vertices}, edges={self.edges}, area={self.area:.6g}, euler={self.euler})"
 
 
-class _DistanceHandle:
-    """owner of an fhip_distance, whose field in device memory the later calls read"""
-    def __init__(self, h):
-        self.h = h
-        self._free = lib().fhip_distance_free      # (held here, as _MeshHandle holds its own)
-
-    def __del__(self):
-        if self.h and self._free is not None:
-            self._free(self.h)
-            self.h = None
-
-
 class DistanceField:
     """The exact Euclidean distance transform of a bitmap (`Voxels.distance`): per voxel the squared distance to the nearest foreground
     voxel, a uint32 - 0 on the foreground, 0xFFFFFFFF ("no distance"; -1 as int32) everywhere when there is no foreground.
@@ -1797,30 +1787,12 @@ class DistanceField:
         squared = int(squared)
         if squared < 0 or squared > 0xFFFFFFFF:
             raise FidgetHipError(6, "distance threshold: t at most 0xFFFFFFFE")
-        v = self.voxels
-        B = 1 << self.depth
-        words = B ** 3
-        if out is None and v.on_device:
-            import torch
-            out = torch.empty((B, B, B), dtype=torch.int64, device=v.bricks.device)
-        if out is not None and not isinstance(out, np.ndarray):
-            import torch
-            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words
-            ptr, dev = _dev_ptr(out), 1
-        else:
-            if out is None:
-                out = np.zeros((B, B, B), np.uint64)
-            assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
-            ptr, dev = _p(out), 0
+        out, ptr, dev = _bitmap_out(self.depth, out, self.voxels._out_device())
         if beyond == 2:          # (ThicknessField.thin)
             self._hip.check(lib().fhip_thickness_thin(self._hip._h, self._owner.h, squared, ptr, dev))
         else:
             self._hip.check(lib().fhip_distance_threshold(self._hip._h, self._owner.h, squared, int(beyond), ptr, dev))
-        if dev:
-            bricks = out.reshape(-1).view(torch.uint8)[:8 * words].view(torch.int64).view(B, B, B)
-        else:
-            bricks = out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B)
-        return Voxels(self._hip, bricks, self.depth, None)
+        return _bitmap_of(self._hip, out, dev, self.depth)
 
     def within(self, r=None, squared=None, out=None):
         """fhip_distance_threshold: the voxels with d2 <= t as a bitmap -> Voxels (`.cells` None).  Exactly one of `r` - a radius in
@@ -1837,7 +1809,7 @@ class DistanceField:
         -> ThicknessField.  Refused for a field without foreground."""
         h = C.c_void_p()
         self._hip.check(lib().fhip_distance_thickness(self._hip._h, self._owner.h, C.byref(h)))
-        return ThicknessField(self.voxels, _DistanceHandle(h.value), self.complement)
+        return ThicknessField(self.voxels, _Handle(h.value, lib().fhip_distance_free), self.complement)
 
     def __repr__(self):
         return f"DistanceField(depth={self.depth}, grid={self.grid}, max_squared={self.max_squared}, argmax={self.argmax}, n={self.n}, complement={self.complement})"
@@ -1897,18 +1869,6 @@ class ThicknessField(DistanceField):
                 f"argmin={self.argmin}, n={self.n}, balls={self.balls}, complement={self.complement})")
 
 
-class _ComponentsHandle:
-    """owner of an fhip_components, whose device arrays the later calls read"""
-    def __init__(self, h):
-        self.h = h
-        self._free = lib().fhip_components_free      # (held here, as _MeshHandle holds its own)
-
-    def __del__(self):
-        if self.h and self._free is not None:
-            self._free(self.h)
-            self.h = None
-
-
 class Components:
     """The connected parts of a bitmap (`Voxels.components`), numbered by ascending seed - the voxel of smallest key word * 64 + bit:
     `.count`, `.nodes` (the bricks' own parts, what the union-find joined), `.n` (foreground voxels); per component `.sizes` uint64
@@ -1961,24 +1921,9 @@ class Components:
         if ((ids < 0) | (ids > 0xFFFFFFFF)).any():
             raise FidgetHipError(6, "extract: a component id beyond the number of components")
         ids = ids.astype(np.uint32)
-        B = 1 << self.depth
-        words = B ** 3
-        if out is None and v.on_device:
-            import torch
-            out = torch.empty((B, B, B), dtype=torch.int64, device=v.bricks.device)
-        if out is not None and not isinstance(out, np.ndarray):
-            import torch
-            assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
-            ptr, dev = _dev_ptr(out), 1
-            bricks = out.reshape(-1).view(torch.int64)[:words].view(B, B, B)
-        else:
-            if out is None:
-                out = np.zeros((B, B, B), np.uint64)
-            assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
-            ptr, dev = _p(out), 0
-            bricks = out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B)
+        out, ptr, dev = _bitmap_out(self.depth, out, v._out_device(), aligned=True)
         self._hip.check(lib().fhip_components_extract(self._hip._h, self._owner.h, v._ptr(), int(v.on_device), _p(ids), len(ids), ptr, dev))
-        return Voxels(self._hip, bricks, self.depth, None)
+        return _bitmap_of(self._hip, out, dev, self.depth)
 
     def __repr__(self):
         return f"Components(count={self.count}, nodes={self.nodes}, n={self.n}, connectivity={self.connectivity}, complement={self.complement})"
@@ -1997,25 +1942,13 @@ def voxelize(shape, depth, world_to_model=None, vars=None, out=None):
     if shape._vars is not None:
         ax = np.array(shape._vars, dtype=np.int32)
         vk = np.array([shape._named_slot(k) for k in (vars or {})], dtype=np.uint64)
-    B = 1 << depth
-    words = int(lib().fhip_voxels_words(depth))       # (0 beyond depth 10: the call below refuses before it touches `out`)
     cells = np.zeros(4, np.uint64)
-    if out is not None and not isinstance(out, np.ndarray):
-        import torch
-        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
-        ptr, dev = _dev_ptr(out), 1
-        bricks = (lambda: out.reshape(-1).view(torch.int64)[:words].view(B, B, B))
-    else:
-        if out is None:
-            out = np.zeros((B, B, B) if words else 0, np.uint64)
-        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
-        ptr, dev = _p(out), 0
-        bricks = (lambda: out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B))
+    out, ptr, dev = _bitmap_out(depth, out, aligned=True)
     st = lib().fhip_shape_voxels(hip._h, shape._h, depth, _p(w2m), _p(ax), _p(vk), _p(vv), len(vk), ptr, dev, _p(cells))
     if st == 4:
         raise ValueError("MissingVar")
     hip.check(st)
-    return Voxels(hip, bricks(), depth, dict(zip(("cells", "full", "empty", "leaf_cells"), (int(v) for v in cells))))
+    return _bitmap_of(hip, out, dev, depth, dict(zip(("cells", "full", "empty", "leaf_cells"), (int(v) for v in cells))))
 
 
 # ---- a triangle mesh back into the library: binary STL in, voxel bitmap out (fhip_triangles_voxels, fhip_mesh_voxels) ------------
@@ -2085,19 +2018,7 @@ def voxelize_mesh(mesh, depth, mesh_to_world=None, out=None, hip=None):
         n_verts = int(verts.shape[0])
         n_tris = int(tris.shape[0]) if tris is not None else n_verts // 3
         keep = (verts, tris)
-    B = 1 << depth
-    words = int(lib().fhip_voxels_words(depth))       # (0 beyond depth 10: the call below refuses before it touches `out`)
-    if out is not None and not isinstance(out, np.ndarray):
-        import torch
-        assert out.is_cuda and out.is_contiguous() and out.numel() * out.element_size() >= 8 * words and out.data_ptr() % 8 == 0
-        ptr, out_dev = _dev_ptr(out), 1
-        bricks = (lambda: out.reshape(-1).view(torch.int64)[:words].view(B, B, B))
-    else:
-        if out is None:
-            out = np.zeros((B, B, B) if words else 0, np.uint64)
-        assert out.flags.c_contiguous and out.flags.writeable and out.nbytes >= 8 * words
-        ptr, out_dev = _p(out), 0
-        bricks = (lambda: out.reshape(-1).view(np.uint8)[:8 * words].view(np.uint64).reshape(B, B, B))
+    out, ptr, out_dev = _bitmap_out(depth, out, aligned=True)
     info = np.zeros(8, np.uint64)
     if isinstance(mesh, Mesh):
         st = lib().fhip_mesh_voxels(hip._h, mesh._owner.h, _p(m2w), depth, ptr, out_dev, _p(info))
@@ -2105,7 +2026,7 @@ def voxelize_mesh(mesh, depth, mesh_to_world=None, out=None, hip=None):
         st = lib().fhip_triangles_voxels(hip._h, vp, n_verts, tp, n_tris, dev, _p(m2w), depth, ptr, out_dev, _p(info))
     del keep
     hip.check(st)
-    res = Voxels(hip, bricks(), depth, {"cells": 0, "full": 0, "empty": 0, "leaf_cells": 0})
+    res = _bitmap_of(hip, out, out_dev, depth, {"cells": 0, "full": 0, "empty": 0, "leaf_cells": 0})
     res.mesh_info = dict(zip(MESH_INFO, (int(v) for v in info)))
     res._n = res.mesh_info["set_voxels"]
     if res.mesh_info["rejected"]:
@@ -2117,18 +2038,6 @@ def voxelize_mesh(mesh, depth, mesh_to_world=None, out=None, hip=None):
 # ---- the check of a triangle mesh: weld, edges, shells, volume (fhip_triangles_topology, fhip_mesh_topology) ----------------------
 TOPOLOGY_COUNTS = ("triangles", "rejected", "degenerate", "vertices", "edges", "boundary", "flipped", "nonmanifold", "unbalanced", "shells", "vertex_slots", "edge_slots")
 EDGE_KINDS = ("boundary", "flipped", "nonmanifold", "unbalanced")
-
-
-class _TopologyHandle:
-    """owner of an fhip_topology whose device arrays the views borrow"""
-    def __init__(self, h):
-        self.h = h
-        self._free = lib().fhip_topology_free      # (held here, as _MeshHandle holds its own)
-
-    def __del__(self):
-        if self.h and self._free is not None:
-            self._free(self.h)
-            self.h = None
 
 
 class Topology:
@@ -2253,25 +2162,13 @@ def mesh_topology(mesh, weld=None, hip=None, table_log2=0):
         st = lib().fhip_triangles_topology(hip._h, vp, n_verts, tp, n_tris, dev, int(tris is None if weld is None else bool(weld)), int(table_log2), C.byref(h))
     del keep
     hip.check(st)
-    res = Topology(_TopologyHandle(h.value), hip)
+    res = Topology(_Handle(h.value, lib().fhip_topology_free), hip)
     if res.counts["rejected"]:
         raise ValueError(f"mesh_topology: {res.counts['rejected']} of {res.counts['triangles']} triangles rejected: a coordinate that is not finite, or an index beyond the vertices")
     return res
 
 
 # ---- contours of a 2D slice: vertices on the crossing lattice edges, directed segments, loops, SVG (fhip_contour2d) -----------
-class _ContoursHandle:
-    """owner of an fhip_contours whose device arrays the views borrow"""
-    def __init__(self, h):
-        self.h = h
-        self._free = lib().fhip_contours_free      # (held here, as _MeshHandle holds its own)
-
-    def __del__(self):
-        if self.h and self._free is not None:
-            self._free(self.h)
-            self.h = None
-
-
 def contour_loops(next):
     """fhip_contour_loops (host only): the chains of a link array as [(ids uint32 array, closed bool)] - open chains first, from the
     vertices no segment arrives at in ascending order, then the closed loops, each from its smallest id, in ascending order of that"""
@@ -2395,7 +2292,7 @@ def contour(shape, width, height=None, z=0.0, world_to_model=None, vars=None):
         raise ValueError("MissingVar")
     hip.check(st)
     counts = np.zeros(4, np.uint64)
-    owner = _ContoursHandle(h.value)
+    owner = _Handle(h.value, lib().fhip_contours_free)
     lib().fhip_contours_counts(owner.h, _p(counts))
     return Contours(owner, width, height, z, counts[0], counts[1])
 

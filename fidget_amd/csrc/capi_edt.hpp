@@ -1,7 +1,7 @@
 // ---- the distance transform of a voxel bitmap -----------------------------------------------------------------------------------------------
 // fhip_voxels_distance (fidget_hip.h; the handle it declares void* is a fhip_distance): the three passes of edt.hip and the summary, all on
-// the context's stream; the host waits once, at the end, for the summary.  A fragment of the C ABI like capi_mesh.hpp, which includes it
-// and whose helpers (voxels_in, FxStage, ScratchBuf, mesh_now, cc_grid) it uses.  FHIP_MESH_TIMES: the passes' wall times on stderr.
+// the context's stream; the host waits once, at the end, for the summary.  A fragment of the C ABI, included by capi_mesh.hpp; uses
+// capi_mesh_util.hpp.  FHIP_MESH_TIMES: the passes' wall times on stderr.
 struct fhip_distance {
     uint64_t max_d2 = 0, arg = ~(uint64_t)0, n_fg = 0;       // arg: the smallest index with max_d2, all ones for "none"
     uint32_t depth = 0;
@@ -22,17 +22,7 @@ fhip_status fhip_voxels_distance(fhip_ctx* ctx, const uint64_t* bricks, uint32_t
     FxStage stage{ctx, on_device, {}};
     const uint64_t* d_bricks = nullptr;
     { const fhip_status s = voxels_in(ctx, stage, bricks, depth, d_bricks); if (s) return s; }
-    const bool times = getenv("FHIP_MESH_TIMES") != nullptr;
-    double t_last = times ? mesh_now() : 0;
-    auto mark = [&](const char* what) -> hipError_t {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess || !times) return e;
-        const hipError_t es = hipStreamSynchronize(st);
-        const double t = mesh_now();
-        if (what) fprintf(stderr, "fhip distance depth %u%s: %-16s %.6f s\n", depth, complement ? " complement" : "", what, t - t_last);
-        t_last = mesh_now();
-        return es;
-    };
+    PassTimes times(st, "fhip distance depth %u%s", depth, complement ? " complement" : "");
     std::unique_ptr<fhip_distance> R(new fhip_distance());
     R->depth = depth; R->complement = complement ? 1 : 0; R->device = ctx->device;
     const uint32_t B = 1u << depth, N = 4u << depth;
@@ -49,24 +39,24 @@ fhip_status fhip_voxels_distance(fhip_ctx* ctx, const uint64_t* bricks, uint32_t
     HIP_TRY(ctx, parts.ensure(((size_t)red_blocks + 1) * 16));
     uint64_t* const d_parts = (uint64_t*)parts.p;
     uint64_t* const d_sum = d_parts + 2 * (size_t)red_blocks;
-    HIP_TRY(ctx, mark("allocate"));
+    HIP_TRY(ctx, times.mark("allocate"));
     hipLaunchKernelGGL(fhm::k_edt_rows, dim3(B * B), dim3(256), 0, st, d_bricks, depth, complement ? ~(uint64_t)0 : (uint64_t)0, R->d_field);
-    HIP_TRY(ctx, mark("k_edt_rows"));
+    HIP_TRY(ctx, times.mark("k_edt_rows"));
     for (uint32_t axis = 1; axis <= 2; axis++) {
         if (in_lds) hipLaunchKernelGGL(fhm::k_edt_cols<true>, dim3(col_blocks), dim3(fhm::FH_EDT_LANES), lds_bytes, st, R->d_field, depth, axis, (fhedt::Entry*)nullptr);
         else hipLaunchKernelGGL(fhm::k_edt_cols<false>, dim3(col_blocks), dim3(fhm::FH_EDT_LANES), 0, st, R->d_field, depth, axis, (fhedt::Entry*)work.p);
-        HIP_TRY(ctx, mark(axis == 1 ? "k_edt_cols j" : "k_edt_cols k"));
+        HIP_TRY(ctx, times.mark(axis == 1 ? "k_edt_cols j" : "k_edt_cols k"));
     }
     hipLaunchKernelGGL(fhm::k_edt_reduce, dim3(red_blocks), dim3(256), 0, st, (const uint32_t*)R->d_field, depth, d_parts);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fhm::k_edt_reduce_sum, dim3(1), dim3(256), 0, st, (const uint64_t*)d_parts, red_blocks, d_sum);
-    HIP_TRY(ctx, mark("k_edt_reduce"));
+    HIP_TRY(ctx, times.mark("k_edt_reduce"));
     uint64_t sum[2] = {0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(sum, d_sum, 16, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (times) {          // (otherwise the two go with the scope)
+    if (times.on) {          // (otherwise the two go with the scope)
         work.release(); parts.release();
-        HIP_TRY(ctx, mark("release"));
+        HIP_TRY(ctx, times.mark("release"));
     }
     R->n_fg = sum[1];
     if (sum[0] != 0) { R->max_d2 = sum[0] >> 32; R->arg = 0xFFFFFFFFull - (sum[0] & 0xFFFFFFFFull); }
@@ -77,7 +67,7 @@ void fhip_distance_info(const void* h, uint64_t out[4]) {
     const fhip_distance* const d = (const fhip_distance*)h;
     out[0] = d ? d->max_d2 : 0; out[1] = d ? d->arg : ~(uint64_t)0; out[2] = d ? d->n_fg : 0; out[3] = d ? d->depth : 0;
 }
-const uint32_t* fhip_distance_dev(const void* h) { return h ? ((const fhip_distance*)h)->d_field : nullptr; }
+const uint32_t* fhip_distance_dev(const void* h) { return HANDLE_GET(fhip_distance, h, d_field); }
 fhip_status fhip_distance_slices(fhip_ctx* ctx, const void* h, uint32_t k0, uint32_t k1, uint32_t* out, int out_on_device) {
     const fhip_distance* const d = (const fhip_distance*)h;
     if (!ctx || !d) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_distance_slices: context and distance field");

@@ -2,18 +2,11 @@
 // fhip_voxels_flow, fhip_voxels_overhangs and fhip_voxels_heights (fidget_hip.h): one launch of flow.hip each, on the context's stream.
 // The effects' convention, as fhip_voxels_slices has it: device pointers are worked on in place and asynchronously; host arrays go
 // through the context's staging buffers (seeds or bricks io_a, blockers io_c, the result io_b) and the call waits for the result.  A
-// fragment of the C ABI like capi_vmesh.hpp, included by capi_mesh.hpp, whose helpers (voxels_in, FxStage, cc_grid) it uses.
-static fhip_status flow_bitmap_out(fhip_ctx* ctx, const char* what, uint32_t depth, const uint64_t* a, const uint64_t* b, const uint64_t* out, int out_on_device) {
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    if (!a) return fail(ctx, FHIP_ERR_UNSUPPORTED, what);
-    if (out == a || out == b) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap along a direction: the result must not be an input");
-    if (out_on_device && ((uintptr_t)out & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap on the device must be 8-byte aligned");
-    return FHIP_OK;
-}
+// fragment of the C ABI, included by capi_mesh.hpp; uses capi_mesh_util.hpp.
 fhip_status fhip_voxels_flow(fhip_ctx* ctx, const uint64_t* seeds, const uint64_t* blockers, uint32_t depth, int on_device, uint32_t dir, uint32_t flags,
                              uint64_t* out, int out_on_device) {
     if (!ctx || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_voxels_flow: context and result");
-    { const fhip_status s = flow_bitmap_out(ctx, "fhip_voxels_flow: the seeds", depth, seeds, blockers, out, out_on_device); if (s) return s; }
+    { const fhip_status s = bitmap_args(ctx, "fhip_voxels_flow: the seeds", depth, seeds, blockers, out, out_on_device); if (s) return s; }
     if (dir > 5) return fail(ctx, FHIP_ERR_UNSUPPORTED, "flow: a direction is 0 .. 5 = -x, +x, -y, +y, -z, +z");
     if (flags & ~fhfl::FLOW_WITH_SEEDS) return fail(ctx, FHIP_ERR_UNSUPPORTED, "flow: unknown flag bits");
     if (on_device && ((uintptr_t)blockers & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap on the device must be 8-byte aligned");
@@ -37,7 +30,7 @@ fhip_status fhip_voxels_flow(fhip_ctx* ctx, const uint64_t* seeds, const uint64_
 fhip_status fhip_voxels_overhangs(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t up, uint32_t reach2, int bed, uint64_t* out,
                                   int out_on_device) {
     if (!ctx || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_voxels_overhangs: context and result");
-    { const fhip_status s = flow_bitmap_out(ctx, "fhip_voxels_overhangs: the bitmap", depth, bricks, nullptr, out, out_on_device); if (s) return s; }
+    { const fhip_status s = bitmap_args(ctx, "fhip_voxels_overhangs: the bitmap", depth, bricks, nullptr, out, out_on_device); if (s) return s; }
     if (up > 5) return fail(ctx, FHIP_ERR_UNSUPPORTED, "overhangs: a direction is 0 .. 5 = -x, +x, -y, +y, -z, +z");
     if (reach2 > fhfl::MAX_REACH2) return fail(ctx, FHIP_ERR_UNSUPPORTED, "overhangs: reach2 at most 16 - a supporter lies in the brick or in one next to it");
     (void)hipSetDevice(ctx->device);
@@ -52,8 +45,7 @@ fhip_status fhip_voxels_overhangs(fhip_ctx* ctx, const uint64_t* bricks, uint32_
 }
 fhip_status fhip_voxels_heights(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t axis, int32_t* out, int out_on_device) {
     if (!ctx || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_voxels_heights: context and result");
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    if (!bricks) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_heights: the bitmap");
+    { const fhip_status s = bitmap_args(ctx, "fhip_voxels_heights: the bitmap", depth, bricks); if (s) return s; }
     if (axis > 2) return fail(ctx, FHIP_ERR_UNSUPPORTED, "heights: an axis is 0, 1, 2 = x, y, z");
     if ((const void*)out == (const void*)bricks) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap along a direction: the result must not be an input");
     if (out_on_device && ((uintptr_t)out & 3u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "heights to the device: the buffer must be 4-byte aligned");

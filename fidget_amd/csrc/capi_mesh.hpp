@@ -1,17 +1,11 @@
-// Fragment of capi.hip (meshing (the only fragment the mesh path owns: tools/src_hash.py leaves it out of the render path's hash)); not a stand-alone header: included by capi.hip only.
+// Fragment of capi.hip: the mesh path's single way into the translation unit (tools/src_hash.py leaves it and all it includes out of the
+// render path's hash).  It holds the octree mesher, the export and merge of its parts, binary STL and the gradients at a mesh's vertices;
+// what the mesh path's fragments share is in capi_mesh_util.hpp, included here at the top, and the fragments themselves are the list at
+// the end of this file.  Not a stand-alone header: included by capi.hip only.
 extern "C++" {
 #include "mesh_split.hpp"
 }
-// The context's pinned landing area (leaf records, octree cells and finished meshes on their way to the host), kept between calls - pinning
-// 17 GB takes over a second: at least `bytes`, and an eighth more where it has to grow
-static hipError_t pinned_ensure(fhip_ctx* ctx, size_t bytes) {
-    if (ctx->mesh_pinned_cap >= bytes) return hipSuccess;
-    if (ctx->mesh_pinned) (void)hipHostFree(ctx->mesh_pinned);
-    ctx->mesh_pinned = nullptr; ctx->mesh_pinned_cap = 0;
-    const hipError_t e = hipHostMalloc(&ctx->mesh_pinned, bytes + bytes / 8, hipHostMallocDefault);
-    if (e == hipSuccess) ctx->mesh_pinned_cap = bytes + bytes / 8;
-    return e;
-}
+#include "capi_mesh_util.hpp"
 // ---- meshing: the evaluation side of fidget_mesh::Octree::build (fidget-mesh/src/octree.rs) --------------------------------
 // CELL_TO_VERT_TO_EDGES of fidget-mesh/build.rs:26-160: per corner mask, the inside -> outside edges grouped into cell vertices
 // by connected region (filled regions first, then empty ones, each in ascending order of their corner sets)
@@ -422,12 +416,6 @@ static MeshDoes mesh_does(MeshMode mode, uint32_t n_parts, bool device_assembly)
     D.sample_leaves = !D.occupancy && !D.voxels;
     return D;
 }
-static double mesh_now() { return std::chrono::duration<double>(std::chrono::steady_clock::now().time_since_epoch()).count(); }
-struct ScratchBuf : DevBuf {       // a device buffer that goes with its scope (movable for std::vector, not copyable)
-    ScratchBuf() = default;
-    ScratchBuf(ScratchBuf&& o) noexcept { p = o.p; cap = o.cap; o.p = nullptr; o.cap = 0; }
-    ~ScratchBuf() { release(); }
-};
 static_assert(sizeof(fhsplit::TabEntry) == sizeof(uint2) && offsetof(fhsplit::TabEntry, off) == 0 && offsetof(fhsplit::TabEntry, len) == 4 &&
               alignof(fhsplit::TabEntry) <= alignof(uint2), "a split's table goes to the device as it is: {off, len} = uint2 {x, y}");
 #define MESH_CHECK(call) do { const hipError_t e_ = (call); if (e_ != hipSuccess) return hip_failed(#call, e_); } while (0)
@@ -1260,23 +1248,6 @@ void fhip_mesh_leaves(const fhip_mesh* m, void* out) { memcpy(out, m->leaves.dat
 const float* fhip_mesh_vertices_dev(const fhip_mesh* m) { return m ? (const float*)m->d_vertices : nullptr; }
 const uint64_t* fhip_mesh_triangles_dev(const fhip_mesh* m) { return m ? m->d_triangles : nullptr; }
 uint64_t fhip_mesh_stl_bytes(const fhip_mesh* m) { return fhm::FH_STL_HEADER + (uint64_t)fhm::FH_STL_RECORD * (m ? m->triangles.size() : 0); }
-// `bytes` from device memory to a host buffer of the caller's through the context's pinned landing area, as a built mesh travels
-static fhip_status mesh_to_host(fhip_ctx* ctx, void* dst, const void* d_src, size_t bytes) {
-    if (!bytes) return FHIP_OK;
-    HIP_TRY(ctx, pinned_ensure(ctx, bytes));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->mesh_pinned, d_src, bytes, hipMemcpyDeviceToHost, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    const size_t CH = (size_t)4 << 20;
-    fhmesh::parallel_for((bytes + CH - 1) / CH, [&](size_t i) { memcpy((char*)dst + i * CH, (const char*)ctx->mesh_pinned + i * CH, std::min(CH, bytes - i * CH)); });
-    return FHIP_OK;
-}
-// host arrays to the context's buffer `b`; waits, so that the caller's arrays are free again when the call returns
-static fhip_status mesh_upload(fhip_ctx* ctx, DevBuf& b, const void* src, size_t bytes) {
-    HIP_TRY(ctx, b.ensure(std::max<size_t>(bytes, 4)));
-    if (bytes) HIP_TRY(ctx, hipMemcpyAsync(b.p, src, bytes, hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));
-    return FHIP_OK;
-}
 // k_mesh_stl over device arrays; `out`: the caller's device buffer (asynchronous), or a host buffer (filled when the call returns)
 static fhip_status stl_pack(fhip_ctx* ctx, const fhmesh::V3* d_verts, const uint64_t* d_tris, uint64_t n_tris, void* out, int out_is_device) {
     const size_t bytes = fhm::FH_STL_HEADER + (size_t)fhm::FH_STL_RECORD * n_tris;
@@ -1383,395 +1354,24 @@ fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const f
     return out_is_device ? FHIP_OK : mesh_to_host(ctx, out, d_out, (size_t)n * 16);
 }
 
-// ---- the voxel bitmap ---------------------------------------------------------------------------------------------------------------------
-// The voxel bitmap (fidget_hip.h): occupancy's level loop with the bitmap kernels of mesh.hip; a host `out` is filled from the context's
-// buffer through the pinned landing area
-uint64_t fhip_voxels_words(uint32_t depth) { return fhvox::n_words(depth); }
-fhip_status fhip_shape_voxels(fhip_ctx* ctx, const fhip_tape* tape, uint32_t depth, const float* world_to_model, const int32_t* axis_slots,
-                              const uint64_t* var_keys, const float* var_values, uint32_t n_vars, uint64_t* out, int out_is_device, uint64_t cells[4]) {
-    if (!ctx || !tape || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_shape_voxels: context, tape and output buffer");
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10: the bitmap of a grid of more than 4096^3 voxels exceeds 8 GiB");
-    const size_t bytes = (size_t)fhvox::n_words(depth) * 8;
-    VoxTarget vt{out, cells};
-    if (out_is_device) {
-        if ((uintptr_t)out & 7u) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxels to the device: the buffer must be 8-byte aligned");
-    } else {
-        (void)hipSetDevice(ctx->device);
-        HIP_TRY(ctx, ctx->io_d.ensure(bytes));
-        vt.d_out = (uint64_t*)ctx->io_d.p;
-    }
-    fhip_mesh* m = nullptr;
-    const fhip_status st = mesh_run(ctx, tape, depth, world_to_model, axis_slots, var_keys, var_values, n_vars, MESH_VOX, 0, 1, &m, nullptr, &vt);
-    delete m;
-    if (st || out_is_device) return st;
-    return mesh_to_host(ctx, out, vt.d_out, bytes);
-}
-// What is made of a bitmap (k_vox_slices, k_vox_layer_counts): the effects' convention - device pointers and asynchronous, or host buffers
-static fhip_status voxels_in(fhip_ctx* ctx, FxStage& st, const uint64_t* bricks, uint32_t depth, const uint64_t*& d_bricks) {
-    if (st.on_device && ((uintptr_t)bricks & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap on the device must be 8-byte aligned");
-    hipError_t e = hipSuccess;
-    d_bricks = (const uint64_t*)st.in(ctx->io_a, bricks, (size_t)fhvox::n_words(depth) * 8, e);
-    HIP_TRY(ctx, e);
-    return FHIP_OK;
-}
-fhip_status fhip_voxels_slices(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint32_t k0, uint32_t k1, uint8_t* out, int on_device) {
-    if (!ctx) return FHIP_ERR_BAD_TAPE;
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    const uint32_t N = 4u << depth;
-    if (k0 > k1 || k1 > N) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel slices: layers k0 <= k1 <= 4 << depth");
-    if (k0 == k1) return FHIP_OK;
-    if (!bricks || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_slices: bitmap and output buffer");
-    if (on_device && ((uintptr_t)out & 15u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel slices to the device: the buffer must be 16-byte aligned");
-    (void)hipSetDevice(ctx->device);
-    FxStage st{ctx, on_device, {}};
-    const uint64_t* d_bricks = nullptr;
-    { const fhip_status s = voxels_in(ctx, st, bricks, depth, d_bricks); if (s) return s; }
-    hipError_t e = hipSuccess;
-    uint8_t* const d_out = (uint8_t*)st.out(ctx->io_b, out, (size_t)(k1 - k0) * N * N, e); HIP_TRY(ctx, e);
-    const uint64_t runs = ((uint64_t)(k1 - k0) * N) << (depth < 2 ? 0 : depth - 2);
-    const uint32_t nb = (uint32_t)std::min<uint64_t>((runs + 255) / 256, fhm::FH_VOX_SLICE_BLOCKS);
-    hipLaunchKernelGGL(fhm::k_vox_slices, dim3(nb), dim3(256), 0, ctx->stream, d_bricks, depth, k0, k1, d_out);
-    return st.finish();
-}
-fhip_status fhip_voxels_layer_counts(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, uint64_t* out, int on_device) {
-    if (!ctx) return FHIP_ERR_BAD_TAPE;
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    if (!bricks || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_layer_counts: bitmap and output buffer");
-    if (on_device && ((uintptr_t)out & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "layer counts to the device: the buffer must be 8-byte aligned");
-    (void)hipSetDevice(ctx->device);
-    FxStage st{ctx, on_device, {}};
-    const uint64_t* d_bricks = nullptr;
-    { const fhip_status s = voxels_in(ctx, st, bricks, depth, d_bricks); if (s) return s; }
-    const uint32_t B = 1u << depth, N = 4u << depth;
-    const uint32_t n_parts = (uint32_t)std::min<uint64_t>((((uint64_t)B * B) + 255) / 256, fhm::FH_VOX_COUNT_PARTS);
-    hipError_t e = hipSuccess;
-    uint64_t* const d_out = (uint64_t*)st.out(ctx->io_b, out, (size_t)N * 8, e); HIP_TRY(ctx, e);
-    HIP_TRY(ctx, ctx->io_c.ensure((size_t)B * n_parts * 4 * 8));
-    hipLaunchKernelGGL(fhm::k_vox_layer_counts, dim3(n_parts, B), dim3(256), 0, ctx->stream, d_bricks, depth, (uint64_t*)ctx->io_c.p);
-    HIP_TRY(ctx, hipGetLastError());
-    hipLaunchKernelGGL(fhm::k_vox_layer_sum, dim3((N + 255) / 256), dim3(256), 0, ctx->stream, (const uint64_t*)ctx->io_c.p, n_parts, N, d_out);
-    return st.finish();
-}
-
-// ---- contours of a 2D slice -----------------------------------------------------------------------------------------------------------------
-// fhip_contour2d (fidget_hip.h; the handle it declares void* is a fhip_contours): the pixel-perfect render2d frame into the context's buffer, then the four k_ctr_* passes of mesh.hip with
-// the two prefix sums between them, all on the context's stream.  The host waits once in the middle - for the two totals, which size the
-// arrays of the result - and once at the end.
-struct fhip_contours {
-    uint64_t n_vertices = 0, n_segments = 0;
-    uint32_t width = 0, height = 0;
-    int device = 0;
-    float2* d_vertices = nullptr;
-    uint2* d_segments = nullptr;
-    uint32_t* d_next = nullptr;
-    ~fhip_contours() {
-        if (d_vertices) (void)hipFree(d_vertices);
-        if (d_segments) (void)hipFree(d_segments);
-        if (d_next) (void)hipFree(d_next);
-    }
-};
-// k_scan_block / k_scan_add over `n` counts (WalkDevX::scan) with the block totals of every level in `tmp`, ctr_scan_words(n) words of it
-static size_t ctr_scan_words(uint32_t n) {
-    size_t t = 0;
-    for (uint32_t nb = (uint32_t)(((uint64_t)n + fhm::FH_SCAN_PER_BLOCK) / fhm::FH_SCAN_PER_BLOCK); nb > 1; nb = (nb + fhm::FH_SCAN_PER_BLOCK) / fhm::FH_SCAN_PER_BLOCK) t += 2 * (size_t)nb + 1;       // (64 bits: n up to 2^32 - 2, the nodes of fhip_voxels_components)
-    return t;
-}
-static hipError_t ctr_scan(hipStream_t st, const uint32_t* in, uint32_t n, uint32_t* out, uint32_t* tmp) {
-    const uint32_t nb = (uint32_t)(((uint64_t)n + fhm::FH_SCAN_PER_BLOCK) / fhm::FH_SCAN_PER_BLOCK);       // blocks over the n + 1 sums
-    if (nb == 1) {
-        hipLaunchKernelGGL(fhm::k_scan_block, dim3(1), dim3(256), 0, st, in, n, out, (uint32_t*)nullptr);
-        return hipGetLastError();
-    }
-    uint32_t* const sums = tmp;
-    uint32_t* const sums_off = tmp + nb;
-    hipLaunchKernelGGL(fhm::k_scan_block, dim3(nb), dim3(256), 0, st, in, n, out, sums);
-    hipError_t e = hipGetLastError();
-    if (e != hipSuccess) return e;
-    e = ctr_scan(st, sums, nb, sums_off, tmp + 2 * (size_t)nb + 1);
-    if (e != hipSuccess) return e;
-    hipLaunchKernelGGL(fhm::k_scan_add, dim3((unsigned)(((uint64_t)n + 1 + 255) / 256)), dim3(256), 0, st, out, n, (const uint32_t*)sums_off);
-    return hipGetLastError();
-}
-fhip_status fhip_contour2d(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render2d_config* cfg, void** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !tape || !cfg || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_contour2d: context, tape, configuration and result");
-    const uint32_t W = cfg->width, H = cfg->height;
-    if (!fhctr::size_ok(W, H)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "contours: 2^32 pixels or lattice edges and more");
-    (void)hipSetDevice(ctx->device);
-    std::unique_ptr<fhip_contours> R(new fhip_contours());
-    R->width = W; R->height = H; R->device = ctx->device;
-    if (W == 0 || H == 0) { *out = R.release(); return FHIP_OK; }
-    fhip_render2d_config c = *cfg;
-    c.pixel_perfect = 1;        // a true value at every pixel, no fills
-    std::shared_ptr<const fhip_tape> bound;     // (as fhip_render2d)
-    if (tape->t.n_vars > FH_MAX_INPUTS) {
-        const fhip_status bs = bound_tape(ctx, tape, c.axis_slots, c.var_keys, c.var_values, c.n_vars, bound);
-        if (bs) return bs;
-        tape = bound.get();
-        c.axis_slots = BOUND_AXES; c.var_keys = nullptr; c.var_values = nullptr; c.n_vars = 0;
-    }
-    ctx->tune_cur = -1;
-    ctx->tune_last_key = 0;
-    const size_t npix = (size_t)W * H;
-    HIP_TRY(ctx, ctx->io_a.ensure(npix * 4));
-    const float* const img = (const float*)ctx->io_a.p;
-    { const fhip_status st = render2d_frame(ctx, tape, &c, (float*)ctx->io_a.p, 1); if (st) return st; }
-    // what the passes hand to each other, in one buffer: the edges' ballot words, the block counts and their sums, the scans' block totals
-    const uint32_t eb = (uint32_t)((fhctr::n_edges(W, H) + 255) / 256), cb = (uint32_t)((fhctr::n_cells(W, H) + 255) / 256);
-    const size_t scan_words = std::max(ctr_scan_words(eb), ctr_scan_words(cb));
-    HIP_TRY(ctx, ctx->io_b.ensure((size_t)eb * 32 + ((size_t)2 * eb + 2 * (size_t)cb + 2 + scan_words) * 4 + 16));
-    uint64_t* const bits = (uint64_t*)ctx->io_b.p;
-    uint32_t* const e_cnt = (uint32_t*)(bits + (size_t)eb * 4);
-    uint32_t* const e_off = e_cnt + eb;          // eb + 1
-    uint32_t* const c_cnt = e_off + eb + 1;
-    uint32_t* const c_off = c_cnt + cb;          // cb + 1
-    uint32_t* const scan_tmp = c_off + cb + 1;
-    hipStream_t st = ctx->stream;
-    auto grid = [](uint32_t nb) { return dim3(std::max(1u, std::min(nb, fhm::FH_CTR_BLOCKS))); };
-    if (eb) {
-        hipLaunchKernelGGL(fhm::k_ctr_edges, grid(eb), dim3(256), 0, st, img, W, H, bits, e_cnt);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, ctr_scan(st, e_cnt, eb, e_off, scan_tmp));
-    if (cb) {
-        hipLaunchKernelGGL(fhm::k_ctr_cells, grid(cb), dim3(256), 0, st, img, W, H, c_cnt);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    HIP_TRY(ctx, ctr_scan(st, c_cnt, cb, c_off, scan_tmp));      // (the same block totals' room: the stream keeps the two scans in order)
-    uint32_t totals[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(&totals[0], e_off + eb, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipMemcpyAsync(&totals[1], c_off + cb, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    R->n_vertices = totals[0]; R->n_segments = totals[1];
-    if (totals[0]) {
-        HIP_TRY(ctx, hipMalloc((void**)&R->d_vertices, (size_t)totals[0] * 8));
-        HIP_TRY(ctx, hipMalloc((void**)&R->d_next, (size_t)totals[0] * 4));
-        hipLaunchKernelGGL(fhm::k_ctr_vertices, grid(eb), dim3(256), 0, st, img, W, H, (const uint64_t*)bits, (const uint32_t*)e_off, R->d_vertices, R->d_next);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    if (totals[1]) {       // (a segment joins two vertices: there are some)
-        HIP_TRY(ctx, hipMalloc((void**)&R->d_segments, (size_t)totals[1] * 8));
-        hipLaunchKernelGGL(fhm::k_ctr_segments, grid(cb), dim3(256), 0, st, img, W, H, (const uint64_t*)bits, (const uint32_t*)e_off, (const uint32_t*)c_off, R->d_segments, R->d_next);
-        HIP_TRY(ctx, hipGetLastError());
-    }
-    { const fhip_status fs = finish_render(ctx); if (fs) return fs; }      // waits for the stream; the frame's own checks
-    *out = R.release();
-    return FHIP_OK;
-}
-void fhip_contours_counts(const void* h, uint64_t out[4]) {
-    const fhip_contours* const c = (const fhip_contours*)h;
-    out[0] = c ? c->n_vertices : 0; out[1] = c ? c->n_segments : 0; out[2] = c ? c->width : 0; out[3] = c ? c->height : 0;
-}
-static fhip_status contours_to_host(const fhip_contours* c, void* dst, const void* d_src, size_t bytes) {
-    if (!c || (bytes && !dst)) return FHIP_ERR_BAD_TAPE;
-    if (!bytes) return FHIP_OK;
-    (void)hipSetDevice(c->device);
-    return hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FHIP_OK : FHIP_ERR_HIP;
-}
-fhip_status fhip_contours_vertices(const void* h, float* out) { const fhip_contours* const c = (const fhip_contours*)h; return contours_to_host(c, out, c ? c->d_vertices : nullptr, c ? (size_t)c->n_vertices * 8 : 0); }
-fhip_status fhip_contours_segments(const void* h, uint32_t* out) { const fhip_contours* const c = (const fhip_contours*)h; return contours_to_host(c, out, c ? c->d_segments : nullptr, c ? (size_t)c->n_segments * 8 : 0); }
-fhip_status fhip_contours_next(const void* h, uint32_t* out) { const fhip_contours* const c = (const fhip_contours*)h; return contours_to_host(c, out, c ? c->d_next : nullptr, c ? (size_t)c->n_vertices * 4 : 0); }
-const float* fhip_contours_vertices_dev(const void* h) { const fhip_contours* const c = (const fhip_contours*)h; return c ? (const float*)c->d_vertices : nullptr; }
-const uint32_t* fhip_contours_segments_dev(const void* h) { const fhip_contours* const c = (const fhip_contours*)h; return c ? (const uint32_t*)c->d_segments : nullptr; }
-void fhip_contours_free(void* h) { delete (fhip_contours*)h; }
-fhip_status fhip_contour_loops(const uint32_t* next, uint64_t n, uint32_t* order, uint64_t* loop_start, uint8_t* closed, uint64_t* n_loops) {
-    if (n_loops) *n_loops = 0;
-    if (n >= fhctr::NONE || (n && !next)) return FHIP_ERR_UNSUPPORTED;
-    return fhctr::follow_loops(next, n, order, loop_start, closed, n_loops) ? FHIP_OK : FHIP_ERR_UNSUPPORTED;
-}
-
-// ---- connected components of a voxel bitmap --------------------------------------------------------------------------------------------------
-// fhip_voxels_components (fidget_hip.h; the handle it declares void* is a fhip_components): the k_cc_* passes of mesh.hip with the prefix sums
-// of the contours between them, all on the context's stream.  The host waits twice on the way - for the number of nodes, which sizes their
-// arrays, and for the number of components, which sizes the table - and once at the end.  FHIP_MESH_TIMES: the passes' wall times on stderr.
-struct fhip_components {
-    uint64_t n_comps = 0, n_nodes = 0, n_voxels = 0;
-    uint32_t depth = 0, conn = 6;
-    int complement = 0, device = 0;
-    uint32_t* d_base = nullptr;          // [B^3 + 1]: a brick's first node
-    uint32_t* d_comp = nullptr;          // [n_nodes]: a node's component
-    std::vector<uint64_t> size;          // the table, on the host
-    std::vector<uint32_t> seed, lo, hi;
-    std::vector<uint8_t> border;
-    ~fhip_components() {
-        if (d_base) (void)hipFree(d_base);
-        if (d_comp) (void)hipFree(d_comp);
-    }
-};
-static dim3 cc_grid(uint64_t n) { return dim3((unsigned)std::max<uint64_t>(1, (n + 255) / 256)); }
-fhip_status fhip_voxels_components(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint32_t connectivity, int complement, void** out) {
-    if (out) *out = nullptr;
-    if (!ctx || !out) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_voxels_components: context and result");
-    if (!fhcc::conn_ok(connectivity)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "components: connectivity 6 or 26");
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    if (!bricks) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_voxels_components: the bitmap");
-    (void)hipSetDevice(ctx->device);
-    hipStream_t st = ctx->stream;
-    FxStage stage{ctx, on_device, {}};
-    const uint64_t* d_bricks = nullptr;
-    { const fhip_status s = voxels_in(ctx, stage, bricks, depth, d_bricks); if (s) return s; }
-    const bool times = getenv("FHIP_MESH_TIMES") != nullptr;
-    double t_last = 0;
-    auto mark = [&](const char* what) -> hipError_t {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess || !times) return e;
-        const hipError_t es = hipStreamSynchronize(st);
-        const double t = mesh_now();
-        if (what) fprintf(stderr, "fhip components depth %u conn %u%s: %-16s %.6f s\n", depth, connectivity, complement ? " complement" : "", what, t - t_last);
-        t_last = mesh_now();
-        return es;
-    };
-    std::unique_ptr<fhip_components> R(new fhip_components());
-    R->depth = depth; R->conn = connectivity; R->complement = complement ? 1 : 0; R->device = ctx->device;
-    const uint64_t n_words = fhvox::n_words(depth), flip = complement ? ~(uint64_t)0 : 0;
-    HIP_TRY(ctx, hipMalloc((void**)&R->d_base, (size_t)(n_words + 1) * 4));
-    ScratchBuf counts, node_tmp, scan_tmp, scan_tmp2;
-    HIP_TRY(ctx, counts.ensure((size_t)n_words * 4 + 24));          // the bricks' node counts, then the two totals
-    HIP_TRY(ctx, scan_tmp.ensure((ctr_scan_words((uint32_t)n_words) + 1) * 4));
-    uint32_t* const cnt = (uint32_t*)counts.p;
-    unsigned long long* const totals = (unsigned long long*)((char*)counts.p + (((size_t)n_words * 4 + 7) & ~(size_t)7));
-    HIP_TRY(ctx, hipMemsetAsync(totals, 0, 16, st));
-    HIP_TRY(ctx, mark(nullptr));
-    hipLaunchKernelGGL(fhm::k_cc_count, cc_grid(n_words), dim3(256), 0, st, d_bricks, n_words, flip, connectivity, cnt, totals);
-    HIP_TRY(ctx, mark("k_cc_count"));
-    uint64_t tot[2] = {0, 0};
-    HIP_TRY(ctx, hipMemcpyAsync(tot, totals, 16, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (tot[0] > 0xFFFFFFFEull) return fail(ctx, FHIP_ERR_OVERFLOW, "components: more than 2^32 - 2 nodes (the bricks' own components)");
-    const uint64_t n_nodes = tot[0];
-    R->n_nodes = n_nodes; R->n_voxels = tot[1];
-    HIP_TRY(ctx, ctr_scan(st, cnt, (uint32_t)n_words, R->d_base, (uint32_t*)scan_tmp.p));
-    HIP_TRY(ctx, mark("scan (base)"));
-    if (n_nodes == 0) {         // an empty foreground: no components, and the later calls find no set bit to look up
-        HIP_TRY(ctx, hipStreamSynchronize(st));
-        *out = R.release();
-        return FHIP_OK;
-    }
-    // parent [n_nodes], the roots' ranks [n_nodes + 1]; the flags, and then the components in their place, are the handle's array
-    HIP_TRY(ctx, hipMalloc((void**)&R->d_comp, (size_t)n_nodes * 4));
-    HIP_TRY(ctx, node_tmp.ensure(((size_t)2 * n_nodes + 1) * 4));
-    HIP_TRY(ctx, scan_tmp2.ensure((ctr_scan_words((uint32_t)n_nodes) + 1) * 4));
-    uint32_t* const parent = (uint32_t*)node_tmp.p;
-    uint32_t* const rank = parent + n_nodes;
-    hipLaunchKernelGGL(fhm::k_cc_init, cc_grid(n_nodes), dim3(256), 0, st, parent, n_nodes);
-    HIP_TRY(ctx, mark("k_cc_init"));
-    hipLaunchKernelGGL(fhm::k_cc_merge, cc_grid(n_words), dim3(256), 0, st, d_bricks, depth, flip, connectivity, (const uint32_t*)R->d_base, parent);
-    HIP_TRY(ctx, mark("k_cc_merge"));
-    hipLaunchKernelGGL(fhm::k_cc_flatten, cc_grid(n_nodes), dim3(256), 0, st, parent, n_nodes);
-    HIP_TRY(ctx, mark("k_cc_flatten"));
-    hipLaunchKernelGGL(fhm::k_cc_roots, cc_grid(n_nodes), dim3(256), 0, st, (const uint32_t*)parent, n_nodes, R->d_comp);
-    HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, ctr_scan(st, R->d_comp, (uint32_t)n_nodes, rank, (uint32_t*)scan_tmp2.p));
-    hipLaunchKernelGGL(fhm::k_cc_number, cc_grid(n_nodes), dim3(256), 0, st, (const uint32_t*)parent, (const uint32_t*)rank, n_nodes, R->d_comp);
-    HIP_TRY(ctx, mark("roots+scan+number"));
-    uint32_t n_comps = 0;
-    HIP_TRY(ctx, hipMemcpyAsync(&n_comps, rank + n_nodes, 4, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    R->n_comps = n_comps;
-    // the table on the device: size u64 [c], then lo, hi, seed u32 [c][3] and border u32 [c]
-    ScratchBuf table;
-    const size_t c = n_comps, table_bytes = c * 8 + c * 10 * 4;
-    HIP_TRY(ctx, table.ensure(table_bytes));
-    unsigned long long* const d_size = (unsigned long long*)table.p;
-    uint32_t* const d_lo = (uint32_t*)(d_size + c);
-    uint32_t* const d_hi = d_lo + 3 * c;
-    uint32_t* const d_seed = d_hi + 3 * c;
-    uint32_t* const d_border = d_seed + 3 * c;
-    HIP_TRY(ctx, hipMemsetAsync(table.p, 0, table_bytes, st));
-    HIP_TRY(ctx, hipMemsetAsync(d_lo, 0xFF, 3 * c * 4, st));
-    HIP_TRY(ctx, mark(nullptr));
-    hipLaunchKernelGGL(fhm::k_cc_table, cc_grid(n_words), dim3(256), 0, st, d_bricks, depth, flip, connectivity, (const uint32_t*)R->d_base, (const uint32_t*)R->d_comp,
-                       (const uint32_t*)parent, d_size, d_lo, d_hi, d_border, d_seed);
-    HIP_TRY(ctx, mark("k_cc_table"));
-    std::vector<uint8_t> host(table_bytes);
-    HIP_TRY(ctx, hipMemcpyAsync(host.data(), table.p, table_bytes, hipMemcpyDeviceToHost, st));
-    HIP_TRY(ctx, hipStreamSynchronize(st));
-    R->size.resize(c); R->lo.resize(3 * c); R->hi.resize(3 * c); R->seed.resize(3 * c); R->border.resize(c);
-    memcpy(R->size.data(), host.data(), c * 8);
-    memcpy(R->lo.data(), host.data() + c * 8, 3 * c * 4);
-    memcpy(R->hi.data(), host.data() + c * 8 + 3 * c * 4, 3 * c * 4);
-    memcpy(R->seed.data(), host.data() + c * 8 + 6 * c * 4, 3 * c * 4);
-    const uint32_t* const hb = (const uint32_t*)(host.data() + c * 8 + 9 * c * 4);
-    for (size_t k = 0; k < c; k++) R->border[k] = hb[k] ? 1 : 0;
-    *out = R.release();
-    return FHIP_OK;
-}
-void fhip_components_counts(const void* h, uint64_t out[4]) {
-    const fhip_components* const c = (const fhip_components*)h;
-    out[0] = c ? c->n_comps : 0; out[1] = c ? c->n_nodes : 0; out[2] = c ? c->n_voxels : 0; out[3] = c ? c->depth : 0;
-}
-fhip_status fhip_components_table(const void* h, uint64_t* size, uint32_t* seed, uint32_t* lo, uint32_t* hi, uint8_t* border) {
-    const fhip_components* const c = (const fhip_components*)h;
-    if (!c) return FHIP_ERR_BAD_TAPE;
-    const size_t n = (size_t)c->n_comps;
-    if (n == 0) return FHIP_OK;
-    if (size) memcpy(size, c->size.data(), n * 8);
-    if (seed) memcpy(seed, c->seed.data(), 3 * n * 4);
-    if (lo) memcpy(lo, c->lo.data(), 3 * n * 4);
-    if (hi) memcpy(hi, c->hi.data(), 3 * n * 4);
-    if (border) memcpy(border, c->border.data(), n);
-    return FHIP_OK;
-}
-fhip_status fhip_components_label_slices(fhip_ctx* ctx, const void* h, const uint64_t* bricks, int bricks_on_device, uint32_t k0, uint32_t k1, int32_t* out, int out_on_device) {
-    const fhip_components* const c = (const fhip_components*)h;
-    if (!ctx || !c) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_components_label_slices: context and components");
-    if (ctx->device != c->device) return fail(ctx, FHIP_ERR_UNSUPPORTED, "components: labelled on another device");
-    const uint32_t N = 4u << c->depth;
-    if (k0 > k1 || k1 > N) return fail(ctx, FHIP_ERR_UNSUPPORTED, "label slices: layers k0 <= k1 <= 4 << depth");
-    if (c->n_comps > 0x7FFFFFFFull) return fail(ctx, FHIP_ERR_UNSUPPORTED, "label slices: more than 2^31 - 1 components do not fit an int32 image");
-    if (k0 == k1) return FHIP_OK;
-    if (!bricks || !out) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_components_label_slices: bitmap and output buffer");
-    if (out_on_device && ((uintptr_t)out & 15u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "label slices to the device: the buffer must be 16-byte aligned");
-    (void)hipSetDevice(ctx->device);
-    FxStage in{ctx, bricks_on_device, {}}, st{ctx, out_on_device, {}};
-    const uint64_t* d_bricks = nullptr;
-    { const fhip_status s = voxels_in(ctx, in, bricks, c->depth, d_bricks); if (s) return s; }
-    hipError_t e = hipSuccess;
-    int32_t* const d_out = (int32_t*)st.out(ctx->io_b, out, (size_t)(k1 - k0) * N * N * 4, e); HIP_TRY(ctx, e);
-    const uint64_t runs = ((uint64_t)(k1 - k0) * N) << (c->depth < 2 ? 0 : c->depth - 2);
-    const uint32_t nb = (uint32_t)std::min<uint64_t>((runs + 255) / 256, fhm::FH_VOX_SLICE_BLOCKS);
-    hipLaunchKernelGGL(fhm::k_cc_label_slices, dim3(nb), dim3(256), 0, ctx->stream, d_bricks, c->depth, c->complement ? ~(uint64_t)0 : (uint64_t)0, c->conn,
-                       (const uint32_t*)c->d_base, (const uint32_t*)c->d_comp, k0, k1, d_out);
-    return st.finish();
-}
-fhip_status fhip_components_extract(fhip_ctx* ctx, const void* h, const uint64_t* bricks, int bricks_on_device, const uint32_t* ids, uint64_t n_ids, uint64_t* out, int out_on_device) {
-    const fhip_components* const c = (const fhip_components*)h;
-    if (!ctx || !c) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_components_extract: context and components");
-    if (ctx->device != c->device) return fail(ctx, FHIP_ERR_UNSUPPORTED, "components: labelled on another device");
-    if (!bricks || !out || (n_ids && !ids)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "fhip_components_extract: bitmap, ids and output buffer");
-    if (out_on_device && ((uintptr_t)out & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "extract to the device: the buffer must be 8-byte aligned");
-    std::vector<uint8_t> chosen((size_t)c->n_comps + 1, 0);
-    for (uint64_t k = 0; k < n_ids; k++) {
-        if (ids[k] >= c->n_comps) return fail(ctx, FHIP_ERR_UNSUPPORTED, "extract: a component id beyond the number of components");
-        chosen[ids[k]] = 1;
-    }
-    (void)hipSetDevice(ctx->device);
-    FxStage in{ctx, bricks_on_device, {}}, st{ctx, out_on_device, {}};
-    const uint64_t* d_bricks = nullptr;
-    { const fhip_status s = voxels_in(ctx, in, bricks, c->depth, d_bricks); if (s) return s; }
-    const uint64_t n_words = fhvox::n_words(c->depth);
-    hipError_t e = hipSuccess;
-    uint64_t* const d_out = (uint64_t*)st.out(ctx->io_b, out, (size_t)n_words * 8, e); HIP_TRY(ctx, e);
-    HIP_TRY(ctx, ctx->io_c.ensure(chosen.size()));
-    HIP_TRY(ctx, hipMemcpyAsync(ctx->io_c.p, chosen.data(), chosen.size(), hipMemcpyHostToDevice, ctx->stream));
-    HIP_TRY(ctx, hipStreamSynchronize(ctx->stream));          // (`chosen` is pageable and leaves with this call)
-    hipLaunchKernelGGL(fhm::k_cc_extract, cc_grid(n_words), dim3(256), 0, ctx->stream, d_bricks, n_words, c->complement ? ~(uint64_t)0 : (uint64_t)0, c->conn,
-                       (const uint32_t*)c->d_base, (const uint32_t*)c->d_comp, (const uint8_t*)ctx->io_c.p, d_out);
-    return st.finish();
-}
-void fhip_components_free(void* h) { delete (fhip_components*)h; }
-
-// the distance transform of a voxel bitmap (fhip_voxels_distance): a fragment of its own, with the helpers above
+// ---- the mesh path's other fragments, one per subject, in dependency order; each may use capi_mesh_util.hpp and what stands before it ----
+// the voxel bitmap of a shape - made by mesh_run above - and its slices and layer counts (fhip_shape_voxels, fhip_voxels_slices, ..)
+#include "capi_voxels.hpp"
+// the contours of a 2D slice (fhip_contour2d)
+#include "capi_contour.hpp"
+// the connected components of a voxel bitmap (fhip_voxels_components)
+#include "capi_cc.hpp"
+// the distance transform of a voxel bitmap (fhip_voxels_distance)
 #include "capi_edt.hpp"
-// the local thickness of such a distance field (fhip_distance_thickness): likewise
+// the local thickness of such a distance field (fhip_distance_thickness): after capi_edt.hpp, whose fhip_distance it makes
 #include "capi_thick.hpp"
-// the boundary mesh of a voxel bitmap (fhip_voxels_mesh, fhip_voxels_surface): likewise
+// the boundary mesh of a voxel bitmap (fhip_voxels_mesh, fhip_voxels_surface)
 #include "capi_vmesh.hpp"
-// a voxel bitmap along a direction (fhip_voxels_flow, fhip_voxels_overhangs, fhip_voxels_heights): likewise
+// a voxel bitmap along a direction (fhip_voxels_flow, fhip_voxels_overhangs, fhip_voxels_heights)
 #include "capi_flow.hpp"
-// a triangle mesh to a voxel bitmap (fhip_triangles_voxels, fhip_mesh_voxels): likewise
+// a triangle mesh to a voxel bitmap (fhip_triangles_voxels, fhip_mesh_voxels)
 #include "capi_trivox.hpp"
-// the check of a triangle mesh (fhip_triangles_topology, fhip_mesh_topology): likewise
+// the check of a triangle mesh (fhip_triangles_topology, fhip_mesh_topology)
 #include "capi_topo.hpp"
-// the outlines of a voxel bitmap's layers (fhip_voxels_outlines): likewise
+// the outlines of a voxel bitmap's layers (fhip_voxels_outlines)
 #include "capi_outline.hpp"

@@ -4,8 +4,7 @@
 // device are read in place.  The host waits for the layers' vertex counts - they size the arrays, and 2^32 vertices or more end the
 // call there, before anything is written - for the number of loops, which sizes their table, and at the end: the call blocks, as
 // fhip_contour2d does.  The vertices' arrays - xy, next, loop_of - are the handle's own device arrays; the loops' table and the layers'
-// ranges and sums are on the host.  A fragment of the C ABI like capi_flow.hpp, included by capi_mesh.hpp, whose helpers (voxels_in,
-// FxStage, ScratchBuf, ctr_scan, cc_grid) it uses.
+// ranges and sums are on the host.  A fragment of the C ABI, included by capi_mesh.hpp; uses capi_mesh_util.hpp.
 struct fhip_outlines {
     int device = 0;
     uint32_t N = 0, k0 = 0, conn = 0;
@@ -139,11 +138,10 @@ fhip_status fhip_outlines_vertices(const void* h, uint64_t first, uint64_t count
     const fhip_outlines* const o = (const fhip_outlines*)h;
     if (!o) return FHIP_ERR_BAD_TAPE;
     if (first > o->n_vertices || count > o->n_vertices - first) return FHIP_ERR_UNSUPPORTED;
-    if (count == 0) return FHIP_OK;
-    (void)hipSetDevice(o->device);
-    if (xy && hipMemcpy(xy, o->d_xy + first, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) return FHIP_ERR_HIP;
-    if (next && hipMemcpy(next, o->d_next + first, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) return FHIP_ERR_HIP;
-    if (loop_of && hipMemcpy(loop_of, o->d_loop + first, (size_t)count * 4, hipMemcpyDeviceToHost) != hipSuccess) return FHIP_ERR_HIP;
+    const size_t bytes = (size_t)count * 4;
+    if (xy && handle_to_host(o->device, xy, o->d_xy + first, bytes)) return FHIP_ERR_HIP;
+    if (next && handle_to_host(o->device, next, o->d_next + first, bytes)) return FHIP_ERR_HIP;
+    if (loop_of && handle_to_host(o->device, loop_of, o->d_loop + first, bytes)) return FHIP_ERR_HIP;
     return FHIP_OK;
 }
 fhip_status fhip_outlines_loops(const void* h, uint64_t first, uint64_t count, uint32_t* leader, uint32_t* n_vertices, int64_t* area2, uint64_t* perimeter, uint16_t* lo,
@@ -161,7 +159,7 @@ fhip_status fhip_outlines_loops(const void* h, uint64_t first, uint64_t count, u
     if (hi) memcpy(hi, o->loop_hi.data() + 2 * f, 2 * c * 2);
     return FHIP_OK;
 }
-const uint16_t* fhip_outlines_xy_dev(const void* h) { const fhip_outlines* const o = (const fhip_outlines*)h; return o ? (const uint16_t*)o->d_xy : nullptr; }
-const uint32_t* fhip_outlines_next_dev(const void* h) { const fhip_outlines* const o = (const fhip_outlines*)h; return o ? o->d_next : nullptr; }
-const uint32_t* fhip_outlines_loop_dev(const void* h) { const fhip_outlines* const o = (const fhip_outlines*)h; return o ? o->d_loop : nullptr; }
+const uint16_t* fhip_outlines_xy_dev(const void* h) { return (const uint16_t*)HANDLE_GET(fhip_outlines, h, d_xy); }
+const uint32_t* fhip_outlines_next_dev(const void* h) { return HANDLE_GET(fhip_outlines, h, d_next); }
+const uint32_t* fhip_outlines_loop_dev(const void* h) { return HANDLE_GET(fhip_outlines, h, d_loop); }
 void fhip_outlines_free(void* h) { delete (fhip_outlines*)h; }

@@ -1,8 +1,8 @@
 // ---- the local thickness of a distance field ---------------------------------------------------------------------------------------------------
 // fhip_distance_thickness (fidget_hip.h): the passes of thick.hip on a finished fhip_distance, all on the context's stream; the host waits
 // once, at the end, for the summary.  The result is a fhip_distance again - its field is T - so fhip_distance_slices, _threshold, _dev
-// and _free serve it as they are.  A fragment of the C ABI like capi_edt.hpp, after which capi_mesh.hpp includes it and whose helpers
-// (FxStage, ScratchBuf, mesh_now, cc_grid, distance_threshold) it uses.  FHIP_MESH_TIMES: the passes' wall times on stderr.
+// and _free serve it as they are.  A fragment of the C ABI, included by capi_mesh.hpp after capi_edt.hpp, whose
+// fhip_distance and distance_threshold it uses; uses capi_mesh_util.hpp.  FHIP_MESH_TIMES: the passes' wall times on stderr.
 fhip_status fhip_distance_thickness(fhip_ctx* ctx, const void* distance, void** out) {
     if (out) *out = nullptr;
     const fhip_distance* const d = (const fhip_distance*)distance;
@@ -14,17 +14,7 @@ fhip_status fhip_distance_thickness(fhip_ctx* ctx, const void* distance, void** 
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     const uint32_t depth = d->depth;
-    const bool times = getenv("FHIP_MESH_TIMES") != nullptr;
-    double t_last = times ? mesh_now() : 0;
-    auto mark = [&](const char* what) -> hipError_t {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess || !times) return e;
-        const hipError_t es = hipStreamSynchronize(st);
-        const double t = mesh_now();
-        if (what) fprintf(stderr, "fhip thickness depth %u: %-16s %.6f s\n", depth, what, t - t_last);
-        t_last = mesh_now();
-        return es;
-    };
+    PassTimes times(st, "fhip thickness depth %u", depth);
     std::unique_ptr<fhip_distance> R(new fhip_distance());
     R->depth = depth; R->complement = d->complement; R->device = ctx->device; R->thickness = 1;
     const uint32_t N = 4u << depth;
@@ -42,31 +32,31 @@ fhip_status fhip_distance_thickness(fhip_ctx* ctx, const void* distance, void** 
     HIP_TRY(ctx, hipMemsetAsync(tables.p, 0, table_bytes, st));
     HIP_TRY(ctx, hipMemsetAsync(d_sum, 0, 32, st));
     HIP_TRY(ctx, hipMemsetAsync(R->d_field, 0, (size_t)n_voxels * 4, st));
-    HIP_TRY(ctx, mark("allocate, zero"));
+    HIP_TRY(ctx, times.mark("allocate, zero"));
     const uint64_t pairs = ((uint64_t)A + 1) * (A + 1);
     hipLaunchKernelGGL(fhm::k_lt_shells, cc_grid(pairs), dim3(256), 0, st, vmax, A, (uint32_t*)tables.p);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fhm::k_lt_need, dim3(3), dim3(1024), 0, st, vmax, (uint32_t*)tables.p);
-    HIP_TRY(ctx, mark("need"));
+    HIP_TRY(ctx, times.mark("need"));
     hipLaunchKernelGGL(fhm::k_lt_ridge, cc_grid(n_voxels), dim3(256), 0, st, (const uint32_t*)d->d_field, depth, (const uint32_t*)tables.p, vmax, (uint64_t*)keep.p,
                        (unsigned long long*)(d_sum + 3));
-    HIP_TRY(ctx, mark("k_lt_ridge"));
+    HIP_TRY(ctx, times.mark("k_lt_ridge"));
     // a large ball's rows in parts, so that the few words that hold such centres occupy more than a wave each
     const uint32_t side = 2 * A + 1;
     const uint32_t split = std::min<uint32_t>(std::max<uint32_t>(side * side / 512, 1), fhm::FH_LT_PAINT_SPLIT);
     const uint32_t paint_blocks = (uint32_t)std::min<uint64_t>((n_keep + 3) / 4, fhm::FH_LT_PAINT_BLOCKS);
     hipLaunchKernelGGL(fhm::k_lt_paint, dim3(paint_blocks, split), dim3(256), 0, st, (const uint32_t*)d->d_field, (const uint64_t*)keep.p, depth, R->d_field);
-    HIP_TRY(ctx, mark("k_lt_paint"));
+    HIP_TRY(ctx, times.mark("k_lt_paint"));
     hipLaunchKernelGGL(fhm::k_lt_reduce, dim3(red_blocks), dim3(256), 0, st, (const uint32_t*)R->d_field, depth, d_parts);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fhm::k_lt_reduce_sum, dim3(1), dim3(256), 0, st, (const uint64_t*)d_parts, red_blocks, d_sum);
-    HIP_TRY(ctx, mark("k_lt_reduce"));
+    HIP_TRY(ctx, times.mark("k_lt_reduce"));
     uint64_t sum[4] = {0, 0, 0, 0};
     HIP_TRY(ctx, hipMemcpyAsync(sum, d_sum, 32, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
-    if (times) {          // (otherwise they go with the scope)
+    if (times.on) {          // (otherwise they go with the scope)
         tables.release(); keep.release(); parts.release();
-        HIP_TRY(ctx, mark("release"));
+        HIP_TRY(ctx, times.mark("release"));
         fprintf(stderr, "fhip thickness depth %u: %llu centres, %llu balls painted, largest squared radius %llu\n", depth, (unsigned long long)(n_voxels - d->n_fg),
                 (unsigned long long)sum[3], (unsigned long long)(sum[0] >> 32));
     }

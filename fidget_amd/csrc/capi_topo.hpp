@@ -7,8 +7,8 @@
 // vertex id, a flag and a rank, per triangle a parent, a flag and a rank, the scans' block totals - is carved from ctx->mesh_leaves as
 // capi_trivox.hpp does: it stays with the context and fhip_ctx_trim gives it back.  The results - the vertices, the triangles, a shell per
 // triangle and a byte per corner, from which fhip_topology_edges makes its lists - are the handle's own device arrays; the shells'
-// columns and the counts are on the host.  A fragment of the C ABI like capi_trivox.hpp, included by capi_mesh.hpp, whose helpers
-// (ScratchBuf, ctr_scan, cc_grid) it uses.  FHIP_MESH_TIMES: the passes' times between events on the stream, on stderr.
+// columns and the counts are on the host.  A fragment of the C ABI, included by capi_mesh.hpp; uses capi_mesh_util.hpp.
+// FHIP_MESH_TIMES: the passes' times between events on the stream, on stderr.
 struct fhip_topology {
     int device = 0;
     uint64_t counts[16] = {};
@@ -76,7 +76,7 @@ fhip_status fhip_triangles_topology(fhip_ctx* ctx, const float* vertices, uint64
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     TopoTimes tt{getenv("FHIP_MESH_TIMES") != nullptr, st, {}};
-    auto mark = [&](const char* what) -> hipError_t {
+    const auto mark = [&tt](const char* what) -> hipError_t {          // a launch's error, or the event after the pass
         const hipError_t e = hipGetLastError();
         return e != hipSuccess ? e : tt.mark(what);
     };
@@ -269,19 +269,26 @@ void fhip_topology_counts(const void* h, uint64_t out[16]) {
     const fhip_topology* const t = (const fhip_topology*)h;
     for (int k = 0; k < 16; k++) out[k] = t ? t->counts[k] : 0;
 }
-static fhip_status topology_to_host(const fhip_topology* t, void* dst, const void* d_src, size_t bytes) {
-    if (!t || (bytes && !dst)) return FHIP_ERR_BAD_TAPE;
-    if (!bytes || !d_src) return FHIP_OK;
-    (void)hipSetDevice(t->device);
-    return hipMemcpy(dst, d_src, bytes, hipMemcpyDeviceToHost) == hipSuccess ? FHIP_OK : FHIP_ERR_HIP;
+uint64_t fhip_topology_vertex_rows(const void* h) { return HANDLE_GET(fhip_topology, h, n_vertex_rows); }
+// the arrays to the host: refused without a handle, and without a destination for rows that the handle has; an array it has not is no rows
+fhip_status fhip_topology_vertices(const void* h, float* out) {
+    const fhip_topology* const t = (const fhip_topology*)h;
+    if (!t || (t->n_vertex_rows && !out)) return FHIP_ERR_BAD_TAPE;
+    return t->d_vertices ? handle_to_host(t->device, out, t->d_vertices, (size_t)t->n_vertex_rows * 12) : FHIP_OK;
 }
-uint64_t fhip_topology_vertex_rows(const void* h) { const fhip_topology* const t = (const fhip_topology*)h; return t ? t->n_vertex_rows : 0; }
-fhip_status fhip_topology_vertices(const void* h, float* out) { const fhip_topology* const t = (const fhip_topology*)h; return topology_to_host(t, out, t ? t->d_vertices : nullptr, t ? (size_t)t->n_vertex_rows * 12 : 0); }
-fhip_status fhip_topology_triangles(const void* h, uint64_t* out) { const fhip_topology* const t = (const fhip_topology*)h; return topology_to_host(t, out, t ? t->d_triangles : nullptr, t && t->d_triangles ? (size_t)t->counts[TOPO_TRIANGLES] * 24 : 0); }
-fhip_status fhip_topology_triangle_shells(const void* h, uint32_t* out) { const fhip_topology* const t = (const fhip_topology*)h; return topology_to_host(t, out, t ? t->d_shell : nullptr, t && t->d_shell ? (size_t)t->counts[TOPO_TRIANGLES] * 4 : 0); }
-const float* fhip_topology_vertices_dev(const void* h) { const fhip_topology* const t = (const fhip_topology*)h; return t ? t->d_vertices : nullptr; }
-const uint64_t* fhip_topology_triangles_dev(const void* h) { const fhip_topology* const t = (const fhip_topology*)h; return t ? t->d_triangles : nullptr; }
-const uint32_t* fhip_topology_triangle_shells_dev(const void* h) { const fhip_topology* const t = (const fhip_topology*)h; return t ? t->d_shell : nullptr; }
+fhip_status fhip_topology_triangles(const void* h, uint64_t* out) {
+    const fhip_topology* const t = (const fhip_topology*)h;
+    if (!t || (t->d_triangles && t->counts[TOPO_TRIANGLES] && !out)) return FHIP_ERR_BAD_TAPE;
+    return t->d_triangles ? handle_to_host(t->device, out, t->d_triangles, (size_t)t->counts[TOPO_TRIANGLES] * 24) : FHIP_OK;
+}
+fhip_status fhip_topology_triangle_shells(const void* h, uint32_t* out) {
+    const fhip_topology* const t = (const fhip_topology*)h;
+    if (!t || (t->d_shell && t->counts[TOPO_TRIANGLES] && !out)) return FHIP_ERR_BAD_TAPE;
+    return t->d_shell ? handle_to_host(t->device, out, t->d_shell, (size_t)t->counts[TOPO_TRIANGLES] * 4) : FHIP_OK;
+}
+const float* fhip_topology_vertices_dev(const void* h) { return HANDLE_GET(fhip_topology, h, d_vertices); }
+const uint64_t* fhip_topology_triangles_dev(const void* h) { return HANDLE_GET(fhip_topology, h, d_triangles); }
+const uint32_t* fhip_topology_triangle_shells_dev(const void* h) { return HANDLE_GET(fhip_topology, h, d_shell); }
 fhip_status fhip_topology_shells(const void* h, uint64_t* triangles, uint32_t* first, uint64_t* unbalanced, float* lo, float* hi, double* volume6, double* area2) {
     const fhip_topology* const t = (const fhip_topology*)h;
     if (!t) return FHIP_ERR_BAD_TAPE;

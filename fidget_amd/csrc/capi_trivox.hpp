@@ -9,9 +9,8 @@
 // context after the call, and fhip_ctx_trim (or a frame that needs the room, or fhip_ctx_destroy) gives it back.  Neither use needs
 // its contents after its own call.  Why it is kept: allocating and releasing some gigabytes in every call of a row of calls took,
 // in some runs, thirty times what the passes take (profiles/mesh_voxels/README.md).  A host `out` goes through the staging buffer
-// io_b, a bitmap's size, as the other bitmap calls' results do; like theirs it stays until fhip_ctx_destroy.  A fragment of the C ABI
-// like capi_flow.hpp, included by capi_mesh.hpp, whose helpers (FxStage, ScratchBuf, ctr_scan, mesh_now) it uses.  FHIP_MESH_TIMES: the
-// passes' wall times on stderr.
+// io_b, a bitmap's size, as the other bitmap calls' results do; like theirs it stays until fhip_ctx_destroy.  A fragment of the C ABI,
+// included by capi_mesh.hpp; uses capi_mesh_util.hpp.  FHIP_MESH_TIMES: the passes' wall times on stderr.
 fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t n_vertices, const uint64_t* triangles, uint64_t n_triangles, int on_device,
                                   const double* mesh_to_world, uint32_t depth, uint64_t* out, int out_on_device, uint64_t info[8]) {
     if (!ctx || !out || !info) return fail(ctx, FHIP_ERR_BAD_TAPE, "fhip_triangles_voxels: context, result and info");
@@ -24,16 +23,7 @@ fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t
     if (out_on_device && ((uintptr_t)out & 7u)) return fail(ctx, FHIP_ERR_UNSUPPORTED, "a voxel bitmap on the device must be 8-byte aligned");
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
-    const bool times = getenv("FHIP_MESH_TIMES") != nullptr;
-    double t_last = times ? mesh_now() : 0;
-    auto mark = [&](const char* what) -> hipError_t {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess || !times) return e;
-        const hipError_t es = hipStreamSynchronize(st);
-        fprintf(stderr, "fhip mesh to voxels depth %u: %-16s %.6f s\n", depth, what, mesh_now() - t_last);
-        t_last = mesh_now();
-        return es;
-    };
+    PassTimes times(st, "fhip mesh to voxels depth %u", depth);
     const uint32_t T = (uint32_t)n_triangles, B = 1u << depth;
     const uint64_t n_words = fhvox::n_words(depth), n_exit = fhtv::exit_words(depth);
     FxStage stage{ctx, out_on_device, {}};
@@ -63,7 +53,7 @@ fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t
     uint64_t* const d_counters = d_exit + n_exit;
     HIP_TRY(ctx, hipMemsetAsync(d_out, 0, (size_t)n_words * 8, st));
     HIP_TRY(ctx, hipMemsetAsync(d_exit, 0, (size_t)(n_exit + n_counters) * 8, st));
-    HIP_TRY(ctx, mark("clear"));
+    HIP_TRY(ctx, times.mark("clear"));
     uint64_t W = 0;
     if (T) {
         fhtv::Tri* const records = (fhtv::Tri*)((char*)ctx->mesh_leaves.p + head_bytes);
@@ -77,12 +67,12 @@ fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t
         if (mesh_to_world) { memcpy(M.m, mesh_to_world, sizeof(M.m)); M.present = 1; }
         hipLaunchKernelGGL(fhm::k_tv_setup, dim3((unsigned)(((uint64_t)T + 255) / 256)), dim3(256), 0, st, d_vertices, n_vertices, d_triangles, T, M, depth,
                            records, columns, d_counters);
-        HIP_TRY(ctx, mark("k_tv_setup"));
+        HIP_TRY(ctx, times.mark("k_tv_setup"));
         HIP_TRY(ctx, ctr_scan(st, columns, T, low, scan_tmp));
         hipLaunchKernelGGL(fhm::k_tv_wraps, dim3((unsigned)(((uint64_t)T + 255) / 256)), dim3(256), 0, st, (const uint32_t*)low, T, wrapped);
         HIP_TRY(ctx, hipGetLastError());
         HIP_TRY(ctx, ctr_scan(st, (const uint32_t*)wrapped, T, high, scan_tmp));          // (the same block totals' room: the stream keeps the two in order)
-        HIP_TRY(ctx, mark("scans"));
+        HIP_TRY(ctx, times.mark("scans"));
         uint32_t w_low = 0, w_high = 0;
         HIP_TRY(ctx, hipMemcpyAsync(&w_low, low + T, 4, hipMemcpyDeviceToHost, st));
         HIP_TRY(ctx, hipMemcpyAsync(&w_high, high + T, 4, hipMemcpyDeviceToHost, st));
@@ -96,12 +86,12 @@ fhip_status fhip_triangles_voxels(fhip_ctx* ctx, const float* vertices, uint64_t
             const uint32_t nb = (uint32_t)(((W + per_wave - 1) / per_wave + 3) / 4);
             hipLaunchKernelGGL(fhm::k_tv_cross, dim3(nb), dim3(256), 0, st, (const fhtv::Tri*)records, (const uint32_t*)low, (const uint32_t*)high, T, W, per_wave, depth,
                                d_out, d_exit, d_counters);
-            HIP_TRY(ctx, mark("k_tv_cross"));
+            HIP_TRY(ctx, times.mark("k_tv_cross"));
         }
         // (an empty bitmap is its own prefix XOR, but the open rows of crossings that were all clipped are still counted)
         const uint64_t waves = depth < 6 ? (n_words + 63) / 64 : (uint64_t)B * B;
         hipLaunchKernelGGL(fhm::k_tv_fill, dim3((unsigned)((waves + 3) / 4)), dim3(256), 0, st, d_out, (const uint64_t*)d_exit, depth, d_counters);
-        HIP_TRY(ctx, mark("k_tv_fill"));
+        HIP_TRY(ctx, times.mark("k_tv_fill"));
     }
     std::vector<uint64_t> rows(n_counters);
     HIP_TRY(ctx, hipMemcpyAsync(rows.data(), d_counters, n_counters * 8, hipMemcpyDeviceToHost, st));

@@ -1,28 +1,16 @@
 // ---- the boundary mesh of a voxel bitmap ------------------------------------------------------------------------------------------------------
 // fhip_voxels_surface and fhip_voxels_mesh (fidget_hip.h): the counting pass of vmesh.hip and its sums; for the mesh, the two prefix sums
 // (ctr_scan) and the two emitting passes, all on the context's stream.  The host waits once for the totals - they decide an overflow and
-// size the arrays - and once at the end, for the arrays on their way to the host.  A fragment of the C ABI like capi_edt.hpp, included by
-// capi_mesh.hpp, whose helpers (voxels_in, FxStage, ScratchBuf, ctr_scan, mesh_to_host, mesh_now) it uses.  FHIP_MESH_TIMES: the passes'
-// wall times on stderr.
+// size the arrays - and once at the end, for the arrays on their way to the host.  A fragment of the C ABI, included by
+// capi_mesh.hpp; uses capi_mesh_util.hpp.  FHIP_MESH_TIMES: the passes' wall times on stderr.
 static fhip_status vmesh_run(fhip_ctx* ctx, const uint64_t* bricks, uint32_t depth, int on_device, uint64_t sums[fhm::FH_VM_SUMS], fhip_mesh** mesh) {
-    if (depth > fhvox::MAX_DEPTH) return fail(ctx, FHIP_ERR_UNSUPPORTED, "voxel depth above 10");
-    if (!bricks) return fail(ctx, FHIP_ERR_UNSUPPORTED, "the boundary of a voxel bitmap: the bitmap");
+    { const fhip_status s = bitmap_args(ctx, "the boundary of a voxel bitmap: the bitmap", depth, bricks); if (s) return s; }
     (void)hipSetDevice(ctx->device);
     hipStream_t st = ctx->stream;
     FxStage stage{ctx, on_device, {}};
     const uint64_t* d_bricks = nullptr;
     { const fhip_status s = voxels_in(ctx, stage, bricks, depth, d_bricks); if (s) return s; }
-    const bool times = getenv("FHIP_MESH_TIMES") != nullptr;
-    double t_last = times ? mesh_now() : 0;
-    auto mark = [&](const char* what) -> hipError_t {
-        const hipError_t e = hipGetLastError();
-        if (e != hipSuccess || !times) return e;
-        const hipError_t es = hipStreamSynchronize(st);
-        const double t = mesh_now();
-        if (what) fprintf(stderr, "fhip voxel %s depth %u: %-16s %.6f s\n", mesh ? "mesh" : "surface", depth, what, t - t_last);
-        t_last = mesh_now();
-        return es;
-    };
+    PassTimes times(st, "fhip voxel %s depth %u", mesh ? "mesh" : "surface", depth);
     const uint64_t n_words = fhvox::n_words(depth);
     const uint32_t n_corner = (uint32_t)fhvm::n_corner_bricks(depth);
     const uint32_t count_blocks = std::min((n_corner + 255) / 256, fhm::FH_VM_COUNT_BLOCKS);
@@ -40,11 +28,11 @@ static fhip_status vmesh_run(fhip_ctx* ctx, const uint64_t* bricks, uint32_t dep
         face_count = (uint32_t*)face_buf.p; face_base = face_count + n_words;
         vertex_count = (uint32_t*)corner_buf.p; vertex_base = vertex_count + n_corner;
     }
-    HIP_TRY(ctx, mark("allocate"));
+    HIP_TRY(ctx, times.mark("allocate"));
     hipLaunchKernelGGL(fhm::k_vm_count, dim3(count_blocks), dim3(256), 0, st, d_bricks, depth, face_count, (uint64_t*)flag_buf.p, vertex_count, d_parts);
     HIP_TRY(ctx, hipGetLastError());
     hipLaunchKernelGGL(fhm::k_vm_sum, dim3(fhm::FH_VM_SUMS), dim3(256), 0, st, (const uint64_t*)d_parts, count_blocks, d_sums);
-    HIP_TRY(ctx, mark("k_vm_count"));
+    HIP_TRY(ctx, times.mark("k_vm_count"));
     HIP_TRY(ctx, hipMemcpyAsync(sums, d_sums, fhm::FH_VM_SUMS * 8, hipMemcpyDeviceToHost, st));
     HIP_TRY(ctx, hipStreamSynchronize(st));
     if (!mesh) return FHIP_OK;
@@ -56,21 +44,21 @@ static fhip_status vmesh_run(fhip_ctx* ctx, const uint64_t* bricks, uint32_t dep
     if (n_faces == 0) { *mesh = M.release(); return FHIP_OK; }
     HIP_TRY(ctx, ctr_scan(st, face_count, (uint32_t)n_words, face_base, (uint32_t*)scan_tmp.p));
     HIP_TRY(ctx, ctr_scan(st, vertex_count, n_corner, vertex_base, (uint32_t*)scan_tmp.p));          // (the same block totals' room: the stream keeps the two in order)
-    HIP_TRY(ctx, mark("scans"));
+    HIP_TRY(ctx, times.mark("scans"));
     HIP_TRY(ctx, hipMalloc((void**)&M->d_vertices, (size_t)n_verts * sizeof(fhmesh::V3)));
     HIP_TRY(ctx, hipMalloc((void**)&M->d_triangles, (size_t)n_faces * 48));
-    HIP_TRY(ctx, mark("allocate arrays"));
+    HIP_TRY(ctx, times.mark("allocate arrays"));
     hipLaunchKernelGGL(fhm::k_vm_vertices, dim3((n_corner + fhm::FH_VM_PER_BLOCK - 1) / fhm::FH_VM_PER_BLOCK), dim3(256), 0, st, (const uint64_t*)flag_buf.p,
                        (const uint32_t*)vertex_base, depth, M->d_vertices);
-    HIP_TRY(ctx, mark("k_vm_vertices"));
+    HIP_TRY(ctx, times.mark("k_vm_vertices"));
     hipLaunchKernelGGL(fhm::k_vm_faces, dim3((unsigned)((n_words + fhm::FH_VM_PER_BLOCK - 1) / fhm::FH_VM_PER_BLOCK)), dim3(256), 0, st, d_bricks, depth,
                        (const uint32_t*)face_base, (const uint64_t*)flag_buf.p, (const uint32_t*)vertex_base, M->d_triangles);
-    HIP_TRY(ctx, mark("k_vm_faces"));
+    HIP_TRY(ctx, times.mark("k_vm_faces"));
     M->vertices.resize((size_t)n_verts);
     M->triangles.resize((size_t)(2 * n_faces));
     { const fhip_status s = mesh_to_host(ctx, M->vertices.data(), M->d_vertices, (size_t)n_verts * sizeof(fhmesh::V3)); if (s) return s; }
     { const fhip_status s = mesh_to_host(ctx, M->triangles.data(), M->d_triangles, (size_t)n_faces * 48); if (s) return s; }
-    HIP_TRY(ctx, mark("to the host"));
+    HIP_TRY(ctx, times.mark("to the host"));
     *mesh = M.release();
     return FHIP_OK;
 }

@@ -1,6 +1,7 @@
 // The index arithmetic of the voxel bitmap (fhip_shape_voxels, include/fidget_hip.h): where the cell with a given octree path lies in the
 // array of bricks, and how the words of a Full cell are dealt out to the lanes of k_vox_full.  No HIP and no memory access: compiled for
-// the device by mesh.hip and for the host by tests/host_build/mesh_vox_host.cpp.
+// the device by mesh.hip and for the host by tests/host_build/mesh_vox_host.cpp - but for the device helper at the end (wave_sum), which the
+// kernels of trivox.hip and topo.hip share and the host build does not see.
 //
 // The bitmap of depth `depth` is B^3 words, B = 1 << depth: word (bz * B + by) * B + bx is the brick of the voxels
 // (4 bx + lx, 4 by + ly, 4 bz + lz), bit lx + 4 ly + 16 lz.  A cell of level l covers r^3 bricks, r = B >> l, from brick (ox r, oy r, oz r)
@@ -62,4 +63,12 @@ FHV_HD uint64_t slot_word(const FullSlots& S, uint32_t depth, uint64_t cell, uin
     const uint32_t ry = row & (S.r - 1), rz = row >> S.lg_r;
     return cell + word_index(depth, p * S.vec, ry, rz);
 }
+#if defined(__HIPCC__)
+// the sum of v over the 64 lanes of a wave, in every lane
+template <typename T> __device__ __forceinline__ T wave_sum(T v) {
+#pragma unroll
+    for (uint32_t step = 32; step > 0; step >>= 1) v += __shfl_xor(v, step, 64);
+    return v;
+}
+#endif
 }  // namespace fhvox

@@ -54,11 +54,6 @@ __device__ __forceinline__ void mt_count_if(uint64_t* counters, uint32_t which, 
     const uint32_t n = (uint32_t)__popcll(__ballot(mine));
     if ((threadIdx.x & 63) == 0) mt_count(counters, which, n);
 }
-__device__ __forceinline__ uint32_t mt_wave_sum(uint32_t v) {
-#pragma unroll
-    for (uint32_t step = 32; step > 0; step >>= 1) v += __shfl_xor(v, step, 64);
-    return v;
-}
 
 __global__ void __launch_bounds__(256) k_mt_check(const float* __restrict__ vertices, uint64_t n_vertices, const uint64_t* __restrict__ triangles, uint32_t n_triangles,
                                                   uint64_t* __restrict__ counters) {
@@ -113,7 +108,7 @@ __global__ void __launch_bounds__(256) k_mt_ids(const uint64_t* __restrict__ tri
 // ... counted four at a time: n_words words of four bytes, the bytes past the last vertex zero
 __global__ void __launch_bounds__(256) k_mt_used(const uint32_t* __restrict__ used, uint32_t n_words, uint64_t* __restrict__ counters) {
     const uint64_t w = (uint64_t)blockIdx.x * 256 + threadIdx.x;
-    const uint32_t n = mt_wave_sum(w < n_words ? (uint32_t)__popc(used[w] & 0x01010101u) : 0u);
+    const uint32_t n = fhvox::wave_sum(w < n_words ? (uint32_t)__popc(used[w] & 0x01010101u) : 0u);
     if ((threadIdx.x & 63) == 0) mt_count(counters, FH_MT_USED, n);
 }
 
@@ -167,7 +162,7 @@ __global__ void __launch_bounds__(256) k_mt_link(const uint64_t* __restrict__ tr
     }
 #pragma unroll
     for (uint32_t i = 0; i <= fhtopo::N_KINDS; i++) {
-        const uint32_t sum = mt_wave_sum(n[i]);
+        const uint32_t sum = fhvox::wave_sum(n[i]);
         if ((threadIdx.x & 63) == 0) mt_count(counters, FH_MT_EDGES + i, sum);
     }
 }
@@ -207,11 +202,6 @@ __device__ __forceinline__ uint32_t mt_wave_max(uint32_t v) {
     for (uint32_t step = 32; step > 0; step >>= 1) { const uint32_t o = __shfl_xor(v, step, 64); v = o > v ? o : v; }
     return v;
 }
-__device__ __forceinline__ double mt_wave_sum(double v) {
-#pragma unroll
-    for (uint32_t step = 32; step > 0; step >>= 1) v += __shfl_xor(v, step, 64);
-    return v;
-}
 // what a lane, and after mt_reduce a wave, holds of one shell
 struct MtPart {
     uint32_t n, unbalanced, lo[3], hi[3];
@@ -230,10 +220,10 @@ __device__ __forceinline__ void mt_add(MtPart& p, const MtPart& q) {
     p.v6 += q.v6; p.a2 += q.a2;
 }
 __device__ __forceinline__ MtPart mt_reduce(MtPart p) {          // over the wave; every lane gets the result
-    p.n = mt_wave_sum(p.n); p.unbalanced = mt_wave_sum(p.unbalanced);
+    p.n = fhvox::wave_sum(p.n); p.unbalanced = fhvox::wave_sum(p.unbalanced);
 #pragma unroll
     for (uint32_t a = 0; a < 3; a++) { p.lo[a] = mt_wave_min(p.lo[a]); p.hi[a] = mt_wave_max(p.hi[a]); }
-    p.v6 = mt_wave_sum(p.v6); p.a2 = mt_wave_sum(p.a2);
+    p.v6 = fhvox::wave_sum(p.v6); p.a2 = fhvox::wave_sum(p.a2);
     return p;
 }
 __device__ __forceinline__ void mt_send(const MtShellTable& T, uint32_t s, const MtPart& p) {

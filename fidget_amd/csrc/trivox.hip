@@ -35,11 +35,6 @@ struct FhTvTransform {
     uint32_t present;
 };
 
-__device__ __forceinline__ uint32_t tv_wave_sum(uint32_t v) {
-#pragma unroll
-    for (uint32_t step = 32; step > 0; step >>= 1) v += __shfl_xor(v, step, 64);
-    return v;
-}
 __device__ __forceinline__ void tv_count(uint64_t* counters, uint32_t which, uint32_t in_wave) {          // (called by one lane of the wave)
     const uint32_t wave = blockIdx.x * (blockDim.x >> 6) + (threadIdx.x >> 6);
     if (in_wave) atomicAdd((unsigned long long*)counters + (wave & (FH_TV_SLOTS - 1)) * FH_TV_COUNTERS + which, (unsigned long long)in_wave);
@@ -138,8 +133,8 @@ __global__ void __launch_bounds__(256) k_tv_cross(const fhtv::Tri* __restrict__ 
             }
         }
     }
-    crossings = tv_wave_sum(crossings);
-    clipped = tv_wave_sum(clipped);
+    crossings = fhvox::wave_sum(crossings);
+    clipped = fhvox::wave_sum(clipped);
     if (lane == 0) {
         tv_count(counters, FH_TV_CROSSINGS, crossings);
         tv_count(counters, FH_TV_CLIPPED, clipped);
@@ -178,8 +173,8 @@ __global__ void __launch_bounds__(256) k_tv_fill(uint64_t* __restrict__ bricks, 
         }
         if (more) carry ^= __shfl(acc, 63, 64);          // (only with width == 64: the row's last brick of this chunk is in lane 63)
     }
-    n_set = tv_wave_sum(n_set);
-    n_open = tv_wave_sum(n_open);
+    n_set = fhvox::wave_sum(n_set);
+    n_open = fhvox::wave_sum(n_open);
     if (lane == 0) {
         tv_count(counters, FH_TV_SET, n_set);
         tv_count(counters, FH_TV_OPEN, n_open);
