@@ -119,7 +119,9 @@ struct FrameBufs {
     hipEvent_t ev_done = nullptr;   // recorded when the last frame of this set has been queued completely
     bool ev_done_valid = false;
     std::shared_ptr<const fhip_tape> bound_hold;   // the bound tape of the last frame of this set (capi_bound.hpp), kept until that frame is over
+    CleanSig clean;                 // what the set's last 3D frame left z-buffer, normals and pyramid clean for (frame_plan.hpp clean buffer sets)
     void release_all() {
+        clean = CleanSig();
         DevBuf* bufs[] = {&state, &arena, &leaves, &leaf_table, &zbuf, &normals, &fp_lists, &mind, &squeue, &slots[0], &slots[1],
                           &leaves_b, &leaf_table_b, &fp_lists_b, &chw[0], &chw[1], &tvals, &topch, &chwr, &gscratch, &rare_scratch};
         for (DevBuf* b : bufs) b->release();

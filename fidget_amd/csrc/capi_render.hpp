@@ -405,11 +405,12 @@ static void launch_tiles_mono(fhip_ctx* ctx, const RenderSetup& R, FhRenderState
         });
 }
 // ... on the stream fs is at; fs moves only where the plan says so (LevelPlan::rest_on)
-static void launch_tiles(fhip_ctx* ctx, const RenderSetup& R, const LevelPlan& L, FhRenderState* dS, int level, bool is3d, FrameStreams& fs) {
+// (`head`: the level is the first of a frame's first tile chain and its set-up kernel carries the chain's head - tile_head below)
+static void launch_tiles(fhip_ctx* ctx, const RenderSetup& R, const LevelPlan& L, FhRenderState* dS, int level, bool is3d, FrameStreams& fs, const FhHead* head = nullptr) {
     if (L.path == LevelPlan::MONO) return launch_tiles_mono(ctx, R, dS, level, is3d, fs.on());
     const int gp = ctx->n_cu * 8;
     launch(ctx, fs.on(), FHIP_K_TILES, [&] {
-        if (is3d) FH_KLAUNCH(k_tsetup3d, dim3(gp), dim3(WAVE), 0, fs.on(), dS, level);
+        if (is3d) FH_KLAUNCH(k_tsetup3d, dim3(gp), dim3(WAVE), 0, fs.on(), dS, level, head ? *head : FhHead{});
         else FH_KLAUNCH(k_tsetup2d, dim3(gp), dim3(WAVE), 0, fs.on(), dS, level);
     });
     launch(ctx, fs.on(), FHIP_K_TILES, [&] {
@@ -568,11 +569,12 @@ static void slab_begin(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule&
     });
 }
 // The tile chain of slab k (the idx-th slab rendered) on the schedule's tile stream
-static fhip_status tile_step(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, int k, int idx) {
+static fhip_status tile_step(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, int k, int idx, const FhHead* head) {
     fs.cur = F.tiles;
     if (F.pipe && idx >= (int)F.NC) HIP_TRY(ctx, hipStreamWaitEvent(fs.on(), ctx->ev_leaves[idx - (int)F.NC], 0));  // context free again
-    slab_begin(ctx, R, F, dS, k, fs.on());
-    for (uint32_t l = R.S.pre_levels; l < R.S.P.n_levels; l++) launch_tiles(ctx, R, F.level[l], dS, (int)l, true, fs);
+    const FhHead* const mine = head && idx == 0 ? head : nullptr;      // (the frame's first tile chain: no launch for the slab's reset - in its set-up kernel)
+    if (!mine) slab_begin(ctx, R, F, dS, k, fs.on());
+    for (uint32_t l = R.S.pre_levels; l < R.S.P.n_levels; l++) launch_tiles(ctx, R, F.level[l], dS, (int)l, true, fs, l == R.S.pre_levels ? mine : nullptr);
     if (F.pipe) HIP_TRY(ctx, hipEventRecord(ctx->ev_tiles[idx], fs.on()));
     fs.cur = CALLER;
     return FHIP_OK;
@@ -663,13 +665,26 @@ static void normals_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedul
 }
 // The coarse levels of every slab in one go, then what follows them - the flags of the parked parents, the frame mark, the fork of the slab
 // contexts - and the edges to the streams the slabs run on; leaves fs on the caller's stream
-static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS) {
-    const uint32_t pre = R.S.pre_levels;
-    FhFork fork{};
+// What follows the root push of a frame of ONE coarse level whose leaf stage goes by the list - the flags of the parked parents, the frame
+// mark, the fork of the slab contexts - and the first slab's reset (no table to clear in such a frame) were two launches at the head of the
+// tile chain: both are the work of the chain's first kernel now, the set-up of level 1 (kernels.hip FhHead).  A frame of two coarse levels
+// keeps its launches: its frames are bound by level 1 and the leaf kernels, not by the host's launch count, and level 1's own flags launch stays either way.
+// What makes the head see the push's final counts: the tile chain's stream waits for the root level's - ev_l0 (hop to `fork_on`) where the
+// chain runs on the stream the fork went to, ev_fork (fork_to_side) where it does not; on one stream, the order of the launches.
+static FhHead tile_head(const fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F) {
+    FhHead h{};
+    FhFork& fork = h.fork;
     fork.n = F.NC; fork.mark = F.coarse ? 1u : 0u;
     fork.leaves = (FhLeaf*)ctx->leaves_b.p; fork.leaf_table = (FhLeafRef*)ctx->leaf_table_b.p; fork.fp_lists = (uint32_t*)ctx->fp_lists_b.p;
     fork.leaf_cap = (size_t)R.S.leaf_cap; fork.n_footprints = (size_t)R.n_footprints; fork.hit_words = R.hit_words;
-    const bool forked_here = F.coarse && R.zrep;
+    h.on = F.coarse && R.zrep && R.S.pre_levels == 1 && F.by_list && F.n_rendered > 0 && F.level[1].path != LevelPlan::MONO ? 1u : 0u;
+    h.slab = (uint32_t)F.slab_first; h.n_root_groups = R.groups_per_slab; h.depmask = R.col_depmask;
+    return h;
+}
+static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, const FhHead& head) {
+    const uint32_t pre = R.S.pre_levels;
+    const FhFork& fork = head.fork;
+    const bool forked_here = F.coarse && R.zrep;      // (by the flags launch below, or by the head of the tile chain)
     if (F.coarse) {
         launch_tiles(ctx, R, F.level[0], dS, 0, true, fs);
         if (pre > 1) {
@@ -680,7 +695,7 @@ static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const Fram
         }
         HIP_TRY(ctx, hop(fs, F.fork_on, pre > 1 ? ctx->ev_l1 : ctx->ev_l0));      // (level 1 did not go through fh_tiles_v64; or one coarse level whose tail goes to the side stream)
         // (the fork of a pipelined frame's slab contexts - or, with ONE context, the frame mark alone - in the same launch)
-        if (R.zrep) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 8 + 1), dim3(WAVE), 0, fs.on(), dS, (int)pre, R.col_depmask, 1, fork); });
+        if (R.zrep && !head.on) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 8 + 1), dim3(WAVE), 0, fs.on(), dS, (int)pre, R.col_depmask, 1, fork); });
         if (!F.pipe && !forked_here) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_mark_frame, dim3(1), dim3(1), 0, fs.on(), dS); });
     }
     if (F.pipe) {
@@ -695,14 +710,18 @@ static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const Fram
 }
 // The slabs, front to back (voxel.rs:252-261): tile chain, footprint lists, leaf kernel, normals - each on its role's stream, slab
 // contexts in turn
-static fhip_status render_slabs(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS0) {
+static fhip_status render_slabs(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS0, const FhHead& head) {
+    const FhHead* const hd = head.on ? &head : nullptr;
     auto slab_state = [&](int idx) { return dS0 + (F.pipe ? (uint32_t)idx % F.NC : 0u); };
-    for (int idx = 0; F.tiles_first && idx < F.n_rendered; idx++) { const fhip_status st = tile_step(ctx, R, F, fs, slab_state(idx), F.slab_first - idx, idx); if (st) return st; }
+    for (int idx = 0; F.tiles_first && idx < F.n_rendered; idx++) { const fhip_status st = tile_step(ctx, R, F, fs, slab_state(idx), F.slab_first - idx, idx, hd); if (st) return st; }
     for (int idx = 0; idx < F.n_rendered; idx++) {
-        if (ctx->is_cancelled()) return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
+        if (ctx->is_cancelled()) {
+            if (hd && idx == 0 && !F.tiles_first) ctx->forked = 0;      // (the fork rides on the first tile chain, which is not queued now: nobody reads the other slab contexts' states)
+            return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
+        }
         const int k = F.slab_first - idx;
         FhRenderState* const dS = slab_state(idx);
-        if (!F.tiles_first) { const fhip_status st = tile_step(ctx, R, F, fs, dS, k, idx); if (st) return st; }
+        if (!F.tiles_first) { const fhip_status st = tile_step(ctx, R, F, fs, dS, k, idx, hd); if (st) return st; }
         if (F.pipe) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.leaf], ctx->ev_tiles[idx], 0));
         if (F.aux_edge) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.lists], ctx->ev_tiles[idx], 0));
         classify_work(ctx, R, F, dS, fs.s[F.lists]);
@@ -754,6 +773,10 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
         in.frames_queued = ctx->extra_sets > 0 && ctx->others[0].ev_done_valid && hipEventQuery(ctx->others[0].ev_done) == hipErrorNotReady;
         (void)hipGetLastError();
     }
+    // (clean buffer sets, frame_plan.hpp: what the set's last frame left it clean for - taken off the set before anything of this frame can
+    // touch its buffers, prepare()'s growing them included: whatever ends this frame early leaves no record)
+    const CleanSig left_clean = ctx->clean;
+    ctx->clean = CleanSig();
     FH_SPAN(0);
     st = prepare(ctx, tape, facts, true, tiles.ts, part, R);
     if (st) return st;
@@ -772,23 +795,30 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     FhGeometryPixel* d_out = (FhGeometryPixel*)out;
     if (!out_is_device) { HIP_TRY(ctx, ctx->tmp_out.ensure(npix * sizeof(FhGeometryPixel))); d_out = (FhGeometryPixel*)ctx->tmp_out.p; }
     FhRenderState* const dS0 = (FhRenderState*)ctx->state.p;
-    const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u}, {ctx->mind.p, R.mind_words * 4, 0u}};
-    st = upload_frame(ctx, fs.on(), tape, R, clear3);
+    const CleanFrame kind = {out_is_device != 0, ctx->profiling};
+    CleanSig want_clean;
+    want_clean.valid = true; want_clean.pixels = npix; want_clean.mind_words = R.mind_words;
+    const bool is_clean = set_is_clean(left_clean, want_clean);      // (then the clears are skipped)
+    const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u}, {ctx->mind.p, R.mind_words * 4, 0u}}, no_clear[3] = {};
+    st = upload_frame(ctx, fs.on(), tape, R, is_clean ? no_clear : clear3);
     if (st) return st;
     FH_SPAN(2);
-    st = coarse_levels(ctx, R, F, fs, dS0);
+    const FhHead head = tile_head(ctx, R, F);
+    st = coarse_levels(ctx, R, F, fs, dS0, head);
     if (st) return st;
     FH_SPAN(3);
-    st = render_slabs(ctx, R, F, fs, dS0);
+    st = render_slabs(ctx, R, F, fs, dS0, head);
     if (st) return st;
     FH_SPAN(4);
     // finish: the image, the overflow latches and the pinned host words, on the caller's stream
-    launch(ctx, ctx->stream, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_finish3d, dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS0, d_out, std::max<uint32_t>(ctx->forked, 1u), (uint32_t*)ctx->sticky.p, ctx->host_flags); });
+    launch(ctx, ctx->stream, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_finish3d, dim3(ctx->n_cu * 16), dim3(WAVE), 0, ctx->stream, dS0, d_out, std::max<uint32_t>(ctx->forked, 1u), (uint32_t*)ctx->sticky.p, ctx->host_flags,
+                                                            leaves_set_clean(kind) ? 1u : 0u, (uint32_t)R.mind_words); });
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->launch_failed) { ctx->launch_failed = false; return FHIP_ERR_HIP; }   // (message in fhip_last_error)
     ctx->async_pending = out_is_device != 0;
     HIP_TRY(ctx, hipEventRecord(ctx->ev_done, ctx->stream));     // (a later pipelined frame that takes this set waits for it)
     ctx->ev_done_valid = true;
+    ctx->clean = set_left_by(kind, want_clean, true);
     if (ctx->opt.stats & 2) { g_spans.mark(5); g_spans.frame(); }
     if (!out_is_device) {
         HIP_TRY(ctx, hipMemcpyAsync(out, d_out, npix * sizeof(FhGeometryPixel), hipMemcpyDeviceToHost, ctx->stream));

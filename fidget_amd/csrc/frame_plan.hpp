@@ -490,3 +490,32 @@ static void plan_linked_prune(const TapeFacts& t, const PlanInputs& in, bool has
     R.prune2 = R.groups && has_links && linked_root_tape(t, in) && R.lds_prune2 <= FH_LDS_MAX &&
                R.roots.size() * 64 <= (size_t)2 * in.n_cu * FH_P2_WPB;      // (a root group = up to 64 root tiles)
 }
+
+// ---- clean buffer sets ---------------------------------------------------------------------------------------------------------
+// A 3D frame starts from a z-buffer, normals and a min-depth pyramid that are all zero.  k_finish3d, the last kernel to touch them, reads
+// every z-buffer word anyway and can hand the set back that way (`leave_clean`: it zeroes what the frame wrote); the next frame of the
+// set then clears nothing (k_frame_begin: 20 MB of stores at 1024^2, at the head of the frame's longest chain).  What a set was left clean
+// FOR is recorded with the set on the host: the pixels and the pyramid words k_finish3d went over.  A frame whose own numbers are the
+// record's skips the clears; any other frame clears everything, as a set's first frame does.  The record is dropped when a frame starts
+// and written when the frame has been queued to its end with a k_finish3d that cleans: a frame that was cancelled or failed half way, a
+// frame whose image goes to the host and a profiled frame leave none.
+struct CleanSig {
+    bool valid = false;
+    uint64_t pixels = 0, mind_words = 0;
+};
+// What kind of frame it is, for the rule
+struct CleanFrame {
+    bool out_is_device = true, profiling = false;
+};
+// Does this frame's k_finish3d clean behind itself (and, queued to its end, leave a record)?
+static bool leaves_set_clean(const CleanFrame& f) { return f.out_is_device && !f.profiling; }
+// May the frame skip its clears?  `left`: the set's record; `want`: what this frame needs cleared
+static bool set_is_clean(const CleanSig& left, const CleanSig& want) {
+    return left.valid && want.valid && left.pixels == want.pixels && left.mind_words == want.mind_words;
+}
+// The record a frame leaves: none unless it ran to its end (`queued_whole`) with a cleaning k_finish3d
+static CleanSig set_left_by(const CleanFrame& f, const CleanSig& want, bool queued_whole) {
+    CleanSig s = want;
+    s.valid = want.valid && queued_whole && leaves_set_clean(f);
+    return s;
+}

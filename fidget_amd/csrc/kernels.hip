@@ -574,6 +574,28 @@ FH_DEV void fork_state_body(FhRenderState* A, const FhFork& f) {
     A->arena_cap = lo + part;
 }
 __global__ void k_fork_state(FhRenderState* A, FhFork f) { fork_state_body(A, f); }
+// Does the tape read an input that changes along z (`depmask`)?  The whole wave scans it, 64 ops at a time; every lane gets the answer.
+// The value of FhGroup::stride for a queue entry with that tape: bit 31 = it reads none.
+FH_DEV uint32_t tape_flag(const FhRenderState* S, uint32_t off, uint32_t len, uint32_t depmask, int lane) {
+    const ctape_t tape = (ctape_t)(S->arena + off);
+    bool dep = false;
+    for (uint32_t k = lane; k < len; k += WAVE) {
+        const uint64_t w = tape[k];
+        if ((uint32_t)(w & 0xFFu) == FH_INPUT && ((depmask >> ((uint32_t)(w >> 32) & 31u)) & 1u)) dep = true;
+    }
+    return ballot(dep) != 0 ? 0u : 0x80000000u;
+}
+// Head of the first slab's tile chain in a frame of ONE coarse level (capi_render.hpp tile_head): what follows the root push - the frame
+// mark and the fork of the slab contexts - and the slab's reset, in the first block of the chain's first kernel (k_tsetup3d) instead of a
+// launch each; the other blocks take the slab's parents from the parking queue itself, not from the fields the first block sets.  And the
+// parked entries' column-invariance flags (k_tape_flags, parked = 1: a function of the entry's tape alone, read by this kernel alone): the
+// wave that takes an entry scans its tape against `depmask` itself.  (The root push that writes the entries has one wave per 64 of
+// them: the scans there would run one after the other on the frame's longest chain.)
+struct FhHead {
+    uint32_t on, slab, n_root_groups, depmask;
+    FhFork fork;
+};
+FH_DEV void reset_slab_body(FhRenderState* S, uint32_t i, uint32_t stride, uint32_t table_words, uint32_t slab, uint32_t n_root_groups, uint32_t reset_root_mind);
 
 // (fork.n != 0: the launch's last block forks the slab contexts - k_fork_state's work, which touches nothing this kernel reads or writes: the
 // state's arena bounds and pointers against the queue entries' flags - one launch less on the frame's coarse chain)
@@ -591,15 +613,8 @@ __global__ void __launch_bounds__(WAVE) k_tape_flags(FhRenderState* S, int level
         const uint32_t ns = parked ? S->scount[q] : S->count[level], nb = parked ? S->scount_big[q] : S->count_big[level];
         for (uint32_t gi = blockIdx.x; gi < ns + nb; gi += n_blocks) {
             FhGroup& g = base[gi < ns ? gi : cap - 1 - (gi - ns)];
-            const ctape_t tape = (ctape_t)(S->arena + g.tape.off);
-            const uint32_t len = uni(g.tape.len);
-            bool dep = false;
-            for (uint32_t k = lane; k < len; k += WAVE) {
-                const uint64_t w = tape[k];
-                if ((uint32_t)(w & 0xFFu) == FH_INPUT && ((depmask >> ((uint32_t)(w >> 32) & 31u)) & 1u)) dep = true;
-            }
-            const bool any = ballot(dep) != 0;
-            if (lane == 0) g.stride = any ? 0u : 0x80000000u;
+            const uint32_t flag = tape_flag(S, uni(g.tape.off), uni(g.tape.len), depmask, lane);
+            if (lane == 0) g.stride = flag;
         }
     }
 }
@@ -616,7 +631,7 @@ __global__ void __launch_bounds__(WAVE) k_tape_flags(FhRenderState* S, int level
 // but classifying and pruning only its share of the children, repeat the forward pass on SIMDs that would be idle and
 // shorten the prune.  Slots are independent for everything downstream (the push stage sees F small parents).
 template <bool IS3D>
-FH_DEV void tsetup_body(FhRenderState* S, int level) {
+FH_DEV void tsetup_body(FhRenderState* S, int level, const FhHead* head = nullptr) {
     const AS4 FhRender& P = *(const AS4 FhRender*)&S->P;
     const int lane = threadIdx.x;
     const uint32_t T = P.tiles[level];
@@ -633,7 +648,16 @@ FH_DEV void tsetup_body(FhRenderState* S, int level) {
     // (sharing a level-1 parent's children out over 2 / 4 / 8 slots was measured in round 3 - the kernel 412 -> 377 / 371 / 453 us, the frame
     // unchanged: the lockstep prune's cost is the ops SOME child keeps, and neighbours keep much the same - and taken out)
     const uint32_t G = TG;      // slots per parent (tape groups at level 0)
-    const uint32_t ns = min(S->count[level], S->slot_cap[0] / G), nb = min(S->count_big[level], S->slot_cap[1] / G);
+    // (head of a frame's first tile chain, FhHead: the level's queue IS the slab's parking queue - what reset_slab_body points queue[level] and
+    // its counts at; the first block does that for the kernels behind this one, after the mark and the fork, which read what the root push left)
+    const bool hd = IS3D && head && head->on;
+    const FhGroup* const queue = hd ? S->squeue + (size_t)head->slab * S->squeue_cap : S->queue[level];
+    const uint32_t cnt = hd ? S->scount[head->slab] : S->count[level], cnt_big = hd ? S->scount_big[head->slab] : S->count_big[level];
+    if (hd && blockIdx.x == 0) {
+        if (lane == 0 && head->fork.n) fork_state_body(S, head->fork);
+        reset_slab_body(S, (uint32_t)lane, WAVE, 0u, head->slab, head->n_root_groups, 0u);
+    }
+    const uint32_t ns = min(cnt, S->slot_cap[0] / G), nb = min(cnt_big, S->slot_cap[1] / G);
     if (blockIdx.x == 0 && lane == 0) {
         S->n_slots[0][level] = ns * G; S->n_slots[1][level] = nb * G;
         if (IS3D && nb && S->pre_levels > 0 && (uint32_t)level >= S->pre_levels) S->rare_seen = 1u;      // (a per-slab level's parent outside the small list)
@@ -644,7 +668,7 @@ FH_DEV void tsetup_body(FhRenderState* S, int level) {
     for (uint32_t wi = blockIdx.x; wi < (ns + nb) * parts; wi += gridDim.x) {
         const uint32_t gi = wi / parts, part = wi % parts;
         const bool big = gi >= ns;
-        const AS4 FhGroup& g = *(const AS4 FhGroup*)&S->queue[level][big ? S->qcap[level] - 1 - (gi - ns) : gi];
+        const AS4 FhGroup& g = *(const AS4 FhGroup*)&queue[big ? S->qcap[level] - 1 - (gi - ns) : gi];
         FhSlot* const slg = &S->slots[big ? 1 : 0][(big ? (gi - ns) : gi) * G];
         FhSlot& sl = *slg;
         // Column-invariant parents (k_tape_flags: the tape reads no input that changes along z, axis-aligned camera): the
@@ -653,11 +677,13 @@ FH_DEV void tsetup_body(FhRenderState* S, int level) {
         // layer is evaluated, the push stage hands its results to all the instances.  Occlusion is tested for the instance
         // nearest the camera.
         const uint32_t zrep = (IS3D && level > 0 && g.n > 1) ? g.n : 1u;
-        const bool inv = IS3D && level > 0 && ((g.stride >> 31) != 0 || zrep > 1);   // (a copy-carrying entry's tape is invariant: pruning only removes ops)
         if (IS3D && level > 0) {  // the whole parent may have been occluded since it was queued
             const uint32_t Tp = P.tiles[level - 1], ntxp = (P.width + Tp - 1) / Tp;
             if (S->mind[level - 1][(g.y / Tp) * ntxp + g.x / Tp] >= g.z + (zrep - 1) * Tp + Tp + 1) { if (lane < (int)G && part == 0) slg[lane].act = 0; continue; }
         }
+        // (a copy-carrying entry's tape is invariant: pruning only removes ops; any other entry: the flag k_tape_flags left in it - at the head
+        // of a frame's first tile chain nobody has, and the entry's own wave scans the tape here, as k_tape_flags' wave would have)
+        const bool inv = IS3D && level > 0 && (zrep > 1 || ((hd ? tape_flag(S, g.tape.off, g.tape.len, head->depmask, lane) : g.stride) >> 31) != 0);
         uint32_t nchild, cx, cy, cz;
         // (level 0 with a column-invariant root tape, capi_render.hpp root_zrep: the group's root tiles stand for g.x layers stacked on them)
         const uint32_t copies0 = (IS3D && level == 0 && g.x > 1) ? g.x : 1u;
@@ -701,7 +727,7 @@ FH_DEV void tsetup_body(FhRenderState* S, int level) {
     }
 }
 
-__global__ void __launch_bounds__(WAVE) k_tsetup3d(FhRenderState* S, int level) { tsetup_body<true>(S, level); }
+__global__ void __launch_bounds__(WAVE) k_tsetup3d(FhRenderState* S, int level, FhHead head) { tsetup_body<true>(S, level, &head); }
 // ... and of the 2D renderer when its tile sizes give 64 children per parent (the 128 / 16 hint): same slots, same
 // evaluate + prune kernels; children are the n x n sub-tiles at the slice height z
 __global__ void __launch_bounds__(WAVE) k_tsetup2d(FhRenderState* S, int level) { tsetup_body<false>(S, level); }
@@ -1736,9 +1762,15 @@ FH_DEV void latch_arena(const FhRenderState* S, uint32_t n_ctx, volatile uint32_
     if (peak > host_flags[1]) host_flags[1] = peak;
 }
 __global__ void k_latch_arena(const FhRenderState* S, uint32_t n_ctx, volatile uint32_t* host_flags) { latch_arena(S, n_ctx, host_flags); }
-__global__ void k_finish3d(FhRenderState* S, FhGeometryPixel* out, uint32_t n_ctx, uint32_t* sticky, volatile uint32_t* host_flags) {
+// `leave_clean`: the frame hands its buffer set back the way k_frame_begin's clears would leave it for the next frame (capi_render.hpp
+// clean sets) - this kernel reads every z-buffer word anyway and is the last to touch the set.  A word that is still 0 was never
+// written, and neither were its pixel's normals (a normals kernel writes the pixel whose hit it finds in the z-buffer and leaves the
+// depth, >= 1, there): only the words the frame wrote are written again.  The min-depth pyramid (`mind_words` words from mind[0]) is zeroed whole.
+__global__ void k_finish3d(FhRenderState* S, FhGeometryPixel* out, uint32_t n_ctx, uint32_t* sticky, volatile uint32_t* host_flags, uint32_t leave_clean, uint32_t mind_words) {
     const AS4 FhRender& P = *(const AS4 FhRender*)&S->P;
     const size_t n = (size_t)P.width * P.height;
+    if (leave_clean)
+        for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < mind_words; i += (size_t)gridDim.x * blockDim.x) S->mind[0][i] = 0u;
     if (blockIdx.x == 0 && threadIdx.x == 0 && sticky) {
         uint32_t q = 0;
         for (uint32_t k = 0; k < n_ctx; k++) q |= S[k].queue_overflow;
@@ -1754,11 +1786,13 @@ __global__ void k_finish3d(FhRenderState* S, FhGeometryPixel* out, uint32_t n_ct
         }
     }
     for (size_t i = blockIdx.x * (size_t)blockDim.x + threadIdx.x; i < n; i += (size_t)gridDim.x * blockDim.x) {
-        const uint32_t d = (uint32_t)(S->zbuf[i] >> 32);
+        const uint64_t zb = S->zbuf[i];
+        const uint32_t d = (uint32_t)(zb >> 32);
         FhGeometryPixel o;
         if (d >= P.depth - 1) { o.normal[0] = 0.0f; o.normal[1] = 0.0f; o.normal[2] = 1.0f; o.depth = P.depth; }
         else { o.normal[0] = S->normals[i * 3]; o.normal[1] = S->normals[i * 3 + 1]; o.normal[2] = S->normals[i * 3 + 2]; o.depth = d; }
         out[i] = o;
+        if (leave_clean && zb) { S->zbuf[i] = 0; S->normals[i * 3] = 0.0f; S->normals[i * 3 + 1] = 0.0f; S->normals[i * 3 + 2] = 0.0f; }
     }
 }
 
