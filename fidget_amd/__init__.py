@@ -26,7 +26,7 @@ import numpy as np
 _HERE = os.path.dirname(os.path.abspath(__file__))
 _CSRC = os.path.join(_HERE, "csrc")
 LIB_PATH = os.environ.get("FHIP_LIB") or os.path.join(_CSRC, "libfidget_hip.so")     # (FHIP_LIB: a variant build, tools/build_lib_variant.py - A/B runs)
-_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_bound.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_mesh_util.hpp", "capi_voxels.hpp", "capi_contour.hpp", "capi_cc.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
+_SOURCES = ["capi.hip", "capi_core.hpp", "capi_context.hpp", "capi_tapes.hpp", "capi_eval.hpp", "capi_bound.hpp", "capi_render.hpp", "frame_plan.hpp", "frame_schedule.hpp", "capi_effects.hpp", "capi_mesh.hpp", "capi_mesh_util.hpp", "capi_voxels.hpp", "capi_contour.hpp", "capi_cc.hpp", "capi_debug.hpp", "capi_solve.hpp", "solve.hip", "solve_lm.hpp", "kernels.hip", "prune2.hip", "effects.hip", "mesh.hip", "mesh_qef.hpp", "mesh_collapse.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "mesh_slice.hpp", "slice.hip", "capi_slice.hpp", "contour/contour.hpp", "host_mesh.hpp", "dev_ops.hpp", "host_graph.hpp", "host_regtape.hpp", "render_state.h", "tape_format.h",
             "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py", "trans_funcs.hip", "trans_libm.hpp", "offsets.cpp", "../../include/fidget_hip.h",
             "../../include/fidget_hip_debug.h"]
 
@@ -65,6 +65,8 @@ EXPORTS = [
     "fhip_topology_vertices_dev", "fhip_topology_triangles_dev", "fhip_topology_triangle_shells_dev", "fhip_topology_shells", "fhip_topology_edges", "fhip_topology_free",
     "fhip_voxels_outlines", "fhip_outlines_counts", "fhip_outlines_layers", "fhip_outlines_vertices", "fhip_outlines_loops", "fhip_outlines_xy_dev", "fhip_outlines_next_dev",
     "fhip_outlines_loop_dev", "fhip_outlines_free",
+    "fhip_topology_slices", "fhip_slices_counts", "fhip_slices_planes", "fhip_slices_loops", "fhip_slices_vertices", "fhip_slices_xy_dev", "fhip_slices_next_dev", "fhip_slices_loop_dev",
+    "fhip_slices_plane_dev", "fhip_slices_free",
     "fhip_profile_enable", "fhip_profile_read", "fhip_profile_read_kernels", "fhip_render_counters", "fhip_graph_new", "fhip_graph_free",
     "fhip_graph_len", "fhip_graph_var", "fhip_graph_constant", "fhip_graph_unary", "fhip_graph_binary",
     "fhip_graph_from_text", "fhip_tape_from_graph", "fhip_tape_axis_slot", "fhip_tape_var_slot",
@@ -215,6 +217,9 @@ def lib():
             "fhip_voxels_outlines": (i32, [vp, vp, u32, i32, u32, u32, u32, vp]), "fhip_outlines_counts": (None, [vp, vp]), "fhip_outlines_layers": (i32, [vp, vp, vp, vp, vp]),
             "fhip_outlines_vertices": (i32, [vp, u64, u64, vp, vp, vp]), "fhip_outlines_loops": (i32, [vp, u64, u64, vp, vp, vp, vp, vp, vp]),
             "fhip_outlines_xy_dev": (vp, [vp]), "fhip_outlines_next_dev": (vp, [vp]), "fhip_outlines_loop_dev": (vp, [vp]), "fhip_outlines_free": (None, [vp]),
+            "fhip_topology_slices": (i32, [vp, vp, vp, u32, u32, vp]), "fhip_slices_counts": (None, [vp, vp]), "fhip_slices_planes": (i32, [vp, vp, vp, vp, vp]),
+            "fhip_slices_loops": (i32, [vp, vp, vp, vp, vp, vp, vp, vp, vp]), "fhip_slices_vertices": (i32, [vp, vp, vp, vp, vp, vp, vp]), "fhip_slices_xy_dev": (vp, [vp]),
+            "fhip_slices_next_dev": (vp, [vp]), "fhip_slices_loop_dev": (vp, [vp]), "fhip_slices_plane_dev": (vp, [vp]), "fhip_slices_free": (None, [vp]),
             "fhip_debug_stl_pack": (i32, [vp, vp, u64, vp, u64, vp]),
             "fhip_profile_enable": (None, [vp, i32]), "fhip_profile_read": (i32, [vp, vp, vp]), "fhip_profile_read_kernels": (i32, [vp, vp, vp]),
             "fhip_render_counters": (i32, [vp, vp]),
@@ -1167,6 +1172,10 @@ class Mesh:
         """`mesh_topology(self, weld)`: what kind of mesh this is - edges, shells, volume - from the resident arrays where there are any"""
         return mesh_topology(self, weld)
 
+    def slices(self, zs):
+        """`mesh_slices(self, zs)`: the contour loops in which the planes z = zs[p] cut this mesh, from the resident arrays where there are any"""
+        return mesh_slices(self, zs)
+
     def vertices_device(self):
         """The vertices where the dual walk left them in device memory ([m, 3] float32), as an object carrying
         `__cuda_array_interface__` that keeps the mesh alive - `torch.as_tensor(obj, device="cuda")` views it; None when the
@@ -2101,6 +2110,15 @@ class Topology:
         """... and `.triangle_shell` ("<u4")"""
         return self._device("triangle_shells")
 
+    def slices(self, zs, table_log2=0):
+        """fhip_topology_slices: this indexed mesh cut by the planes z = zs[p] (float32, finite, strictly ascending) -> MeshSlices: per
+        plane the closed polygons whose vertices lie on the mesh's edges.  `table_log2`: 0, or the size of the crossing edges' hash table
+        as a power of two (tests; a table too small raises FidgetHipError Overflow)."""
+        zs = np.ascontiguousarray(zs, np.float32).reshape(-1)
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_topology_slices(self._hip._h, self._owner.h, _p(zs), len(zs), int(table_log2), C.byref(h)))
+        return MeshSlices(_Handle(h.value, lib().fhip_slices_free), self._hip, self)
+
     def edges(self, kind, device=False):
         """fhip_topology_edges: the edges of one class - "boundary" (where the holes are), "flipped", "nonmanifold", "unbalanced" - as
         [n, 2] uint32 vertex pairs (a, b), a < b, in the order of the first corners that use them: a numpy array, or with `device` a
@@ -2166,6 +2184,126 @@ def mesh_topology(mesh, weld=None, hip=None, table_log2=0):
     if res.counts["rejected"]:
         raise ValueError(f"mesh_topology: {res.counts['rejected']} of {res.counts['triangles']} triangles rejected: a coordinate that is not finite, or an index beyond the vertices")
     return res
+
+
+# ---- the slices of a triangle mesh: contour loops per plane (fhip_topology_slices) -------------------------------------------------
+SLICES_COUNTS = ("planes", "vertices", "segments", "loops", "irregular", "edge_slots")
+
+
+class MeshSlices:
+    """What `mesh_slices` found: the mesh of a `Topology` cut by planes z = const; the definitions stand in include/fidget_hip.h.
+    `.counts`: {planes, vertices, segments, loops, irregular, edge_slots}; `.zs` float32 [P]; `.per_plane`: {crossings, segments, loops}
+    uint64 [P]; `.topology`: the mesh that was cut.  Per crossing - a vertex of the slice on a mesh edge, ids in the order of the edges'
+    first corners and then by plane: `.xy` float32 [n, 2], `.plane` uint32 [n], `.edge` uint32 [n, 2] (u < v), `.next` uint32 [n]
+    (0xFFFFFFFF: no segment leaves), `.loop_of` uint32 [n], `.degree` uint8 [n] (out | in << 4, each at most 15).  `.loops`: a dict of
+    arrays, a row per loop in ascending order of leader - leader, plane, crossings, segments, irregular, area2 (float64: > 0 an outer
+    boundary, < 0 a hole), lo, hi [., 2].  The crossings' arrays stay in device memory (`.xy_device()` ...); host copies are made when
+    first asked for.  Everything is the same from run to run but area2, a float64 sum in an order of arrival."""
+
+    def __init__(self, owner, hip, topology=None):
+        self._owner, self._hip, self.topology = owner, hip, topology
+        c = np.zeros(8, np.uint64)
+        lib().fhip_slices_counts(owner.h, _p(c))
+        self.counts = dict(zip(SLICES_COUNTS, (int(v) for v in c)))
+        P, L = self.counts["planes"], self.counts["loops"]
+        self.zs = np.zeros(P, np.float32)
+        self.per_plane = {"crossings": np.zeros(P, np.uint64), "segments": np.zeros(P, np.uint64), "loops": np.zeros(P, np.uint64)}
+        hip.check(lib().fhip_slices_planes(owner.h, _p(self.zs), *(_p(self.per_plane[k]) for k in ("crossings", "segments", "loops"))))
+        self._loops = {"leader": np.zeros(L, np.uint32), "plane": np.zeros(L, np.uint32), "crossings": np.zeros(L, np.uint32), "segments": np.zeros(L, np.uint32),
+                       "irregular": np.zeros(L, np.uint32), "area2": np.zeros(L, np.float64), "lo": np.zeros((L, 2), np.float32), "hi": np.zeros((L, 2), np.float32)}
+        hip.check(lib().fhip_slices_loops(owner.h, *(_p(a) for a in self._loops.values())))
+        self._host = None
+
+    def _vertices(self):
+        if self._host is None:
+            n = self.counts["vertices"]
+            a = {"xy": np.zeros((n, 2), np.float32), "plane": np.zeros(n, np.uint32), "edge": np.zeros((n, 2), np.uint32), "next": np.zeros(n, np.uint32),
+                 "loop_of": np.zeros(n, np.uint32), "degree": np.zeros(n, np.uint8)}
+            self._hip.check(lib().fhip_slices_vertices(self._owner.h, *(_p(v) for v in a.values())))
+            self._host = a
+        return self._host
+
+    xy = property(lambda self: self._vertices()["xy"])
+    plane = property(lambda self: self._vertices()["plane"])
+    edge = property(lambda self: self._vertices()["edge"])
+    next = property(lambda self: self._vertices()["next"])
+    loop_of = property(lambda self: self._vertices()["loop_of"])
+    degree = property(lambda self: self._vertices()["degree"])
+    loops = property(lambda self: self._loops)
+
+    def _plane(self, p):
+        p = int(p)
+        if not 0 <= p < self.counts["planes"]:
+            raise IndexError(f"plane {p} is not among 0 .. {self.counts['planes'] - 1}")
+        return p
+
+    def loops_of(self, p):
+        """the ids of plane p's loops, ascending"""
+        return np.flatnonzero(self._loops["plane"] == self._plane(p))
+
+    def polygons(self, p):
+        """-> (the closed loops of plane p as float32 [n, 2] arrays, each from its leader on along `next`: walked on the host; the number
+        of plane p's loops left out because they hold an irregular crossing)"""
+        out, skipped = [], 0
+        for q in self.loops_of(p):
+            if self._loops["irregular"][q]:
+                skipped += 1
+                continue
+            m = int(self._loops["crossings"][q])
+            ids, v = np.zeros(m, np.int64), int(self._loops["leader"][q])
+            for k in range(m):
+                ids[k] = v
+                v = int(self.next[v])
+            out.append(self.xy[ids])
+        return out, skipped
+
+    def svg(self, p, path=None):
+        """Plane p's closed loops as one <path fill-rule="evenodd"> each, `M x y L x y ... Z`, with y negated - SVG's y grows downward -
+        and the bounds of the plane's loops as the viewBox.  Returns the text; written to `path` when given."""
+        polys, _ = self.polygons(p)
+        ids = self.loops_of(p)
+        lo = self._loops["lo"][ids].min(axis=0) if len(ids) else np.array([-1.0, -1.0])
+        hi = self._loops["hi"][ids].max(axis=0) if len(ids) else np.array([1.0, 1.0])
+        paths = "".join('<path fill-rule="evenodd" d="M ' + " L ".join(f"{float(x):.9g} {-float(y):.9g}" for x, y in q) + ' Z"/>\n' for q in polys)
+        text = (f'<svg xmlns="http://www.w3.org/2000/svg" viewBox="{float(lo[0]):.9g} {-float(hi[1]):.9g} {float(hi[0] - lo[0]):.9g} {float(hi[1] - lo[1]):.9g}">\n'
+                f'{paths}</svg>\n')
+        if path is not None:
+            with open(path, "w") as f:
+                f.write(text)
+        return text
+
+    def _device(self, what, shape, typestr):
+        ptr = getattr(lib(), f"fhip_slices_{what}_dev")(self._owner.h)
+        return _DeviceArray(self._owner, ptr, shape, typestr) if ptr else None
+
+    def xy_device(self):
+        """`.xy` where it is in device memory ([n, 2] "<f4") as an object carrying `__cuda_array_interface__` that keeps the result
+        alive; None when nothing crosses"""
+        return self._device("xy", (self.counts["vertices"], 2), "<f4")
+
+    def next_device(self):
+        """... `.next` ("<i4": the bits of the uint32 ids, as `Outlines.next_device` gives its)"""
+        return self._device("next", (self.counts["vertices"],), "<i4")
+
+    def loop_of_device(self):
+        """... `.loop_of` ("<i4")"""
+        return self._device("loop", (self.counts["vertices"],), "<i4")
+
+    def plane_device(self):
+        """... and `.plane` ("<i4")"""
+        return self._device("plane", (self.counts["vertices"],), "<i4")
+
+    def __repr__(self):
+        return f"MeshSlices({', '.join(f'{k}={v}' for k, v in self.counts.items())})"
+
+
+def mesh_slices(mesh, zs, weld=None, hip=None, table_log2=0):
+    """fhip_topology_slices: the step a slicer performs on an STL - the triangles cut by the planes z = zs[p] -> MeshSlices.  `mesh`:
+    anything `mesh_topology` takes - a `Mesh`, [T, 3, 3] triangles, a pair (vertices, triangles), numpy or torch CUDA - which is run
+    first with `weld`, or a `Topology`, which is cut as it is.  `zs`: float32, finite and strictly ascending, else FidgetHipError
+    Unsupported."""
+    topo = mesh if isinstance(mesh, Topology) else mesh_topology(mesh, weld, hip)
+    return topo.slices(zs, table_log2)
 
 
 # ---- contours of a 2D slice: vertices on the crossing lattice edges, directed segments, loops, SVG (fhip_contour2d) -----------

@@ -1375,3 +1375,5 @@ fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const f
 #include "capi_topo.hpp"
 // the outlines of a voxel bitmap's layers (fhip_voxels_outlines)
 #include "capi_outline.hpp"
+// the slices of a triangle mesh (fhip_topology_slices): after capi_topo.hpp, whose fhip_topology it cuts
+#include "capi_slice.hpp"

@@ -727,6 +727,62 @@ const uint32_t* fhip_outlines_next_dev(const void* outlines);
 const uint32_t* fhip_outlines_loop_dev(const void* outlines);
 void fhip_outlines_free(void* outlines);
 
+/* ---- the slices of a triangle mesh: closed contour loops per plane z = const ----------------------------------------
+ * (No counterpart in the reference, which never cuts a mesh: the definition below is the specification.  Every output but one is the
+ * same bits from run to run and does not depend on how the hardware orders the threads; a loop's area2 is a float64 sum of the same
+ * terms in an order of arrival that may differ from run to run, and it alone.)
+ * INPUT.  `topology`: a handle of fhip_triangles_topology or fhip_mesh_topology with its device arrays - the vertices, 3 f32 each, and
+ * the triangles as vertex ids, welded or as given, no coordinate that is not finite.  A topology that rejected triangles holds no mesh
+ * and is FHIP_ERR_UNSUPPORTED.  `zs`: n_planes f32 on the host.  The planes must be finite and strictly ascending: anything else is
+ * FHIP_ERR_UNSUPPORTED, and nothing is written.  n_planes == 0 is FHIP_OK with empty results, as is a mesh without triangles.  A
+ * triangle with two equal vertex ids is skipped.  Planes are always z = const; other directions are the caller's transform of the
+ * vertices.
+ * SIDE.  Vertex v is above plane p iff z_v >= zs[p], by float comparison, so -0 equals +0.  a(v) is the number of planes v is above,
+ * an upper bound search in zs; everything after it is integer arithmetic.  Edge {u, v} crosses exactly the planes
+ * min(a_u, a_v) <= p < max(a_u, a_v); triangle t crosses the planes from the smallest to the largest a of its corners.  A solid
+ * spanning [z0, z1] is therefore cut by the planes in (z0, z1].
+ * CROSSINGS.  A crossing is a pair (undirected mesh edge, plane): a vertex of the slice, the same one from whichever triangle reaches
+ * it.  The crossing edges are taken in the order of their first corners - the smallest corner 3 t + i that uses the edge, from i to
+ * i + 1 - and within an edge the crossings by ascending plane; ids come from one exclusive prefix sum over the corners, never from the
+ * order of the table's slots.  2^32 - 1 crossings or more is FHIP_ERR_OVERFLOW, and so is 2^32 - 1 segments or more.  edge[X] = (u, v),
+ * u < v, and plane[X].  Position: with u the end with the smaller vertex id, t = (zs[p] - z_u) / (z_v - z_u), x = x_u + t (x_v - x_u)
+ * and y likewise, in binary64 from the floats converted, every operation rounded on its own, no contraction, the result rounded to
+ * float32: xy[X].  z_u == zs[p] gives the mesh vertex itself.  Coincident crossings and zero-length segments are legal.
+ * SEGMENTS.  A crossing triangle has one corner alone on its side of the plane; name the corners (A, B, C) in the triangle's order
+ * with A the lone one.  If A is above, the segment runs from the crossing on edge A -> B to the crossing on edge C -> A; if A is below,
+ * the other way.  For a mesh that is counter-clockwise seen from outside the inside is then on the left seen from +z: outer boundaries
+ * have area2 > 0 and holes area2 < 0, as for fhip_voxels_outlines and fhip_contour2d.  Vertices are not reduced to turns.
+ * PER CROSSING.  out and in are the numbers of segments that leave a crossing and arrive at it; degree[X] is one byte, out | in << 4,
+ * each saturating at 15.  A crossing is irregular iff out != 1 or in != 1: on a boundary edge, a nonmanifold edge, a flipped
+ * triangle.  next[X] is the end of the segment leaving X in the triangle with the smallest index, 0xFFFFFFFF when out == 0.
+ * LOOPS.  A loop is a connected part of the crossings under all segments.  A loop's leader is its smallest crossing id; loops are
+ * numbered in ascending order of leader; loop_of[X].  Per loop: leader; plane; the numbers of its crossings, segments and irregular
+ * crossings; area2, the float64 sum over its segments s -> d of x_s y_d - x_d y_s from the float32 positions converted, each product
+ * and the difference rounded on their own; lo[2] and hi[2], the exact bounds of its positions, -0 taken as +0.  A loop is a closed
+ * polygon iff it has no irregular crossing: next then walks it from the leader back to the leader.  Per plane: the counts of
+ * crossings, segments and loops.
+ * THE PASSES.  Levels per vertex; the crossing edges alone into a lock-free edge table as fhip_triangles_topology's (a topology does
+ * not keep its own), sized from the count of crossing corners: the least power of two at or above 4/3 of them, or exactly
+ * 1 << table_log2 slots (at most 32); a probe sequence that finds no room is FHIP_ERR_OVERFLOW, nothing spins.  Counts at the first
+ * corners and per triangle, prefix sums; then a lane per crossing and a lane per segment, each finding its corner or triangle by a
+ * search in the sums, so that a coarse mesh under thousands of planes fills the device; a union-find towards the smaller root; the
+ * loops' table by atomics.  No pass waits for another workgroup.  The scratch stays with the context in the buffer of the mesher's leaf
+ * records: fhip_ctx_trim gives it back.  The call blocks.
+ * counts = {planes, crossings, segments, loops, irregular crossings, edge-table slots, 0, 0}.  fhip_slices_planes: zs and the three
+ * counts per plane; fhip_slices_loops: a row per loop; fhip_slices_vertices: host copies of the arrays per crossing (xy 2 f32, edge 2
+ * u32); any output pointer may be NULL.  The _dev getters return the handle's device arrays, NULL where there are no crossings. */
+fhip_status fhip_topology_slices(fhip_ctx* ctx, const void* topology, const float* zs, uint32_t n_planes, uint32_t table_log2, void** out);
+void fhip_slices_counts(const void* slices, uint64_t out[8]);
+fhip_status fhip_slices_planes(const void* slices, float* zs, uint64_t* crossings, uint64_t* segments, uint64_t* loops);
+fhip_status fhip_slices_loops(const void* slices, uint32_t* leader, uint32_t* plane, uint32_t* crossings, uint32_t* segments, uint32_t* irregular,
+                              double* area2, float* lo, float* hi);
+fhip_status fhip_slices_vertices(const void* slices, float* xy, uint32_t* plane, uint32_t* edge, uint32_t* next, uint32_t* loop_of, uint8_t* degree);
+const float* fhip_slices_xy_dev(const void* slices);
+const uint32_t* fhip_slices_next_dev(const void* slices);
+const uint32_t* fhip_slices_loop_dev(const void* slices);
+const uint32_t* fhip_slices_plane_dev(const void* slices);
+void fhip_slices_free(void* slices);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

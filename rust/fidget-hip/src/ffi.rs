@@ -200,6 +200,18 @@ extern "C" {
     pub fn fhip_outlines_next_dev(outlines: *const c_void) -> *const u32;
     pub fn fhip_outlines_loop_dev(outlines: *const c_void) -> *const u32;
     pub fn fhip_outlines_free(outlines: *mut c_void);
+    // the slices of a checked mesh under planes z = const: crossings on the mesh's edges, their successors, the loops and their table
+    pub fn fhip_topology_slices(ctx: *mut fhip_ctx, topology: *const c_void, zs: *const f32, n_planes: u32, table_log2: u32, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_slices_counts(slices: *const c_void, out: *mut u64);
+    pub fn fhip_slices_planes(slices: *const c_void, zs: *mut f32, crossings: *mut u64, segments: *mut u64, loops: *mut u64) -> fhip_status;
+    pub fn fhip_slices_loops(slices: *const c_void, leader: *mut u32, plane: *mut u32, crossings: *mut u32, segments: *mut u32, irregular: *mut u32, area2: *mut f64,
+                             lo: *mut f32, hi: *mut f32) -> fhip_status;
+    pub fn fhip_slices_vertices(slices: *const c_void, xy: *mut f32, plane: *mut u32, edge: *mut u32, next: *mut u32, loop_of: *mut u32, degree: *mut u8) -> fhip_status;
+    pub fn fhip_slices_xy_dev(slices: *const c_void) -> *const f32;
+    pub fn fhip_slices_next_dev(slices: *const c_void) -> *const u32;
+    pub fn fhip_slices_loop_dev(slices: *const c_void) -> *const u32;
+    pub fn fhip_slices_plane_dev(slices: *const c_void) -> *const u32;
+    pub fn fhip_slices_free(slices: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,
