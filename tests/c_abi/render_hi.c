@@ -50,7 +50,7 @@ int main(int argc, char** argv) {
         return m[0] == 0.0625f ? 0 : 1;
     }
     if (argc == 2 && strcmp(argv[1], "--layout") == 0) {
-        /* the config structs as this C compiler lays them out, for the check against the ctypes mirror (fidget_amd/__init__.py) */
+        /* the config structs as this C compiler lays them out, for the check against the ctypes mirror (fidget_amd/_abi.py) */
 #define F(T, f) printf("\"" #T "." #f "\": [%zu, %zu], ", offsetof(T, f), sizeof(((T*)0)->f))
         printf("{");
         F(fhip_render2d_config, width); F(fhip_render2d_config, height); F(fhip_render2d_config, world_to_model);

@@ -1,6 +1,6 @@
 """The boundary from a native caller: tests/c_abi/render_hi.c, plain C11 against include/fidget_hip.h only (the closest stand-in
 for the Rust FFI of INTEGRATION.md that this image can compile).  Without a GPU: the header is valid strict C11, every entry
-point the program uses links and loads, and the config structs are laid out as the ctypes mirror in fidget_amd/__init__.py
+point the program uses links and loads, and the config structs are laid out as the ctypes mirror in fidget_amd/_abi.py
 types them by hand.  With one: the program renders hi.vm and finds the reference's golden image (pixel_render.rs:75-106)."""
 import ctypes as C
 import json

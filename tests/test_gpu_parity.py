@@ -113,7 +113,7 @@ def test_render3d_survives_a_full_tape_arena(arena_mb):
         a = F.render3d(F.Shape.from_vm(m), 256)[0]
         b = O.render3d(O.Shape.from_vm(m), 256)[0]
         assert (a["depth"] == b["depth"]).all() and (a["normal"].view(np.uint32) == b["normal"].view(np.uint32)).all()
-        c = F._default_ctx.counters() if F._default_ctx else None
+        c = F.default_context().counters()
         print("overflows", c["arena_overflow"] if c else "?")
     """)
     r = subprocess.run([sys.executable, "-c", code], capture_output=True, text=True, timeout=300)
