@@ -16,7 +16,7 @@
 
 static const uint32_t VM_TILES_2D[] = {128, 32, 8};        // fidget-core/src/vm/mod.rs:255-257
 static const uint32_t VM_TILES_3D[] = {128, 64, 32, 16, 8};  // fidget-core/src/vm/mod.rs:251-253
-static const uint32_t FH_LEAF_REGS = 40, FH_LEAF_REGS_T = 44;      // (gen_interp.py main(): fh_columns' 40 x 2 shape, fh_columns_t's 44 x 4)
+static const uint32_t FH_LEAF_REGS = 40, FH_LEAF_REGS_T = 44;      // (gen_interp.py gen_columns: fh_columns' 40 x 2 shape, fh_columns_t's 44 x 4)
 static const uint32_t FH_NORMAL_REGS = 40;                         // (gen_normals.py NR)
 // 2D hint of the HIP shape: 128 -> 16 with 16 x 16 pixel leaves - what fidget-jit uses (fidget-jit/src/lib.rs:984-986); a fan-out
 // of 64 children per parent fills a wavefront of the tile-stage kernels (the VM's 128 / 32 / 8 fans out by 16)
@@ -278,7 +278,7 @@ static PlanStatus plan_frame(const TapeFacts& t, const PlanInputs& in, bool is3d
     // assembly leaf kernels: supported opcodes only (any 4x4 screen-to-model matrix, projective ones included)
     R.asm_points = in.use_asm && is3d && (t.asm_ok || !in.no_columns_t);
     R.asm_points_t = R.asm_points && !t.asm_ok;   // transcendental / modulo / rng opcodes: the variant that calls the compiled routines
-    // (the most registers of a leaf the leaf kernel takes - gen_interp.py main(): the largest register-file shape of fh_columns / fh_columns_t)
+    // (the most registers of a leaf the leaf kernel takes - gen_interp.py gen_columns: the largest register-file shape of fh_columns / fh_columns_t)
     S.leaf_asm_regs = !R.asm_points ? 32u : (R.asm_points_t ? FH_LEAF_REGS_T : FH_LEAF_REGS);
     // (fh_normals_t has the transcendental, rng and atan2 handlers; a modulo's gradient - div_euclid - keeps the C++ kernel)
     R.asm_normals = R.asm_points && !in.no_asm_normals && (!R.asm_points_t || !t.has_mod);

@@ -26,17 +26,20 @@ Mode bit 0 (frames whose leaf stage is driven by the slab's `leaves`, render_sta
 leaf that owns a pixel's hit is the column's leaf or nobody): no list of k_hits3d - wave pass i takes leaf i, i + n_waves, ... of the slab
 and finds out from the z-buffer words whether it has a hit, as above; a leaf of more registers than the file holds is skipped.
 """
-from gen_interp import (Interp, OPS, FILE, S_KERNARG, S_STATE, S_MAT, S_SIGN, S_ABSM, S_ARENA, S_TAPE, S_LEN, S_W1, S_T0, S_OUT, S_A, S_T1, S_PC, S_SAVE,
-                        S_M, S_RET, V_LANE, V_QNAN, V_SQRTC, VT, VU, VW, VD, SRC0, SRC1, DST, kernel_header, kernel_footer, common_consts,
-                        handler_base, call_interp)
+import gen_trans
+from gen_asm import (Kernel, PTR, U32, pcrel, ieee_div, ieee_sqrt, round_half_away, SRC1, DST, S_KERNARG, S_STATE, S_SIGN, S_W1, S_T0,
+                     S_OUT, S_A, S_T1, S_PC, S_SAVE, S_M, V_LANE)
+from gen_interp import (Interp, DEFAULT, S_MAT, S_ARENA, S_LEN, S_SLOTX, S_SLOTY, S_SLOTZ, S_WIDTH, S_HEIGHT, S_ZBUF, S_FPLIST,
+                        common_consts, handler_base, call_interp)
 
+# The kernel works under the default register map (gen_interp.DEFAULT), handed to its interpreter explicitly; the map's names used here:
+REGS = DEFAULT
+VT, VU, VW, VD, V_QNAN = REGS.VT, REGS.VU, REGS.VW, REGS.VD, REGS.V_QNAN
 NR = 40      # registers of a leaf tape the kernel takes (4 VGPRs each: a file of 160 behind 64 fixed registers - two waves per SIMD as with 32; capi_render.hpp FH_NORMAL_REGS)
-T_BASE = FILE + NR * 4      # register window of the transcendental routines (fh_normals_t)
-S_SLOTX, S_SLOTY, S_SLOTZ = "s0", "s1", "s3"
+T_BASE = REGS.FILE + NR * 4      # register window of the transcendental routines (fh_normals_t)
 S_WI, S_NWG, S_NFP = "s6", "s7", "s40"
-S_WIDTH, S_HEIGHT = "s24", "s25"
 S_ZLO, S_ZHI = "s26", "s27"
-S_NORMALS, S_LEAVES, S_ZBUF, S_FPLIST = "s[32:33]", "s[34:35]", "s[36:37]", "s[38:39]"
+S_NORMALS, S_LEAVES = "s[32:33]", "s[34:35]"
 S_TODO = "s[80:81]"
 S_CUR = "s78"
 S_MODE = "s41"          # kernarg word 7: bit 0 = by the slab's leaves (no hit lists)
@@ -51,65 +54,24 @@ class GradInterp(Interp):
     INPLACE = set()
 
     def __init__(self, a, name, off, trans=False):
-        super().__init__(a, name, NR, 4, "grad", off, trans=trans)
+        super().__init__(a, name, NR, 4, "grad", off, trans=trans, regs=REGS)
 
     def call(self, fn, arg, res, arg2=None):
         """res = <fn>(arg [, arg2]) by the compiled routine fh_tn_<fn> (gen_trans.py, embedded with its vector registers in
         v[T_BASE .. T_BASE + 25] behind the register file); clobbers those, s86..s97 and vcc"""
         here, ret = self.a.label("call"), self.a.label("ret")
         self.a(f"\tv_mov_b32 v{T_BASE}, {arg}" + (f"\n\tv_mov_b32 v{T_BASE + 1}, {arg2}" if arg2 else ""))
-        self.a(f"""
-	s_getpc_b64 s[96:97]
-{here}:
-	s_add_u32 s96, s96, {ret} - {here}
-	s_addc_u32 s97, s97, 0
-	s_branch fh_tn_{fn}
-{ret}:
-	v_mov_b32 {res}, v{T_BASE}""")
+        pcrel(self.a, "s[96:97]", ret, here)
+        self.a(f"\ts_branch fh_tn_{fn}\n{ret}:\n\tv_mov_b32 {res}, v{T_BASE}")
 
     # ---- scalar helpers on plain VGPRs -----------------------------------------------------------
     def div1(self, n, d, r):
-        """r = n / d, IEEE (the div_scale / rcp / fma / div_fmas / div_fixup sequence of Interp.f_div); r may be n or d"""
-        t = VD
-        self.a(f"""
-	v_div_scale_f32 {t[0]}, {S_SAVE}, {d}, {d}, {n}
-	v_rcp_f32 {t[1]}, {t[0]}
-	v_div_scale_f32 {t[2]}, vcc, {n}, {d}, {n}
-	v_fma_f32 {t[3]}, -{t[0]}, {t[1]}, 1.0
-	v_fmac_f32 {t[1]}, {t[3]}, {t[1]}
-	v_mul_f32 {t[3]}, {t[2]}, {t[1]}
-	v_fma_f32 {t[4]}, -{t[0]}, {t[3]}, {t[2]}
-	v_fmac_f32 {t[3]}, {t[4]}, {t[1]}
-	v_fma_f32 {t[0]}, -{t[0]}, {t[3]}, {t[2]}
-	v_div_fmas_f32 {t[0]}, {t[0]}, {t[1]}, {t[3]}
-	v_div_fixup_f32 {r}, {t[0]}, {d}, {n}""")
+        """r = n / d, IEEE; r may be n or d"""
+        ieee_div(self.a, n, d, r, VD, S_SAVE)
 
     def sqrt1(self, x, r):
-        """r = sqrtf(x), correctly rounded (the full sequence of Interp.f_sqrt)"""
-        d = VD
-        self.a(f"""
-	v_mul_f32 {d[0]}, 0x4f800000, {x}
-	v_cmp_gt_f32 vcc, {V_SQRTC}, {x}
-	s_nop 1
-	v_cndmask_b32 {d[1]}, {x}, {d[0]}, vcc
-	v_sqrt_f32 {d[0]}, {d[1]}
-	s_nop 0
-	v_add_u32 {d[2]}, -1, {d[0]}
-	v_add_u32 {d[3]}, 1, {d[0]}
-	v_fma_f32 {d[4]}, -{d[2]}, {d[0]}, {d[1]}
-	v_fma_f32 {d[5]}, -{d[3]}, {d[0]}, {d[1]}
-	v_cmp_ge_f32_e64 {S_M[0]}, 0, {d[4]}
-	s_nop 1
-	v_cndmask_b32_e64 {d[0]}, {d[0]}, {d[2]}, {S_M[0]}
-	v_cmp_lt_f32_e64 {S_M[0]}, 0, {d[5]}
-	s_nop 1
-	v_cndmask_b32_e64 {d[0]}, {d[0]}, {d[3]}, {S_M[0]}
-	v_mul_f32 {d[2]}, 0x37800000, {d[0]}
-	v_cndmask_b32 {d[0]}, {d[0]}, {d[2]}, vcc
-	v_mov_b32 {d[3]}, 0x260
-	v_cmp_class_f32 vcc, {d[1]}, {d[3]}
-	s_nop 1
-	v_cndmask_b32 {r}, {d[0]}, {d[1]}, vcc""")
+        """r = sqrtf(x), correctly rounded"""
+        ieee_sqrt(self.a, x, r, VD, S_M[0], REGS.V_SQRTC)
 
     def gr_mul(self, A, B, R):
         """dev_ops.hpp gr_mul: v = a.v b.v, d = a.v b.d + b.v a.d"""
@@ -193,16 +155,8 @@ class GradInterp(Interp):
                     a(f"\tv_cmp_eq_f32 vcc, 0, {VT[0]}\n\ts_nop 1\n\tv_cndmask_b32 {VW[0]}, 0, 1.0, vcc")
                     self.gr1(VW, VW[0])
                 else:
-                    if op == "ROUND":           # roundf: half away from zero (Interp.f_round)
-                        d = VD
-                        a(f"""
-	v_trunc_f32 {d[0]}, {VT[0]}
-	v_sub_f32 {d[1]}, {VT[0]}, {d[0]}
-	v_cmp_ge_f32_e64 {S_M[0]}, |{d[1]}|, 0.5
-	s_nop 1
-	v_cndmask_b32_e64 {d[1]}, 0, 1.0, {S_M[0]}
-	v_bfi_b32 {d[1]}, {S_ABSM}, {d[1]}, {VT[0]}
-	v_add_f32 {VW[0]}, {d[0]}, {d[1]}""")
+                    if op == "ROUND":
+                        round_half_away(a, VT[0], VW[0], VD, S_M[0])
                     else:
                         a(f"\t{'v_floor_f32' if op == 'FLOOR' else 'v_ceil_f32'} {VW[0]}, {VT[0]}")
                     self.gr1(VW, VW[0])
@@ -358,15 +312,15 @@ def gen_normals(a, off, trans=None):
     name = "fh_normals_t" if trans else "fh_normals"
     o, m = off, S_MAT
     it = GradInterp(a, name + "_g", off, trans=bool(trans))
-    nvg = T_BASE + 26 if trans else FILE + NR * 4
-    kernel_header(a, name, 32, nvg)
+    kernel = Kernel(name, [PTR] + [U32] * 6, T_BASE + 26 if trans else T_BASE)
+    kernel.begin(a)
     a(f"""
 	s_load_dwordx2 {S_STATE}, {S_KERNARG}, 0x0
 	s_load_dwordx4 s[48:51], {S_KERNARG}, 0x8
 	s_load_dword s52, {S_KERNARG}, 0x18
 	s_load_dword {S_MODE}, {S_KERNARG}, 0x1c
 	s_mov_b32 {S_WI}, s2""")
-    common_consts(a)
+    common_consts(a, REGS)
     handler_base(a, it)
     a(f"""
 	s_waitcnt lgkmcnt(0)
@@ -503,9 +457,8 @@ def gen_normals(a, off, trans=None):
 	s_branch .L{name}_leaf
 .L{name}_exit:
 	s_waitcnt vmcnt(0)""")
-    kernel_footer(a, name, 32, nvg, 102, True)
+    kernel.end(a)
     if trans:
-        import gen_trans
         gen_trans.embed(a, trans, v_base=T_BASE, prefix="fh_tn_")
     it.emit()
-    return name, 32, nvg, [(8, "global_buffer")] + [(4, "by_value")] * 6
+    return kernel

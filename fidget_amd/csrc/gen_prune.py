@@ -18,11 +18,9 @@ kernarg: { FhRenderState* S; u32 level; u32 big; u32 max_choices; u32 mode }
 grid   : 64 workgroups (of one wave) per slot; workgroup = slot * 64 + child lane
 Limits : <= 128 registers
 """
-from gen_tiles import SLOT_SIZE, SL_COFF, SL_CLEN, SL_CRC, SL_XYZ
+from gen_asm import Kernel, PTR, U32, S_KERNARG, S_WG, S_STATE, V_LANE
 
-S_KERNARG = "s[0:1]"
-S_WG = "s2"
-S_STATE = "s[4:5]"
+# (the kernel's working set is its own: S_TAPE, S_M, S_W0, S_T0, S_RET ... are other registers here than in the interpreters)
 S_LEVEL, S_BIG, S_MAXCH = "s6", "s7", "s3"
 S_SLOT = "s[8:9]"
 S_OFF, S_LEN, S_RC = "s12", "s13", "s14"     # slot header s[12:15]
@@ -51,7 +49,7 @@ S_E0, S_E1 = "s84", "s85"
 S_ALIAS = "s86"
 S_RET = "s[88:89]"
 S_MRR, S_MRI, S_MNOA = "s[90:91]", "s[92:93]", "s[94:95]"   # opcode-set bit masks
-V_LANE, V_MAPA, V_MAPB, V_L8, V_E0, V_E1, V_ZERO, V_T = "v0", "v1", "v2", "v3", "v4", "v5", "v6", "v7"
+V_MAPA, V_MAPB, V_L8, V_E0, V_E1, V_ZERO, V_T = "v1", "v2", "v3", "v4", "v5", "v6", "v7"
 V_CW0, V_CW1, V_CCH, V_COUT = "v8", "v9", "v10", "v11"         # current batch: op words, choice, out & 63
 V_NW0, V_NW1, V_NCI, V_NCHW = "v12", "v13", "v14", "v15"       # next batch: op words, choice index, choice word (in flight)
 V_NN = "v[16:17]"                                              # the batch below, in flight
@@ -228,15 +226,10 @@ class Prune1:
 
     def emit(self):
         a, o = self.a, self.off
-        name = "fh_prune1"
+        kernel = Kernel("fh_prune1", [PTR] + [U32] * 4, 24)
         nxt = ".Lfh_prune1_next"
+        kernel.begin(a)
         a(f"""
-	.text
-	.protected {name}
-	.globl {name}
-	.p2align 8
-	.type {name},@function
-{name}:
 	s_load_dwordx2 {S_STATE}, {S_KERNARG}, 0x0
 	s_load_dwordx4 s[8:11], {S_KERNARG}, 0x8
 	v_mov_b32 {V_MAPA}, {DEAD}
@@ -276,8 +269,8 @@ class Prune1:
 	s_cmp_ge_u32 {S_T0}, {S_T2}
 	s_cbranch_scc1 .Lfh_prune1_exit
 	; slot = slots + si * sizeof(FhSlot); chw column of this child
-	s_mul_i32 {S_T1}, {S_T0}, {SLOT_SIZE}
-	s_mul_hi_u32 {S_T2}, {S_T0}, {SLOT_SIZE}
+	s_mul_i32 {S_T1}, {S_T0}, {o['sizeof_slot']}
+	s_mul_hi_u32 {S_T2}, {S_T0}, {o['sizeof_slot']}
 	s_add_u32 s8, s8, {S_T1}
 	s_addc_u32 s9, s9, {S_T2}
 	s_add_u32 {S_T1}, {S_MAXCH}, 15
@@ -293,8 +286,8 @@ class Prune1:
 	; is this child marked (c_len == ~0)?  c_off = end of its arena slot
 	s_add_u32 s82, s8, {S_T1}
 	s_addc_u32 s83, s9, 0
-	s_load_dword {S_T2}, {S_T64}, {SL_CLEN}
-	s_load_dword {S_END}, {S_T64}, {SL_COFF}
+	s_load_dword {S_T2}, {S_T64}, {o['slot.c_len']}
+	s_load_dword {S_END}, {S_T64}, {o['slot.c_off']}
 	s_load_dwordx4 s[12:15], {S_SLOT}, 0x0
 	s_waitcnt lgkmcnt(0)
 	s_cmp_eq_u32 {S_T2}, -1
@@ -359,7 +352,7 @@ class Prune1:
 	v_and_b32 v18, 1, v18
 	v_cmp_ne_u32_e64 {S_M}, 0, v18
 	s_mov_b64 exec, 1
-	{"s_mov_b64 s[48:49], 0" if __import__("os").environ.get("FH_EXP") == "prune_nolive" else ""}
+	{"s_mov_b64 s[48:49], 0" if "prune_nolive" in a.exp else ""}
 	s_or_b64 {S_M}, {S_M}, {S_FORCE}
 	s_and_b64 {S_M}, {S_M}, {S_CAND}
 	s_cbranch_scc0 .Lfh_prune1_bdone
@@ -503,39 +496,13 @@ class Prune1:
 	v_mov_b32 v18, {S_T0}
 	v_mov_b32 v19, {S_COUNT}
 	v_mov_b32 {V_T}, {S_T1}
-	global_store_dword {V_ZERO}, v18, {S_T64} offset:{SL_COFF}
-	global_store_dword {V_ZERO}, v19, {S_T64} offset:{SL_CLEN}
-	global_store_dword {V_ZERO}, {V_T}, {S_T64} offset:{SL_CRC}
-.Lfh_prune1_exit:
-	s_endpgm
-.Lfh_prune1_end:
-	.size {name}, .Lfh_prune1_end - {name}
-	.rodata
-	.p2align 6
-	.amdhsa_kernel {name}
-		.amdhsa_group_segment_fixed_size 0
-		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size 24
-		.amdhsa_user_sgpr_count 2
-		.amdhsa_user_sgpr_kernarg_segment_ptr 1
-		.amdhsa_system_sgpr_workgroup_id_x 1
-		.amdhsa_system_sgpr_workgroup_id_y 0
-		.amdhsa_system_sgpr_workgroup_id_z 0
-		.amdhsa_system_vgpr_workitem_id 0
-		.amdhsa_next_free_vgpr 24
-		.amdhsa_next_free_sgpr 102
-		.amdhsa_accum_offset 24
-		.amdhsa_reserve_vcc 1
-		.amdhsa_float_round_mode_32 0
-		.amdhsa_float_round_mode_16_64 0
-		.amdhsa_float_denorm_mode_32 3
-		.amdhsa_float_denorm_mode_16_64 3
-		.amdhsa_dx10_clamp 1
-		.amdhsa_ieee_mode 1
-	.end_amdhsa_kernel
-	.text""")
+	global_store_dword {V_ZERO}, v18, {S_T64} offset:{o['slot.c_off']}
+	global_store_dword {V_ZERO}, v19, {S_T64} offset:{o['slot.c_len']}
+	global_store_dword {V_ZERO}, {V_T}, {S_T64} offset:{o['slot.c_rc']}
+.Lfh_prune1_exit:""")
+        kernel.end(a)
+        return kernel
 
 
 def gen_prune1(a, off):
-    Prune1(a, off).emit()
-    return "fh_prune1", 24, 24, [(8, "global_buffer")] + [(4, "by_value")] * 4
+    return Prune1(a, off).emit()

@@ -24,11 +24,12 @@ kernarg: { FhRenderState* S; u32 level; u32 big; u32 max_regs; u32 max_choices; 
 LDS    : regs [max_regs][64] x 8 B | choice words [(max_choices+15)/16][64] x 4 B | map [max_regs][64] x 1 B
 Limits : <= 128 registers (pool of 4 x 32 bits), opcodes of the assembly set (no transcendental / modulo / rng)
 """
-from gen_interp import Asm, OPS, UNSUPPORTED, HSTRIDE_LOG2  # noqa: F401
+import gen_trans
+from gen_asm import (Kernel, PTR, U32, renamed, pcrel, ieee_div, ieee_sqrt, round_half_away, S_KERNARG, S_STATE, S_SIGN, S_ABSM, S_HBASE,
+                     S_TAPE, S_QA, S_QB, S_W0, S_W1, S_CUR, S_T0, S_OUT, S_A, S_T1, S_FETCH, S_RET, S_PC, S_SAVE, S_M, V_LANE)
+from gen_interp import OPS, UNSUPPORTED, HSTRIDE_LOG2  # noqa: F401
 
-# ---- SGPRs -----------------------------------------------------------------------------------
-S_KERNARG = "s[0:1]"
-S_STATE = "s[4:5]"
+# ---- SGPRs (beyond gen_asm's, which every interpreter shares) ----------------------------------
 S_LEVEL, S_BIG, S_MAXREGS, S_MAXCH = "s6", "s7", "s8", "s9"
 S_ARENA = "s[10:11]"
 S_ARENACAP = "s12"
@@ -39,29 +40,18 @@ S_CUROFF = "s19"          # byte offset of eval_cur[big][level] in the state
 S_SLOT = "s[20:21]"
 S_OFF, S_LEN, S_RC, S_SLEVEL = "s24", "s25", "s26", "s27"   # slot header words 0..3
 S_ACT = "s[22:23]"
-S_SIGN, S_ABSM = "s28", "s29"
 S_DECIDED = "s[30:31]"
 S_CI = "s32"
 S_NREGS, S_NCH = "s33", "s36"
 S_PRUNE = "s[34:35]"
 S_BASE = "s37"
 S_MA, S_MB = "s[38:39]", "s[40:41]"
-S_HBASE = "s[42:43]"
-S_TAPE = "s[44:45]"
 S_REM = "s46"
 S_K = "s47"               # prune: index of the op being visited
-S_QA, S_QB = 48, 56
-S_W0, S_W1, S_CUR = "s64", "s65", "s[64:65]"
-S_T0, S_OUT, S_A, S_T1 = "s66", "s67", "s68", "s69"
 S_BATCH = "s70"
 S_OP = "s71"
-S_FETCH = "s[72:73]"
-S_RET = "s[74:75]"
 S_T64 = "s[76:77]"
 S_LIVE, S_ALIAS, S_CIMM, S_KEEP = "s[78:79]", "s[80:81]", "s[82:83]", "s[84:85]"
-S_PC = "s[86:87]"
-S_SAVE = "s[88:89]"
-S_M = [f"s[{90 + 2 * j}:{91 + 2 * j}]" for j in range(4)]
 S_T2, S_T3 = "s98", "s99"
 S_STAGED = "s13"
 S_SKIPR, S_SKIPC = "s7", "s19"   # (s7 = `big` is dead after the prologue)
@@ -72,7 +62,7 @@ S_TV = "s[84:85]"          # tape groups (forward only): FhSlot::tvals
 S_SI, S_NWG = "s2", "s100"   # slot index of this wave, waves in the launch
 
 # ---- VGPRs -----------------------------------------------------------------------------------
-V_LANE, V_L8, V_L4 = "v0", "v1", "v2"
+V_L8, V_L4 = "v1", "v2"
 VX, VY, VZ = ("v4", "v5"), ("v6", "v7"), ("v8", "v9")
 AL, AH, BL, BH, RL, RH = "v10", "v11", "v12", "v13", "v14", "v15"
 T = [f"v{16 + i}" for i in range(12)]      # v16..v27 scratch (also the div / sqrt sequences)
@@ -99,9 +89,7 @@ V_AOUT, V_AA, V_AB, V_AAL = "v80", "v81", "v82", "v83"   # prune: LDS addresses 
 V_MBV, V_AV = "v55", "v45"                  # prune: map[b], value of the aliased entry
 N_VGPR = 84
 
-SLOT_SIZE = 40 + 64 * 4 * 14
-SL_ACT, SL_XYZ, SL_CORNER, SL_RES, SL_COFF, SL_CLEN, SL_CRC = 16, 40, 40 + 6 * 256, 40 + 9 * 256, 40 + 11 * 256, 40 + 12 * 256, 40 + 13 * 256
-
+# (the FhSlot layout - its size, the offsets of act, tvals, xyz, res, c_off, c_len, c_rc - comes from offsets.json: off["sizeof_slot"], off["slot.<field>"])
 
 TRANS_UNARY = ("SIN", "COS", "TAN", "ASIN", "ACOS", "ATAN", "EXP", "LN")
 T_SMAP = [78, 79, 80, 81, 82, 83, 84, 85, 88, 89]      # scalar registers of the compiled routines in the tile kernels: the prune's masks
@@ -119,20 +107,17 @@ class Tiles:
         self.trans, self.t_base, self.t_prefix = trans, N_VGPR, "fh_til_"
         self.n_vgpr = N_VGPR + (26 if trans else 0)
 
+    def kernel(self):
+        return Kernel(self.name, [PTR] + [U32] * 8, self.n_vgpr)
+
     # ---- transcendental opcodes: interval rules of types/interval.rs:136-302 (dev_ops.hpp iv_sincos .. iv_ln) around the compiled
     # f32 routines (gen_trans.py), which are what the HIP kernels inline: same bounds, bit for bit --------------------------------
-    def tcall(self, fn, arg, res):
-        """res = <fn>(arg); clobbers the routines' window, s78..s85, s88, s89, s96, s97 and vcc"""
+    def tcall(self, fn, arg, res, arg1=None):
+        """res = <fn>(arg [, arg1]); clobbers the routines' window, s78..s85, s88, s89, s96, s97 and vcc"""
         here, ret = self.a.label("tcall"), self.a.label("tret")
-        self.a(f"""
-	v_mov_b32 v{self.t_base}, {arg}
-	s_getpc_b64 s[96:97]
-{here}:
-	s_add_u32 s96, s96, {ret} - {here}
-	s_addc_u32 s97, s97, 0
-	s_branch {self.t_prefix}{fn}
-{ret}:
-	v_mov_b32 {res}, v{self.t_base}""")
+        self.a(f"\tv_mov_b32 v{self.t_base}, {arg}" + (f"\n\tv_mov_b32 v{self.t_base + 1}, {arg1}" if arg1 else ""))
+        pcrel(self.a, "s[96:97]", ret, here)
+        self.a(f"\ts_branch {self.t_prefix}{fn}\n{ret}:\n\tv_mov_b32 {res}, v{self.t_base}")
 
     def quadrant(self, x, q):
         """q = iv_quadrant(x) as a float 0..3: rem_euclid(floorf(x * 2 / PI), 4), NaN -> 0 (dev_ops.hpp; interval.rs:143-147)"""
@@ -237,20 +222,6 @@ class Tiles:
 
     # ---- rand, mix, modulo, atan2: interval rules of types/interval.rs:485-503, 541-627 (dev_ops.hpp iv_rand, iv_mix, iv_rem_euclid,
     # iv_atan2) - the *_t kernels only: modulo and atan2 CALL the compiled f32 routines (rem_euclid, atan2f), as the HIP kernels inline them ----
-    def tcall2(self, fn, arg0, arg1, res):
-        """res = <fn>(arg0, arg1); clobbers what tcall clobbers"""
-        here, ret = self.a.label("tcall"), self.a.label("tret")
-        self.a(f"""
-	v_mov_b32 v{self.t_base}, {arg0}
-	v_mov_b32 v{self.t_base + 1}, {arg1}
-	s_getpc_b64 s[96:97]
-{here}:
-	s_add_u32 s96, s96, {ret} - {here}
-	s_addc_u32 s97, s97, 0
-	s_branch {self.t_prefix}{fn}
-{ret}:
-	v_mov_b32 {res}, v{self.t_base}""")
-
     def pcg(self, x, r, k):
         """r = rng::hash(x) (rng/mod.rs:8-13: the PCG output permutation); k = three scratch registers (r may be x)"""
         self.a(f"""
@@ -314,8 +285,8 @@ class Tiles:
 	s_and_b64 {S_M[0]}, {S_M[0]}, {S_M[1]}
 	s_and_b64 {S_M[2]}, {S_M[2]}, {S_T64}
 	s_and_b64 {S_M[2]}, {S_M[2]}, {S_M[0]}                    ; same: the remainders of both ends bound the result""")
-        self.tcall2("mod", AL, BL, r1)
-        self.tcall2("mod", AH, BL, r2)
+        self.tcall("mod", AL, r1, BL)
+        self.tcall("mod", AH, r2, BL)
         a(f"""
 	v_cmp_gt_f32_e64 {S_M[0]}, 0, {BL}
 	s_nop 1
@@ -362,8 +333,8 @@ class Tiles:
 	s_or_b64 {xpos}, {ypos}, {yneg}
 	s_nop 1
 	v_cndmask_b32_e64 {x1}, {BL}, {BH}, {xpos}""")
-        self.tcall2("atan2", y0, BL, v0)
-        self.tcall2("atan2", y1, x1, v1)
+        self.tcall("atan2", y0, v0, BL)
+        self.tcall("atan2", y1, v1, x1)
         a(f"""
 	v_min_f32 {RL}, {v0}, {v1}
 	v_max_f32 {RH}, {v0}, {v1}
@@ -409,54 +380,13 @@ class Tiles:
         self.a(f"\tv_cmp_u_f32_e64 {dst}, {lo}, {hi}")
 
     def div(self, num, den, out, d=T):
-        """IEEE-correct num / den (the compiler's own expansion)"""
-        self.a(f"""
-	v_div_scale_f32 {d[0]}, {S_T64}, {den}, {den}, {num}
-	v_rcp_f32 {d[1]}, {d[0]}
-	v_div_scale_f32 {d[2]}, vcc, {num}, {den}, {num}
-	v_fma_f32 {d[3]}, -{d[0]}, {d[1]}, 1.0
-	v_fmac_f32 {d[1]}, {d[3]}, {d[1]}
-	v_mul_f32 {d[3]}, {d[2]}, {d[1]}
-	v_fma_f32 {d[4]}, -{d[0]}, {d[3]}, {d[2]}
-	v_fmac_f32 {d[3]}, {d[4]}, {d[1]}
-	v_fma_f32 {d[0]}, -{d[0]}, {d[3]}, {d[2]}
-	v_div_fmas_f32 {d[0]}, {d[0]}, {d[1]}, {d[3]}
-	v_div_fixup_f32 {out}, {d[0]}, {den}, {num}""")
+        ieee_div(self.a, num, den, out, d, S_T64)
 
     def sqrt(self, x, out, d=T):
-        self.a(f"""
-	v_mul_f32 {d[0]}, 0x4f800000, {x}
-	v_cmp_gt_f32 vcc, {V_SQRTC}, {x}
-	s_nop 1
-	v_cndmask_b32 {d[1]}, {x}, {d[0]}, vcc
-	v_sqrt_f32 {d[0]}, {d[1]}
-	s_nop 0
-	v_add_u32 {d[2]}, -1, {d[0]}
-	v_add_u32 {d[3]}, 1, {d[0]}
-	v_fma_f32 {d[4]}, -{d[2]}, {d[0]}, {d[1]}
-	v_fma_f32 {d[5]}, -{d[3]}, {d[0]}, {d[1]}
-	v_cmp_ge_f32_e64 {S_M[3]}, 0, {d[4]}
-	s_nop 1
-	v_cndmask_b32_e64 {d[0]}, {d[0]}, {d[2]}, {S_M[3]}
-	v_cmp_lt_f32_e64 {S_M[3]}, 0, {d[5]}
-	s_nop 1
-	v_cndmask_b32_e64 {d[0]}, {d[0]}, {d[3]}, {S_M[3]}
-	v_mul_f32 {d[2]}, 0x37800000, {d[0]}
-	v_cndmask_b32 {d[0]}, {d[0]}, {d[2]}, vcc
-	v_mov_b32 {d[3]}, 0x260
-	v_cmp_class_f32 vcc, {d[1]}, {d[3]}
-	s_nop 1
-	v_cndmask_b32 {out}, {d[0]}, {d[1]}, vcc""")
+        ieee_sqrt(self.a, x, out, d, S_M[3], V_SQRTC)
 
     def round(self, x, out, d=T):
-        self.a(f"""
-	v_trunc_f32 {d[0]}, {x}
-	v_sub_f32 {d[1]}, {x}, {d[0]}
-	v_cmp_ge_f32_e64 {S_M[3]}, |{d[1]}|, 0.5
-	s_nop 1
-	v_cndmask_b32_e64 {d[1]}, 0, 1.0, {S_M[3]}
-	v_bfi_b32 {d[1]}, {S_ABSM}, {d[1]}, {x}
-	v_add_f32 {out}, {d[0]}, {d[1]}""")
+        round_half_away(self.a, x, out, d, S_M[3])
 
     def sel(self, dst, if_false, if_true, mask):
         """dst = mask ? if_true : if_false; the mask must have been written >= 2 wait states ago"""
@@ -1213,14 +1143,9 @@ class Tiles:
     def emit_kernel(self):
         a = self.a
         o = self.off
-        name = self.name
+        kernel = self.kernel()
+        kernel.begin(a)
         a(f"""
-	.text
-	.protected {name}
-	.globl {name}
-	.p2align 8
-	.type {name},@function
-{name}:
 	s_load_dwordx2 {S_STATE}, {S_KERNARG}, 0x0
 	s_load_dwordx4 s[8:11], {S_KERNARG}, 0x8
 	s_load_dwordx2 s[100:101], {S_KERNARG}, 0x18
@@ -1265,11 +1190,9 @@ class Tiles:
 	s_addc_u32 s77, s5, 0
 	s_load_dwordx2 {S_CHW}, {S_T64}, {o['chw']}
 	s_load_dwordx2 {S_ARENA}, {S_STATE}, {o['arena']}
-	s_load_dword {S_ARENACAP}, {S_STATE}, {o['arena_cap']}
-	s_getpc_b64 {S_HBASE}
-.Lfh_tiles_pc0:
-	s_add_u32 s42, s42, .Lfh_tiles_handlers - .Lfh_tiles_pc0
-	s_addc_u32 s43, s43, 0
+	s_load_dword {S_ARENACAP}, {S_STATE}, {o['arena_cap']}""")
+        pcrel(a, S_HBASE, ".Lfh_tiles_handlers", ".Lfh_tiles_pc0")
+        a(f"""
 	s_waitcnt lgkmcnt(0)
 	s_min_u32 {S_NSLOTS}, {S_NSLOTS}, {S_T2}
 	s_load_dwordx2 s[76:77], {S_KERNARG}, 0x20
@@ -1293,13 +1216,13 @@ class Tiles:
 	s_mul_i32 {S_T2}, {S_T0}, {S_T2}
 	s_add_u32 s80, s78, {S_T2}
 	s_addc_u32 s81, s79, {S_T3}
-	s_mul_i32 {S_T1}, {S_T0}, {SLOT_SIZE}
-	s_mul_hi_u32 {S_T0}, {S_T0}, {SLOT_SIZE}
+	s_mul_i32 {S_T1}, {S_T0}, {o['sizeof_slot']}
+	s_mul_hi_u32 {S_T0}, {S_T0}, {o['sizeof_slot']}
 	s_add_u32 s20, s14, {S_T1}
 	s_addc_u32 s21, s15, {S_T0}
 	s_load_dwordx4 s[24:27], {S_SLOT}, 0x0
-	s_load_dwordx2 {S_ACT}, {S_SLOT}, {SL_ACT}
-	s_load_dwordx2 {S_TV}, {S_SLOT}, 0x20
+	s_load_dwordx2 {S_ACT}, {S_SLOT}, {o['slot.act']}
+	s_load_dwordx2 {S_TV}, {S_SLOT}, {o['slot.tvals']:#x}
 	s_waitcnt lgkmcnt(0)
 	s_cmp_eq_u64 {S_ACT}, 0
 	s_cbranch_scc1 .Lfh_tiles_outer
@@ -1320,7 +1243,7 @@ class Tiles:
 	s_memrealtime s[56:57]
 	s_memtime s[62:63]""")
         for k, r in enumerate((VX[0], VX[1], VY[0], VY[1], VZ[0], VZ[1])):
-            a(f"\tglobal_load_dword {r}, {V_L4}, {S_SLOT} offset:{SL_XYZ + 256 * k}")
+            a(f"\tglobal_load_dword {r}, {V_L4}, {S_SLOT} offset:{o['slot.xyz'] + 256 * k}")
         a(f"""
 	s_waitcnt lgkmcnt(0)
 	s_mov_b32 s44, {S_OFF}
@@ -1334,11 +1257,9 @@ class Tiles:
 	v_mov_b32 {V_CW}, 0
 	v_mov_b32 {V_RESL}, {V_QNAN}
 	v_mov_b32 {V_RESH}, {V_QNAN}
-	s_waitcnt vmcnt(0)
-	s_getpc_b64 {S_RET}
-.Lfh_tiles_pc1:
-	s_add_u32 s74, s74, .Lfh_tiles_ret1 - .Lfh_tiles_pc1
-	s_addc_u32 s75, s75, 0
+	s_waitcnt vmcnt(0)""")
+        pcrel(a, S_RET, ".Lfh_tiles_ret1", ".Lfh_tiles_pc1")
+        a(f"""
 	s_branch .Lfh_tiles_run
 .Lfh_tiles_ret1:
 	s_memrealtime s[58:59]
@@ -1363,8 +1284,8 @@ class Tiles:
 	s_addc_u32 s83, s81, 0
 	global_store_dword {V_L4}, {V_CW}, {S_CHWTMP}
 .Lfh_tiles_noflush:
-	global_store_dword {V_L4}, {V_RESL}, {S_SLOT} offset:{SL_RES}
-	global_store_dword {V_L4}, {V_RESH}, {S_SLOT} offset:{SL_RES + 256}
+	global_store_dword {V_L4}, {V_RESL}, {S_SLOT} offset:{o['slot.res']}
+	global_store_dword {V_L4}, {V_RESH}, {S_SLOT} offset:{o['slot.res'] + 256}
 	s_bitcmp1_b32 {S_FLAGS}, 2                       ; forward pass only (tape groups: k_ttop3d goes on)
 	s_cbranch_scc1 .Lfh_tiles_outer
 	; ---- classify: ambiguous = act && !(hi < 0) && !(lo > 0); prune those whose trace decided --
@@ -1428,11 +1349,9 @@ class Tiles:
 	v_lshlrev_b64 v[46:47], 3, v[16:17]
 	v_mov_b32 {T[2]}, s11
 	v_add_co_u32 v46, vcc, s10, v46
-	v_addc_co_u32 v47, vcc, {T[2]}, v47, vcc
-	s_getpc_b64 {S_RET}
-.Lfh_tiles_pc2:
-	s_add_u32 s74, s74, .Lfh_tiles_ret2 - .Lfh_tiles_pc2
-	s_addc_u32 s75, s75, 0
+	v_addc_co_u32 v47, vcc, {T[2]}, v47, vcc""")
+        pcrel(a, S_RET, ".Lfh_tiles_ret2", ".Lfh_tiles_pc2")
+        a(f"""
 	s_cmp_le_u32 {S_NREGS}, 32
 	s_cbranch_scc1 .Lfh_tiles_prune1
 	s_branch .Lfh_tiles_prune4
@@ -1482,60 +1401,29 @@ class Tiles:
 	global_atomic_add_x2 {T[2]}, v[16:17], {S_STATE} offset:{o['stat'] + 8 * 16}
 	s_mov_b64 exec, {S_SAVE}
 .Lfh_tiles_noprobe:
-	global_store_dword {V_L4}, {V_COFF}, {S_SLOT} offset:{SL_COFF}
-	global_store_dword {V_L4}, {V_CLEN}, {S_SLOT} offset:{SL_CLEN}
-	global_store_dword {V_L4}, {V_CRC}, {S_SLOT} offset:{SL_CRC}
+	global_store_dword {V_L4}, {V_COFF}, {S_SLOT} offset:{o['slot.c_off']}
+	global_store_dword {V_L4}, {V_CLEN}, {S_SLOT} offset:{o['slot.c_len']}
+	global_store_dword {V_L4}, {V_CRC}, {S_SLOT} offset:{o['slot.c_rc']}
 	s_branch .Lfh_tiles_outer
 .Lfh_tiles_outer_drain:
 	s_waitcnt vmcnt(0)                              ; the per-lane interval loads of the skipped slot
 	s_branch .Lfh_tiles_outer
-.Lfh_tiles_exit:
-	s_endpgm
-.Lfh_tiles_end:
-	.size {name}, .Lfh_tiles_end - {name}
-	.rodata
-	.p2align 6
-	.amdhsa_kernel {name}
-		.amdhsa_group_segment_fixed_size 0
-		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size 40
-		.amdhsa_user_sgpr_count 2
-		.amdhsa_user_sgpr_kernarg_segment_ptr 1
-		.amdhsa_system_sgpr_workgroup_id_x 1
-		.amdhsa_system_sgpr_workgroup_id_y 0
-		.amdhsa_system_sgpr_workgroup_id_z 0
-		.amdhsa_system_vgpr_workitem_id 0
-		.amdhsa_next_free_vgpr {self.n_vgpr}
-		.amdhsa_next_free_sgpr 102
-		.amdhsa_accum_offset {(self.n_vgpr + 3) // 4 * 4}
-		.amdhsa_reserve_vcc 1
-		.amdhsa_float_round_mode_32 0
-		.amdhsa_float_round_mode_16_64 0
-		.amdhsa_float_denorm_mode_32 3
-		.amdhsa_float_denorm_mode_16_64 3
-		.amdhsa_dx10_clamp 1
-		.amdhsa_ieee_mode 1
-	.end_amdhsa_kernel
-	.text""")
+.Lfh_tiles_exit:""")
+        kernel.end(a)
         if self.trans:
-            import gen_trans
             gen_trans.embed(a, self.trans, v_base=self.t_base, prefix=self.t_prefix, s_map=T_SMAP)
         self.emit_forward()
         self.emit_prune(1)
         self.emit_prune(4)
+        return kernel
 
 
 def gen_tiles(a, off, trans=None):
     """fh_tiles, or with `trans` (the compiled routines' assembly) fh_tiles_t: the same kernel with handlers for the transcendental
     opcodes (generated into a scratch buffer, its labels and name renamed)"""
     if trans:
-        b = Asm()
-        b.uid = a.uid + 200000
-        t = Tiles(b, off, trans=trans)
-        t.emit_kernel()
-        a(b.text().replace(".Lfh_tiles_", ".Lfh_tiles_t_").replace("fh_tiles", "fh_tiles_t").replace("fh_tiles_t_t_", "fh_tiles_t_"))
-        a.uid = max(a.uid, b.uid)
-        return "fh_tiles_t", 40, t.n_vgpr, [(8, "global_buffer")] + [(4, "by_value")] * 8
-    t = Tiles(a, off)
-    t.emit_kernel()
-    return t.name, 40, N_VGPR, [(8, "global_buffer")] + [(4, "by_value")] * 8
+        k = renamed(a, lambda b: Tiles(b, off, trans=trans).emit_kernel(), 200000,
+                    [(".Lfh_tiles_", ".Lfh_tiles_t_"), ("fh_tiles", "fh_tiles_t"), ("fh_tiles_t_t_", "fh_tiles_t_")], keep_uid=True)
+        k.name = "fh_tiles_t"
+        return k
+    return Tiles(a, off).emit_kernel()

@@ -32,15 +32,15 @@ kernarg: as fh_tiles { FhRenderState* S; u32 level; u32 big; u32 max_regs; u32 m
          (skip_regs, skip_choices) are left to another launch; flags: bit 0 probes, bit 4 both lists, bit 1 (+ bits 31:16) export of
          the choices of parents that carry links (see the kernel body); the other modes of fh_tiles do not exist here.
 """
-from gen_interp import OPS, UNSUPPORTED, HSTRIDE_LOG2
-import gen_tiles as GT
-from gen_tiles import (Tiles, S_KERNARG, S_STATE, S_LEVEL, S_BIG, S_MAXREGS, S_MAXCH, S_ARENA, S_ARENACAP, S_SLOTS, S_NSLOTS, S_SLOT, S_OFF,
-                       S_LEN, S_RC, S_ACT, S_SIGN, S_ABSM, S_DECIDED, S_CI, S_NREGS, S_NCH, S_PRUNE, S_BASE, S_MA, S_MB, S_HBASE, S_TAPE,
-                       S_REM, S_K, S_W0, S_W1, S_T0, S_OUT, S_A, S_T1, S_OP, S_RET, S_T64, S_LIVE, S_ALIAS, S_CIMM, S_KEEP, S_PC, S_SAVE,
-                       S_M, S_T2, S_T3, S_SKIPR, S_SKIPC, S_SI, S_NWG, V_LANE, V_L4, VX, VY, VZ, AL, AH, BL, BH, RL, RH, T, V_CW, V_C,
-                       V_RESL, V_RESH, V_QNAN, V_SQRTC, V_ONE, SLOT_SIZE, SL_ACT, SL_XYZ, SL_RES, SL_COFF, SL_CLEN, SL_CRC, TRANS_UNARY, T_SMAP)
-
-SRC0, SRC1, SRC2, DST = 1, 2, 4, 8
+import gen_trans
+from gen_asm import (pcrel, add_rel, SRC0, SRC1, SRC2, DST, S_KERNARG, S_STATE, S_SIGN, S_ABSM, S_HBASE, S_TAPE, S_W0, S_W1, S_T0, S_OUT, S_A,
+                     S_T1, S_RET, S_SAVE, S_M, V_LANE)
+from gen_interp import OPS, UNSUPPORTED
+from gen_tiles import (Tiles, S_LEVEL, S_BIG, S_MAXREGS, S_MAXCH, S_ARENA, S_ARENACAP, S_SLOTS, S_NSLOTS, S_SLOT, S_OFF,
+                       S_LEN, S_RC, S_ACT, S_DECIDED, S_CI, S_NREGS, S_NCH, S_PRUNE, S_BASE, S_MA, S_MB,
+                       S_REM, S_K, S_OP, S_T64, S_LIVE, S_ALIAS, S_CIMM, S_KEEP,
+                       S_T2, S_T3, S_SKIPR, S_SKIPC, S_SI, S_NWG, V_L4, VX, VY, VZ, AL, AH, BL, BH, RL, RH, T, V_C,
+                       V_RESL, V_RESH, V_QNAN, V_SQRTC, V_ONE, TRANS_UNARY, T_SMAP)
 
 # ---- SGPRs beyond those shared with gen_tiles ----------------------------------------------------
 S_CB = "s[48:49]"          # address of the tape chunk being fetched
@@ -704,14 +704,10 @@ class TilesV(Tiles):
 
     # ---- kernel ----------------------------------------------------------------------------------------------
     def emit_kernel(self):
-        a, o, p, name = self.a, self.off, self.p, self.name
+        a, o, p = self.a, self.off, self.p
+        kernel = self.kernel()
+        kernel.begin(a)
         a(f"""
-	.text
-	.protected {name}
-	.globl {name}
-	.p2align 8
-	.type {name},@function
-{name}:
 	s_load_dwordx2 {S_STATE}, {S_KERNARG}, 0x0
 	s_load_dwordx4 s[8:11], {S_KERNARG}, 0x8
 	s_load_dwordx2 s[100:101], {S_KERNARG}, 0x18
@@ -771,13 +767,10 @@ class TilesV(Tiles):
 	s_addc_u32 s77, s5, 0
 	s_load_dword {S_NSLOTS}, {S_T64}, {o['n_slots']}
 	s_load_dwordx2 {S_ARENA}, {S_STATE}, {o['arena']}
-	s_load_dword {S_ARENACAP}, {S_STATE}, {o['arena_cap']}
-	s_getpc_b64 {S_HBASE}
-{p}_pc0:
-	s_add_u32 s52, s42, {p}_classes - {p}_pc0
-	s_addc_u32 s53, s43, 0
-	s_add_u32 s42, s42, {p}_handlers - {p}_pc0
-	s_addc_u32 s43, s43, 0
+	s_load_dword {S_ARENACAP}, {S_STATE}, {o['arena_cap']}""")
+        pcrel(a, S_HBASE, f"{p}_classes", f"{p}_pc0", dst=S_PBASE)
+        add_rel(a, S_HBASE, S_HBASE, f"{p}_handlers", f"{p}_pc0")
+        a(f"""
 	s_mov_b32 s55, s43
 	s_waitcnt lgkmcnt(0)
 	s_min_u32 {S_NSLOTS}, {S_NSLOTS}, {S_T2}
@@ -791,12 +784,12 @@ class TilesV(Tiles):
 	s_cbranch_scc1 {p}_exit
 	s_mov_b32 {S_T0}, {S_SI}
 	s_add_u32 {S_SI}, {S_SI}, {S_NWG}
-	s_mul_i32 {S_T1}, {S_T0}, {SLOT_SIZE}
-	s_mul_hi_u32 {S_T0}, {S_T0}, {SLOT_SIZE}
+	s_mul_i32 {S_T1}, {S_T0}, {o['sizeof_slot']}
+	s_mul_hi_u32 {S_T0}, {S_T0}, {o['sizeof_slot']}
 	s_add_u32 s20, s14, {S_T1}
 	s_addc_u32 s21, s15, {S_T0}
 	s_load_dwordx4 s[24:27], {S_SLOT}, 0x0
-	s_load_dwordx2 {S_ACT}, {S_SLOT}, {SL_ACT}
+	s_load_dwordx2 {S_ACT}, {S_SLOT}, {o['slot.act']}
 	s_waitcnt lgkmcnt(0)
 	s_cmp_eq_u64 {S_ACT}, 0
 	s_cbranch_scc1 {p}_outer
@@ -816,7 +809,7 @@ class TilesV(Tiles):
 	s_cbranch_scc1 {p}_outer
 	s_memtime s[60:61]""")
         for k, r in enumerate((VX[0], VX[1], VY[0], VY[1], VZ[0], VZ[1])):
-            a(f"\tglobal_load_dword {r}, {V_L4}, {S_SLOT} offset:{SL_XYZ + 256 * k}")
+            a(f"\tglobal_load_dword {r}, {V_L4}, {S_SLOT} offset:{o['slot.xyz'] + 256 * k}")
         a(f"""
 	s_mov_b32 s44, {S_OFF}
 	s_mov_b32 s45, 0
@@ -826,16 +819,14 @@ class TilesV(Tiles):
 	s_mov_b32 {S_CI}, 0
 	s_mov_b64 {S_DECIDED}, 0
 """ + "".join(f"\tv_mov_b32 v{self.CHF + w}, 0\n" for w in range(self.ncw)) + f"""	v_mov_b32 {V_RESL}, {V_QNAN}
-	v_mov_b32 {V_RESH}, {V_QNAN}
-	s_getpc_b64 {S_RET}
-{p}_pc1:
-	s_add_u32 s74, s74, {p}_ret1 - {p}_pc1
-	s_addc_u32 s75, s75, 0
+	v_mov_b32 {V_RESH}, {V_QNAN}""")
+        pcrel(a, S_RET, f"{p}_ret1", f"{p}_pc1")
+        a(f"""
 	s_branch {p}_run
 {p}_ret1:
 	s_memtime s[62:63]
-	global_store_dword {V_L4}, {V_RESL}, {S_SLOT} offset:{SL_RES}
-	global_store_dword {V_L4}, {V_RESH}, {S_SLOT} offset:{SL_RES + 256}
+	global_store_dword {V_L4}, {V_RESL}, {S_SLOT} offset:{o['slot.res']}
+	global_store_dword {V_L4}, {V_RESH}, {S_SLOT} offset:{o['slot.res'] + 256}
 	; ---- classify: ambiguous = act && !(hi < 0) && !(lo > 0); prune those whose trace decided something ------------
 	v_cmp_gt_f32_e64 {S_M[0]}, 0, {V_RESH}
 	v_cmp_gt_f32_e64 {S_M[1]}, {V_RESL}, 0
@@ -924,11 +915,9 @@ class TilesV(Tiles):
 	v_mov_b32 {T[2]}, s11
 	v_add_co_u32 v20, vcc, s10, v20
 	s_nop 1
-	v_addc_co_u32 v21, vcc, {T[2]}, v21, vcc
-	s_getpc_b64 {S_RET}
-{p}_pc2:
-	s_add_u32 s74, s74, {p}_ret2 - {p}_pc2
-	s_addc_u32 s75, s75, 0
+	v_addc_co_u32 v21, vcc, {T[2]}, v21, vcc""")
+        pcrel(a, S_RET, f"{p}_ret2", f"{p}_pc2")
+        a(f"""
 	s_branch {p}_prune
 {p}_ret2:
 	s_mov_b64 exec, -1
@@ -983,9 +972,9 @@ class TilesV(Tiles):
 	global_atomic_add_x2 {T[2]}, v[16:17], {S_STATE} offset:{o['stat'] + 8 * 8}
 	s_mov_b64 exec, {S_SAVE}
 {p}_noprobe:
-	global_store_dword {V_L4}, {V_COFF}, {S_SLOT} offset:{SL_COFF}
-	global_store_dword {V_L4}, {V_CLEN}, {S_SLOT} offset:{SL_CLEN}
-	global_store_dword {V_L4}, {V_CRC}, {S_SLOT} offset:{SL_CRC}
+	global_store_dword {V_L4}, {V_COFF}, {S_SLOT} offset:{o['slot.c_off']}
+	global_store_dword {V_L4}, {V_CLEN}, {S_SLOT} offset:{o['slot.c_len']}
+	global_store_dword {V_L4}, {V_CRC}, {S_SLOT} offset:{o['slot.c_rc']}
 	s_branch {p}_outer
 {p}_exit:
 	s_bitcmp1_b32 s70, 0
@@ -997,42 +986,14 @@ class TilesV(Tiles):
 	s_lshr_b32 {S_LEVEL}, s70, 8
 	s_mov_b32 {S_SI}, s86
 	s_branch {p}_list
-{p}_quit:
-	s_endpgm
-{p}_end:
-	.size {name}, {p}_end - {name}
-	.rodata
-	.p2align 6
-	.amdhsa_kernel {name}
-		.amdhsa_group_segment_fixed_size 0
-		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size 40
-		.amdhsa_user_sgpr_count 2
-		.amdhsa_user_sgpr_kernarg_segment_ptr 1
-		.amdhsa_system_sgpr_workgroup_id_x 1
-		.amdhsa_system_sgpr_workgroup_id_y 0
-		.amdhsa_system_sgpr_workgroup_id_z 0
-		.amdhsa_system_vgpr_workitem_id 0
-		.amdhsa_next_free_vgpr {self.n_vgpr}
-		.amdhsa_next_free_sgpr 102
-		.amdhsa_accum_offset {(self.n_vgpr + 3) // 4 * 4}
-		.amdhsa_reserve_vcc 1
-		.amdhsa_float_round_mode_32 0
-		.amdhsa_float_round_mode_16_64 0
-		.amdhsa_float_denorm_mode_32 3
-		.amdhsa_float_denorm_mode_16_64 3
-		.amdhsa_dx10_clamp 1
-		.amdhsa_ieee_mode 1
-	.end_amdhsa_kernel
-	.text""")
+{p}_quit:""")
+        kernel.end(a)
         if self.trans:
-            import gen_trans
             gen_trans.embed(a, self.trans, v_base=self.t_base, prefix=self.t_prefix, s_map=T_SMAP)
         self.emit_forward()
         self.emit_prune()
+        return kernel
 
 
 def gen_tilesv(a, off, nr, ncw, trans=None):
-    t = TilesV(a, off, nr, ncw, trans=trans)
-    t.emit_kernel()
-    return t.name, 40, t.n_vgpr, [(8, "global_buffer")] + [(4, "by_value")] * 8
+    return TilesV(a, off, nr, ncw, trans=trans).emit_kernel()

@@ -8,6 +8,8 @@ The routines' tables (trans_libm.hpp MemTables: 2^(i/32), logf's 1/c and log c, 
 .rodata: `tables()` emits them once per code object under the names the renamed code refers to."""
 import re
 
+from gen_asm import pcrel
+
 V_BASE, S_BASE, S_RET = 128, 86, 96
 FUNCS = ["sin", "cos", "tan", "asin", "acos", "atan", "exp", "ln", "atan2", "mod"]
 FUNCS4 = ["sin4", "cos4", "exp4", "ln4"]     # four samples per call (v0..v3 in and out): embedded with a window of WIDE_V registers
@@ -121,13 +123,8 @@ def exp_table_init(a, v_base, prefix="fh_t_", lane="v0"):
     """loads the table registers of the hand-written expf and logf (once per wave; clobbers s86..s89; `lane` = the lane's number)"""
     here = a.label("exptab")
     lo, hi = v_base + EXP_TAB, v_base + EXP_TAB + 1
+    pcrel(a, "s[86:87]", f"{prefix}exp2_tab", here, far="s[88:89]")
     a(f"""
-	s_getpc_b64 s[86:87]
-{here}:
-	s_mov_b32 s88, {prefix}exp2_tab - {here}
-	s_ashr_i32 s89, s88, 31
-	s_add_u32 s86, s86, s88
-	s_addc_u32 s87, s87, s89
 	v_and_b32 v{lo}, 31, {lane}
 	v_lshlrev_b32 v{lo}, 3, v{lo}
 	global_load_dwordx2 v[{lo}:{hi}], v{lo}, s[86:87]
@@ -446,18 +443,16 @@ def hand(fn):
     return sincos_consts, sincos_special, (lambda a, vb, xin, xout, c=(fn == "cos"): sincos_pair(a, vb, xin, xout, c))
 
 
-COPIES = []      # (prefix, v_base, routine names) of every embed(): the probe kernel (gen_interp.py gen_trans_probe) reaches each copy
-
-
 def embed(a, path, v_base=V_BASE, prefix="fh_t_", s_map=None, wide=False, exp2=None, sincos2=False):
     """the routines as `<prefix><name>` with their vector registers in v[v_base .. v_base + 25] (a second kernel with another register
     window embeds its own copies: `s_branch` reaches 128 KB); s_map: the ten scalar registers s0..s9 go to (default s86..s95; pairs
     must stay even-aligned pairs), the return address always to s[96:97]; wide: also the four-sample routines FUNCS4, and a window of
-    WIDE_V registers"""
+    WIDE_V registers.  Every copy is listed in a.copies as (prefix, v_base, routine names): the probe kernel (gen_interp.py
+    gen_trans_probe) reaches each of them."""
     txt = open(path).read()
     # wide = True: all of FUNCS4 in a window of WIDE_V registers; "sincos": sin4 / cos4 only, which fit the ordinary window of MAX_V
     extra = FUNCS4 if wide is True else (["sin4", "cos4"] if wide == "sincos" else [])
-    COPIES.append((prefix, v_base, FUNCS + extra + (["sin2", "cos2", "exp2", "ln2"] if exp2 else (["sin2", "cos2"] if sincos2 else []))))
+    a.copies.append((prefix, v_base, FUNCS + extra + (["sin2", "cos2", "exp2", "ln2"] if exp2 else (["sin2", "cos2"] if sincos2 else []))))
     if exp2:       # the kernel's handlers hold the two-sample expf written by hand (exp_pair): its table
         exp_table(a, prefix)
     for f in FUNCS + extra:

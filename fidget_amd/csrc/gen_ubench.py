@@ -4,6 +4,7 @@ kernarg { float* out; u32 test; u32 iters }.  Every wave runs `iters` times a bo
 `test` between two s_memtime and stores (clocks / (iters * 32)) as f32 at out[workgroup].  128 VGPRs are allocated so that
 at most 4 waves share a SIMD, as in fh_tiles_v32 / fh_columns.
 """
+from gen_asm import Kernel, PTR, U32
 
 TESTS = [
     ("v_mov independent", lambda k: f"\tv_mov_b32 v{10 + k % 16}, v{40 + k % 8}"),
@@ -70,14 +71,9 @@ TESTS = [
 
 
 def gen_ubench(a):
-    name = "fh_ubench"
+    kernel = Kernel("fh_ubench", [PTR, U32, U32], 128, sgprs=64, lds=64)
+    kernel.begin(a)
     a(f"""
-	.text
-	.protected {name}
-	.globl {name}
-	.p2align 8
-	.type {name},@function
-{name}:
 	s_load_dwordx2 s[4:5], s[0:1], 0x0
 	s_load_dwordx2 s[6:7], s[0:1], 0x8
 """ + "".join(f"\tv_mov_b32 v{r}, 1.0\n" for r in range(10, 40)) + f"""	v_mov_b32 v40, 1.0
@@ -137,32 +133,6 @@ def gen_ubench(a):
 	v_cmp_eq_u32 vcc, 0, v0
 	s_and_saveexec_b64 s[16:17], vcc
 	global_store_dword v4, v1, s[4:5]
-.Lub_exit:
-	s_endpgm
-.L{name}_end:
-	.size {name}, .L{name}_end - {name}
-	.rodata
-	.p2align 6
-	.amdhsa_kernel {name}
-		.amdhsa_group_segment_fixed_size 64
-		.amdhsa_private_segment_fixed_size 0
-		.amdhsa_kernarg_size 16
-		.amdhsa_user_sgpr_count 2
-		.amdhsa_user_sgpr_kernarg_segment_ptr 1
-		.amdhsa_system_sgpr_workgroup_id_x 1
-		.amdhsa_system_sgpr_workgroup_id_y 0
-		.amdhsa_system_sgpr_workgroup_id_z 0
-		.amdhsa_system_vgpr_workitem_id 0
-		.amdhsa_next_free_vgpr 128
-		.amdhsa_next_free_sgpr 64
-		.amdhsa_accum_offset 128
-		.amdhsa_reserve_vcc 1
-		.amdhsa_float_round_mode_32 0
-		.amdhsa_float_round_mode_16_64 0
-		.amdhsa_float_denorm_mode_32 3
-		.amdhsa_float_denorm_mode_16_64 3
-		.amdhsa_dx10_clamp 1
-		.amdhsa_ieee_mode 1
-	.end_amdhsa_kernel
-	.text""")
-    return name, 16, 128, [(8, "global_buffer"), (4, "by_value"), (4, "by_value")]
+.Lub_exit:""")
+    kernel.end(a)
+    return kernel

@@ -1,5 +1,5 @@
-// Prints the byte offsets of the FhRenderState fields used by the assembly kernels
-// (gen_interp.py); host and device layouts are identical (plain C, 64-bit pointers).
+// Prints the byte offsets of the FhRenderState and FhSlot fields used by the assembly kernels
+// (gen_interp.py and the generators it drives); host and device layouts are identical (plain C, 64-bit pointers).
 #include <cstddef>
 #include <cstdio>
 
@@ -16,6 +16,8 @@ int main() {
     O("fp_list", fp_list); O("fp_count", fp_count); O("fp_cursor", fp_cursor); O("hit_list", hit_list); O("stat", stat);
     O("count", count); O("count_big", count_big); O("queue", queue); O("qcap", qcap); O("squeue", squeue); O("n_leaves", n_leaves);
     O("leaf_cap", leaf_cap); O("P.depth", P.depth); O("P.n_levels", P.n_levels); O("P.max_regs", P.max_regs);
+#define SL(field) printf(", \"slot.%s\": %zu", #field, (size_t)offsetof(FhSlot, field))
+    SL(act); SL(tvals); SL(xyz); SL(corner); SL(res); SL(c_off); SL(c_len); SL(c_rc);
     printf(", \"sizeof_state\": %zu, \"sizeof_slot\": %zu, \"sizeof_group\": %zu, \"sizeof_leaf\": %zu", sizeof(FhRenderState), sizeof(FhSlot),
            sizeof(FhGroup), sizeof(FhLeaf));
     printf("}\n");

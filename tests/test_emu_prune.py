@@ -11,7 +11,7 @@ from conftest import model_path
 from test_emu_tiles import children, shape_of
 
 ARENA_OPS = 1 << 17
-COFF, CLEN, CRC = 40 + 11 * 256, 40 + 12 * 256, 40 + 13 * 256      # FhSlot: c_off[64], c_len[64], c_rc[64] (gen_tiles SL_*)
+COFF, CLEN, CRC = 40 + 11 * 256, 40 + 12 * 256, 40 + 13 * 256      # FhSlot: c_off[64], c_len[64], c_rc[64] (written out here; the generators take theirs from offsets.json)
 
 
 def run_prune1(tape, choices, marked, n_regs, level=1, big=0, mode=1):

@@ -66,7 +66,7 @@ def test_transcendental_bits_equal_libm(op, oracle_mod):
     assert worst["differ"] == 0, f"{op}: {worst}"
 
 
-# the copies of the compiled routines inside the assembly kernels (gen_trans.COPIES, in the order gen_interp.py's main() embeds them)
+# the copies of the compiled routines inside the assembly kernels (the run's list gen_trans.embed keeps - Asm.copies, gen_asm.py -, in the order of gen_interp.py generate()'s kernel table)
 # and the routines each holds (gen_trans.FUNCS + FUNCS4).  fh_columns_t: the one-sample routines, and under the four-sample routines'
 # numbers the two-sample sinf, cosf, expf and logf written by hand that its SIN / COS / EXP / LN handlers hold (gen_trans.sincos_pair,
 # exp_pair, ln_pair: the probe runs them on the four arguments); the bulk kernels: sinf and cosf that way

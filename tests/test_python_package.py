@@ -33,7 +33,7 @@ PUBLIC = [
     "_Cfg2D", "_Cfg3D", "_SOURCES", "_p",
 ]
 
-UNINCLUDED = ("gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py",
+UNINCLUDED = ("gen_asm.py", "gen_interp.py", "gen_tiles.py", "gen_tilesv.py", "gen_normals.py", "gen_prune.py", "gen_ubench.py", "gen_trans.py",
               "offsets.cpp", "trans_funcs.hip")
 
 
