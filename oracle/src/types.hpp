@@ -64,9 +64,11 @@ static inline uint32_t rng_mix(uint32_t a, uint32_t b) {
 
 // ---------------------------------------------------------------------------
 // Rust std f32 helpers
-// f32::min / f32::max: IEEE minNum / maxNum (NaN-ignoring)
-static inline float rmin(float a, float b) { return fminf(a, b); }
-static inline float rmax(float a, float b) { return fmaxf(a, b); }
+// f32::min / f32::max: IEEE minNum / maxNum (NaN-ignoring).  Of +0 and -0 the reference leaves open which comes back ("either input may
+// be returned", core::f32: x86-64 gives one operand, aarch64 the ordered one) and so does libm's fminf; here -0 < +0, IEEE 754-2019
+// minimumNumber / maximumNumber: independent of the operands' order, and what v_min_f32 / v_max_f32 compute on the device.
+static inline float rmin(float a, float b) { return a == b ? (std::signbit(a) ? a : b) : fminf(a, b); }
+static inline float rmax(float a, float b) { return a == b ? (std::signbit(a) ? b : a) : fmaxf(a, b); }
 // f32::rem_euclid (core::f32): r = self % rhs; if r < 0 { r + rhs.abs() }
 static inline float rem_euclid(float a, float b) {
     float r = fmodf(a, b);

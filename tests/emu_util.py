@@ -233,11 +233,14 @@ def ref_f32(tape, inputs, n):
 
 # ---- intervals -----------------------------------------------------------------------------------
 def _rmin(a, b):
-    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.minimum(a, b))).astype(F32)
+    """dev_ops.hpp rmin: a NaN operand is ignored; of +0 and -0 the smaller is -0 (oracle/src/types.hpp rmin)"""
+    tie = np.where(np.signbit(a), a, b)
+    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.where(a == b, tie, np.minimum(a, b)))).astype(F32)
 
 
 def _rmax(a, b):
-    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.maximum(a, b))).astype(F32)
+    tie = np.where(np.signbit(a), b, a)
+    return np.where(np.isnan(a), b, np.where(np.isnan(b), a, np.where(a == b, tie, np.maximum(a, b)))).astype(F32)
 
 
 def _nan(lo, hi):
