@@ -188,6 +188,15 @@ SIGNATURES = {
     "fhip_outlines_next_dev": (vp, [vp]),
     "fhip_outlines_loop_dev": (vp, [vp]),
     "fhip_outlines_free": (None, [vp]),
+    # ---- the nesting of those outlines: left links, parents, depths, regions
+    "fhip_outlines_nesting": (i32, [vp, vp, vp, i32, vp]),
+    "fhip_nesting_counts": (None, [vp, vp]),
+    "fhip_nesting_layers": (i32, [vp, vp, vp, vp]),
+    "fhip_nesting_loops": (i32, [vp, u64, u64, vp, vp, vp, vp, vp]),
+    "fhip_nesting_parent_dev": (vp, [vp]),
+    "fhip_nesting_depth_dev": (vp, [vp]),
+    "fhip_nesting_children": (i32, [vp, u64, vp, vp]),
+    "fhip_nesting_free": (None, [vp]),
     # ---- the slices of a triangle mesh: closed contour loops per plane z = const
     "fhip_topology_slices": (i32, [vp, vp, vp, u32, u32, vp]),
     "fhip_slices_counts": (None, [vp, vp]),

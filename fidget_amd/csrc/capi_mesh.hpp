@@ -1375,5 +1375,7 @@ fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const f
 #include "capi_topo.hpp"
 // the outlines of a voxel bitmap's layers (fhip_voxels_outlines)
 #include "capi_outline.hpp"
+// the nesting of those outlines (fhip_outlines_nesting): after capi_outline.hpp, whose fhip_outlines it reads
+#include "capi_nest.hpp"
 // the slices of a triangle mesh (fhip_topology_slices): after capi_topo.hpp, whose fhip_topology it cuts
 #include "capi_slice.hpp"

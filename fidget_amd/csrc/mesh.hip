@@ -1261,5 +1261,7 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 #include "topo.hip"
 // k_ol_*: the outlines of such a bitmap's layers - vertices, successors, loops (fhip_voxels_outlines) - its own file
 #include "outline.hip"
+// k_on_*: the nesting of those outlines - left links, parents, depths, regions (fhip_outlines_nesting) - its own file, after outline.hip
+#include "nest.hip"
 // k_ms_*: the slices of a triangle mesh - crossings, segments, loops per plane (fhip_topology_slices) - its own file, after topo.hip
 #include "slice.hip"

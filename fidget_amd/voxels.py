@@ -1,4 +1,4 @@
-"""The voxel family: `voxelize` and its `Voxels` bitmap, and what is made of one - `Outlines`, `Surface`, `DistanceField`,
+"""The voxel family: `voxelize` and its `Voxels` bitmap, and what is made of one - `Outlines` and their `Nesting`, `Surface`, `DistanceField`,
 `ThicknessField`, `Components`."""
 import ctypes as C
 import math
@@ -244,7 +244,7 @@ class Voxels:
         the bricks are; the vertices' arrays stay in device memory.  Integers throughout: the same bits from run to run."""
         h = C.c_void_p()
         self._hip.check(lib().fhip_voxels_outlines(self._hip._h, self._ptr(), self.depth, int(self.on_device), int(k0), int(k1), int(connectivity), C.byref(h)))
-        return Outlines(_Handle(h.value, lib().fhip_outlines_free), self._hip)
+        return Outlines(_Handle(h.value, lib().fhip_outlines_free), self._hip, self)
 
     def outline(self, k, connectivity=4):
         """the loops of the one layer k: `outlines(k, k + 1)`"""
@@ -261,10 +261,11 @@ class Outlines:
     boundary edges.  Per vertex: `.xy()` uint16 [n, 2] the corner (a, b); `.next()` uint32 [n] the next vertex along the loop, a
     permutation inside each layer; `.loop_of()` uint32 [n].  Per loop (`.table()`): leader - its smallest vertex id; loops are numbered
     by ascending leader - n_vertices, area2 (int64 shoelace sum: > 0 an outer boundary, < 0 a hole), perimeter, lo and hi [., 2].
-    The vertices' arrays stay in device memory (`.xy_device()` ...); host copies are made when first asked for."""
+    The vertices' arrays stay in device memory (`.xy_device()` ...); host copies are made when first asked for.  `.voxels`: the
+    bitmap that was outlined, which `nesting()` reads again."""
 
-    def __init__(self, owner, hip):
-        self._owner, self._hip = owner, hip
+    def __init__(self, owner, hip, voxels=None):
+        self._owner, self._hip, self.voxels = owner, hip, voxels
         c = np.zeros(8, np.uint64)
         lib().fhip_outlines_counts(owner.h, _p(c))
         self.n_vertices, self.n_loops, self.n_layers, self.grid, self.k0, self.connectivity = (int(v) for v in c[:6])
@@ -366,9 +367,113 @@ class Outlines:
         """... and `.loop_of()` ("<i4")"""
         return self._device("loop", (self.n_vertices,), "<i4")
 
+    def nesting(self):
+        """fhip_outlines_nesting: which hole belongs to which outer boundary and which island lies in which hole -> Nesting.  One
+        blocking call on the device, over this result's arrays and the bitmap that was outlined (`.voxels`, which must not have
+        changed since)."""
+        if self.voxels is None:
+            raise ValueError("these outlines do not know their bitmap")
+        v = self.voxels
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_outlines_nesting(self._hip._h, self._owner.h, v._ptr(), int(v.on_device), C.byref(h)))
+        return Nesting(self, _Handle(h.value, lib().fhip_nesting_free))
+
     def __repr__(self):
         return (f"Outlines(grid={self.grid}, layers={self.k0}..{self.k1}, connectivity={self.connectivity}, vertices={self.n_vertices}, "
                 f"loops={self.n_loops})")
+
+
+class Nesting:
+    """The containment tree of the loops of an `Outlines` (`Outlines.nesting()`), per layer.  `.outlines`; `.n_loops`, `.n_outer` (loops
+    with area2 > 0), `.n_top` (loops without a parent), `.max_depth`; per layer (index k - k0) `.outer`, `.top` uint64 [K] and
+    `.layer_max_depth` uint32 [K].  Per loop, uint32 [n_loops] with global ids and `NONE` = 0xFFFFFFFF for none, copied when first asked
+    for: `.left` - the loop that owns the nearest boundary edge left of the loop's leader on the leader's pixel row; `.parent` - the
+    first loop of the chain left, left[left], ... whose area2 has the other sign: a hole's outer boundary, an island's hole; `.depth`
+    - 0 without a parent, even exactly for outer boundaries; `.n_children`; and `.region_area2` int64 - area2 of the loop and of its
+    children: for an outer boundary twice the set pixels of one connected part of the layer.  parent and depth also stay in device
+    memory (`.parent_device()`, `.depth_device()`)."""
+    NONE = 0xFFFFFFFF
+
+    def __init__(self, outlines, owner):
+        self.outlines, self._owner, self._hip = outlines, owner, outlines._hip
+        c = np.zeros(8, np.uint64)
+        lib().fhip_nesting_counts(owner.h, _p(c))
+        self.n_loops, self.n_outer, self.n_top, self.max_depth, self.n_layers, self.k0, self.connectivity = (int(v) for v in c[:7])
+        self.k1 = self.k0 + self.n_layers
+        K = self.n_layers
+        self.outer, self.top, self.layer_max_depth = np.zeros(K, np.uint64), np.zeros(K, np.uint64), np.zeros(K, np.uint32)
+        self._hip.check(lib().fhip_nesting_layers(owner.h, _p(self.outer), _p(self.top), _p(self.layer_max_depth)))
+        self._loops = None
+        self._children = None
+
+    def _table(self):
+        if self._loops is None:
+            n = self.n_loops
+            t = {key: np.zeros(n, np.int64 if key == "region_area2" else np.uint32) for key in ("left", "parent", "depth", "n_children", "region_area2")}
+            self._hip.check(lib().fhip_nesting_loops(self._owner.h, 0, n, *(_p(a) for a in t.values())))
+            self._loops = t
+        return self._loops
+
+    left = property(lambda self: self._table()["left"])
+    parent = property(lambda self: self._table()["parent"])
+    depth = property(lambda self: self._table()["depth"])
+    n_children = property(lambda self: self._table()["n_children"])
+    region_area2 = property(lambda self: self._table()["region_area2"])
+
+    def children(self):
+        """fhip_nesting_children -> (child_start uint64 [n_loops + 1], children uint32): the children of loop l, ascending, are
+        children[child_start[l]:child_start[l + 1]]; loops without a parent are in no list"""
+        if self._children is None:
+            n = self.n_loops
+            start, kids = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32)
+            self._hip.check(lib().fhip_nesting_children(_p(self.parent), n, _p(start), _p(kids)))
+            self._children = (start, kids[:int(start[n])])
+        return self._children
+
+    def regions(self, k):
+        """layer k's polygons with holes as [(outer loop id, [hole ids])]: every outer boundary of the layer, ascending, with its
+        children; ids are global, and every loop of the layer is in exactly one region"""
+        lo, hi = self.outlines._layer(k, self.outlines.loop_start)
+        area2 = self.outlines.table()["area2"]
+        start, kids = self.children()
+        return [(l, [int(c) for c in kids[int(start[l]):int(start[l + 1])]]) for l in range(lo, hi) if area2[l] > 0]
+
+    def polygons(self, k):
+        """the same regions as [(outer int [m, 2], [holes int [m, 2]])], the loops of `Outlines.polygons(k)`"""
+        lo, _ = self.outlines._layer(k, self.outlines.loop_start)
+        polys = self.outlines.polygons(k)
+        return [(polys[l - lo], [polys[c - lo] for c in holes]) for l, holes in self.regions(k)]
+
+    def svg(self, k, path=None):
+        """Layer k as one <path fill-rule="evenodd"> per region, the outer boundary and its holes as its subpaths `M x y L x y ... Z`:
+        holes render empty and islands as regions of their own.  Coordinates as in `Outlines.svg`.  Returns the text; written to
+        `path` when given."""
+        lo, _ = self.outlines._layer(k, self.outlines.loop_start)
+        world, _ = self.outlines.world(k)
+        sub = lambda p: "M " + " L ".join(f"{float(x):.9g} {-float(y):.9g}" for x, y in p) + " Z"          # noqa: E731
+        paths = "".join('<path fill-rule="evenodd" d="' + " ".join(sub(world[q - lo]) for q in [l] + holes) + '"/>\n' for l, holes in self.regions(k))
+        text = f'<svg xmlns="http://www.w3.org/2000/svg" viewBox="-1 -1 2 2">\n{paths}</svg>\n'
+        if path is not None:
+            with open(path, "w") as f:
+                f.write(text)
+        return text
+
+    def _device(self, what):
+        ptr = getattr(lib(), f"fhip_nesting_{what}_dev")(self._owner.h)
+        return _DeviceArray(self._owner, ptr, (self.n_loops,), "<i4") if ptr else None
+
+    def parent_device(self):
+        """`.parent` where it is in device memory ([n_loops] "<i4": the bits of the uint32 ids, NONE as -1) as an object carrying
+        `__cuda_array_interface__` that keeps the result alive; None when there are no loops"""
+        return self._device("parent")
+
+    def depth_device(self):
+        """... and `.depth` ("<i4")"""
+        return self._device("depth")
+
+    def __repr__(self):
+        return (f"Nesting(layers={self.k0}..{self.k1}, connectivity={self.connectivity}, loops={self.n_loops}, outer={self.n_outer}, top={self.n_top}, "
+                f"max_depth={self.max_depth})")
 
 
 class Surface:

@@ -727,6 +727,52 @@ const uint32_t* fhip_outlines_next_dev(const void* outlines);
 const uint32_t* fhip_outlines_loop_dev(const void* outlines);
 void fhip_outlines_free(void* outlines);
 
+/* ---- the nesting of those outlines: which hole belongs to which outer boundary, which island lies in which hole -----
+ * (No counterpart in the reference.  The definitions below are the specification, exact and in integers, and the result is the same
+ * from run to run.)  Take a result of fhip_voxels_outlines (layers k0 <= k < k1, connectivity 4 or 8) and the bitmap it was made
+ * from.  For loop l of layer k let (a0, b0) be the corner of its leader and P the layer image, clear outside the grid.
+ * THE LEADER.  The unit boundary edge (a0, b0)-(a0, b0 + 1) belongs to l.  If area2[l] > 0, pixel (a0, b0) is set; if area2[l] < 0,
+ * pixel (a0, b0) is clear and pixel (a0 - 1, b0) is set.  area2 is never 0.
+ * LEFT.  Take the largest a < a0 with P(a - 1, b0) != P(a, b0); a = 0 compares the clear outside with P(0, b0).  left[l] is the loop
+ * that owns the unit boundary edge (a, b0)-(a, b0 + 1); without such an a, left[l] is NONE = 0xFFFFFFFF.  left[l] lies in the same
+ * layer, and left[l] < l.
+ * PARENT.  parent[l] is the first loop in the chain left[l], left[left[l]], ... whose area2 has the opposite sign to l's, NONE if the
+ * chain ends first.  parent[l] < l.  A loop without a parent is an outer boundary; a parent's sign is opposite to its child's.
+ * Equivalently: a loop e != l encloses l iff e has an odd number of vertical unit edges on pixel row b0 with a < a0, and parent[l] is
+ * the enclosing loop of smallest |area2|.
+ * DEPTH.  depth[l] is 0 without a parent, otherwise depth[parent[l]] + 1: even exactly for outer boundaries.
+ * CHILDREN AND REGIONS.  n_children[l] is the number of loops whose parent is l.  region_area2[l] is the int64 sum of area2[l] and the
+ * area2 of the children of l: for an outer boundary twice the number of set pixels of one connected component of the layer under
+ * `connectivity`; for a hole minus twice the number of clear pixels of one component of the clear pixels under the dual connectivity
+ * (8 for 4, 4 for 8), the outside component excluded.
+ * PER LAYER.  outer: its loops with area2 > 0; top: its loops without a parent; max_depth.
+ * `bricks`: a host buffer, or with bricks_on_device != 0 a device pointer (8-byte aligned), as for fhip_components_label_slices.  It MUST
+ * be the bitmap that was outlined, unchanged: the handle holds no copy of it.  With another bitmap the result is unspecified, but
+ * nothing is read or written outside the arrays: the row scan ends at a = 0, the column walk at the lattice's border, the vertex
+ * search inside the layer's own id range, and only a loop of the same layer with a smaller id is kept as left[l].
+ * THE PASSES.  A lane per loop: the row scan, the column walk against the edge's heading to the corner where its straight run begins, a
+ * lower bound search for that corner's word a | b << 16 among the layer's vertices (a saddle's two share the word; only m = 10 has
+ * vertical outgoing headings, 2 then 3), loop_of.  Parents by pointer doubling over the links of equal sign, depths by the same
+ * doubling over (ancestor, hops), double-buffered, ceil(log2(the largest layer's loop count)) rounds each, fixed by the host from
+ * loop_start.  The sums are integer atomics; no kernel waits for another workgroup.
+ * The call blocks, as fhip_voxels_outlines does.  parent and depth stay in device memory, owned by the handle (the _dev getters; NULL
+ * where there are no loops); everything is also on the host: the getters copy, any output pointer may be NULL, and a range beyond the
+ * counts is FHIP_ERR_UNSUPPORTED.  counts = {loops, outer, top, max depth, layers, k0, connectivity, 0}.  Outlines with no loops, or
+ * with k0 == k1, give FHIP_OK and an empty nesting.  Refused before any launch: no context, outlines or result (FHIP_ERR_BAD_TAPE), no
+ * bitmap, outlines of another device's context (FHIP_ERR_UNSUPPORTED).  The outlines are read and not changed.
+ * fhip_nesting_children is host code and needs no context: a counting sort of the n loops by parent into CSR - child_start[n + 1],
+ * children[child_start[n]], each list ascending; loops without a parent are in no list; a parent >= n that is not NONE is
+ * FHIP_ERR_UNSUPPORTED. */
+fhip_status fhip_outlines_nesting(fhip_ctx* ctx, const void* outlines, const uint64_t* bricks, int bricks_on_device, void** out);
+void fhip_nesting_counts(const void* nest, uint64_t out[8]);
+fhip_status fhip_nesting_layers(const void* nest, uint64_t* outer, uint64_t* top, uint32_t* max_depth);
+fhip_status fhip_nesting_loops(const void* nest, uint64_t first, uint64_t count, uint32_t* left, uint32_t* parent, uint32_t* depth,
+                               uint32_t* n_children, int64_t* region_area2);
+const uint32_t* fhip_nesting_parent_dev(const void* nest);
+const uint32_t* fhip_nesting_depth_dev(const void* nest);
+fhip_status fhip_nesting_children(const uint32_t* parent, uint64_t n, uint64_t* child_start, uint32_t* children);
+void fhip_nesting_free(void* nest);
+
 /* ---- the slices of a triangle mesh: closed contour loops per plane z = const ----------------------------------------
  * (No counterpart in the reference, which never cuts a mesh: the definition below is the specification.  Every output but one is the
  * same bits from run to run and does not depend on how the hardware orders the threads; a loop's area2 is a float64 sum of the same

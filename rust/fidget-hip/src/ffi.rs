@@ -200,6 +200,16 @@ extern "C" {
     pub fn fhip_outlines_next_dev(outlines: *const c_void) -> *const u32;
     pub fn fhip_outlines_loop_dev(outlines: *const c_void) -> *const u32;
     pub fn fhip_outlines_free(outlines: *mut c_void);
+    // the nesting of those outlines: per loop its left neighbour, parent, depth, children and region sum; fhip_nesting_children is host code
+    pub fn fhip_outlines_nesting(ctx: *mut fhip_ctx, outlines: *const c_void, bricks: *const u64, bricks_on_device: c_int, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_nesting_counts(nest: *const c_void, out: *mut u64);
+    pub fn fhip_nesting_layers(nest: *const c_void, outer: *mut u64, top: *mut u64, max_depth: *mut u32) -> fhip_status;
+    pub fn fhip_nesting_loops(nest: *const c_void, first: u64, count: u64, left: *mut u32, parent: *mut u32, depth: *mut u32, n_children: *mut u32,
+                              region_area2: *mut i64) -> fhip_status;
+    pub fn fhip_nesting_parent_dev(nest: *const c_void) -> *const u32;
+    pub fn fhip_nesting_depth_dev(nest: *const c_void) -> *const u32;
+    pub fn fhip_nesting_children(parent: *const u32, n: u64, child_start: *mut u64, children: *mut u32) -> fhip_status;
+    pub fn fhip_nesting_free(nest: *mut c_void);
     // the slices of a checked mesh under planes z = const: crossings on the mesh's edges, their successors, the loops and their table
     pub fn fhip_topology_slices(ctx: *mut fhip_ctx, topology: *const c_void, zs: *const f32, n_planes: u32, table_log2: u32, out: *mut *mut c_void) -> fhip_status;
     pub fn fhip_slices_counts(slices: *const c_void, out: *mut u64);
