@@ -235,6 +235,7 @@ SIGNATURES = {
     "fhip_debug_probe": (i32, [vp, vp]),
     "fhip_debug_lane_frames": (u64, [vp]),
     "fhip_debug_rare_frames": (u64, [vp]),
+    "fhip_debug_rare_launches": (u64, [vp]),
     "fhip_debug_lane_tune": (i32, [vp, vp, vp]),
     "fhip_debug_trans_probe": (i32, [vp, u32, u32, u32, u64, vp]),
     "fhip_debug_arena": (u32, [vp, u32, u32, vp]),

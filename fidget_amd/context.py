@@ -66,6 +66,11 @@ class HipContext:
         into the slab's other launches (fhip_debug_rare_frames; capi_render.hpp)"""
         return int(lib().fhip_debug_rare_frames(self._h))
 
+    def rare_launches(self):
+        """Launches this context's by-list frames made for nothing but rare mode's blocks so far: one per slab of such a frame
+        (fhip_debug_rare_launches)"""
+        return int(lib().fhip_debug_rare_launches(self._h))
+
     def set_option(self, name, value=1):
         """A behaviour switch of this context (fhip_ctx_set_option: "no_column_inv", "frame_lanes", ...).  The environment
         (FHIP_<NAME>) is read once, when the context is created; this is the only way to change a switch afterwards."""

@@ -135,7 +135,6 @@ void fhip_ctx_destroy(fhip_ctx* c) {
     (void)hipSetDevice(c->device);
     (void)hipStreamSynchronize(c->stream);
     lanes_release(c);
-    if (c->ev_last) (void)hipEventDestroy(c->ev_last);
     if (c->stream_pre) (void)hipStreamSynchronize(c->stream_pre);
     if (c->stream2) (void)hipStreamSynchronize(c->stream2);
     (void)hipStreamSynchronize(c->stream);

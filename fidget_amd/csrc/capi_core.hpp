@@ -176,7 +176,7 @@ struct fhip_ctx : FrameBufs {
     }
     DevBuf tmp_out, io_a, io_b, io_c, io_d, io_e;
     DevBuf sticky;      // one word: a queue overflow of ANY asynchronous frame since the last fhip_ctx_sync (k_finish3d latches it)
-    struct Staging { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; bool used = false; } staging[8];   // pinned (upload_frame)
+    struct Staging { void* p = nullptr; size_t cap = 0; hipEvent_t ev = nullptr; } staging[FH_STAGING_SLOTS];   // pinned (upload_frame); whose turn and which events count: `ring`
     DevBuf mesh_leaves;               // fhip_mesh_build / fhip_mesh_sample: the leaf records in HBM (17 GB at depth 10), kept between builds - allocating and freeing
                                       // them per build cost 10-20 ms of every build and, once in a few, two seconds (profiles/r04a, r04h)
     void* mesh_pinned = nullptr;      // fhip_mesh_build: the leaf records' landing area on the host, kept between calls (pinning 17 GB takes over a second)
@@ -186,7 +186,7 @@ struct fhip_ctx : FrameBufs {
     void* mesh_octree_cache = nullptr;       // fhmesh::Octree*
     uint32_t* mesh_first = nullptr;
     size_t mesh_first_cap = 0;
-    uint32_t staging_next = 0;
+    StagingRing ring;                 // (frame_schedule.hpp)
     // Tape arena, per buffer set: starts at FH_ARENA_START_MB (prospero.vm at 1024^3 peaks at 79 MB per z-slab context) and is grown
     // twofold - up to option arena_mb, default 4 GiB - when a frame ran out: the frame itself is still right (children keep their parent's
     // tape, tests/test_gpu_parity.py test_render3d_survives_a_full_tape_arena), its last kernel says so in `host_flags` - a pinned word the
@@ -209,10 +209,13 @@ struct fhip_ctx : FrameBufs {
     // Rare mode of a 3D frame (capi_render.hpp): the launches that exist for tapes too large for the assembly kernels' register files - three or
     // four per slab, empty in nearly every frame - folded into launches the slab makes anyway; taken while the last finished frame met no such tape
     uint64_t rare_frames = 0;         // ... frames rendered that way so far (fhip_debug_rare_frames)
+    uint64_t rare_launches = 0;       // ... and the launches by-list frames made for NOTHING BUT rare mode's blocks so far (fhip_debug_rare_launches): one per slab
     uint64_t lane_frames = 0;         // frames that went to a lane so far (fhip_debug_lane_frames)
     uint64_t lane_frames_wanted = 0;  // ... not counting the tuner's measuring windows
-    hipEvent_t ev_last = nullptr;     // the end of the last 3D frame on the caller's stream ("is the frame before still under way?")
-    bool ev_last_valid = false;
+    // "Is the frame before this one still under way?" - asked once per frame (capi_render.hpp frame_before_under_way) of the event that
+    // frame recorded at its end anyway: its set's ev_done, or the lane's lane_copied.  Not owned: whoever destroys such an event clears it.
+    hipEvent_t last_end = nullptr;
+    bool before_asked = false, before_busy = false;      // (this frame's answer, once it has asked)
     // Which of the two arrangements a queued 3D frame takes is MEASURED, per (tape, image size): consecutive queued frames of one kind
     // run a window under the stage pipeline, then one on the lanes, each timed between two events on the caller's stream, and the
     // faster arrangement is kept (capi_render.hpp lane_mode)

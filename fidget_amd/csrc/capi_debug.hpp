@@ -164,6 +164,14 @@ uint64_t fhip_debug_rare_frames(const fhip_ctx* ctx) {
     for (const fhip_ctx* l : ctx->lanes) n += l ? l->rare_frames : 0;
     return n;
 }
+// Diagnostics: how many launches the by-list frames of this context (its lanes included) made for nothing but rare mode's blocks so far
+// (capi_render.hpp classify_work, normals_work): one per slab (k_rare_leaves3d), or two where the leaf and the normals kernel's files differ
+uint64_t fhip_debug_rare_launches(const fhip_ctx* ctx) {
+    if (!ctx) return 0;
+    uint64_t n = ctx->rare_launches;
+    for (const fhip_ctx* l : ctx->lanes) n += l ? l->rare_launches : 0;
+    return n;
+}
 // Diagnostics: how many frames of this context went to a frame lane (capi_render.hpp run_on_lane) so far
 uint64_t fhip_debug_lane_frames(const fhip_ctx* ctx) { return ctx ? ctx->lane_frames : 0; }
 // ... and what the arrangement tuner (capi_render.hpp lane_mode) knows about the kind of 3D frame queued last: its phase (0 / 1 / 2 measuring the

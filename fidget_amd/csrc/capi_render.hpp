@@ -214,12 +214,21 @@ static fhip_status finish_render(fhip_ctx* ctx) {
 }
 
 struct FrameClear { void* p = nullptr; size_t bytes = 0; uint32_t fill = 0; };   // a buffer the frame starts from cleared (bytes: a multiple of 4)
-static fhip_status upload_frame(fhip_ctx* ctx, hipStream_t st, const fhip_tape* tape, RenderSetup& R, const FrameClear (&clear)[3]) {
+// The record that guards a staging slot (frame_schedule.hpp SlotGuard): the slot's event, behind what `st` - the frame's root stream - has been given so far
+struct RecordSlot {
+    fhip_ctx* ctx = nullptr; uint32_t slot = 0; hipStream_t st = nullptr;
+    void operator()() const { if (hipEventRecord(ctx->staging[slot].ev, st) == hipSuccess) ctx->ring.used[slot] = true; else (void)hipGetLastError(); }
+};
+typedef SlotGuard<RecordSlot> StagingGuard;
+// (`later`: the frame records the slot's guard itself, where its root stream leaves the root level or the frame ends - armed here once
+// k_frame_begin is queued; none: recorded here, behind k_frame_begin)
+static fhip_status upload_frame(fhip_ctx* ctx, hipStream_t st, const fhip_tape* tape, RenderSetup& R, const FrameClear (&clear)[3], StagingGuard* later = nullptr) {
     // The frame's state and root groups go through pinned staging slots (a ring of eight, each guarded by an event): a copy from
     // pageable memory would make the host wait for everything queued on the stream before it, i.e. for the previous frame.
     const size_t roots_bytes = R.roots.size() * sizeof(FhGroup);
-    fhip_ctx::Staging& sg = ctx->staging[ctx->staging_next++ % 8];
-    if (sg.ev && sg.used) HIP_TRY(ctx, hipEventSynchronize(sg.ev));
+    const uint32_t slot = ctx->ring.take();
+    fhip_ctx::Staging& sg = ctx->staging[slot];
+    if (sg.ev && ctx->ring.used[slot]) HIP_TRY(ctx, hipEventSynchronize(sg.ev));
     if (!sg.ev) HIP_TRY(ctx, hipEventCreateWithFlags(&sg.ev, hipEventDisableTiming));
     if (sg.cap < sizeof(FhRenderState) + roots_bytes) {
         if (sg.p) (void)hipHostFree(sg.p);
@@ -258,9 +267,10 @@ static fhip_status upload_frame(fhip_ctx* ctx, hipStream_t st, const fhip_tape* 
     }
     const unsigned blocks = (unsigned)std::max<size_t>(8, std::min<size_t>((size_t)ctx->n_cu * 32, (most + 64 * 64 - 1) / (64 * 64)));
     FH_KLAUNCH(k_frame_begin, dim3(blocks), dim3(WAVE), 0, st, fb);
+    // (armed before the launch's status is looked at: a launch that failed may still have been queued)
+    if (later) { later->record_now = RecordSlot{ctx, slot, st}; later->arm(); }
+    else RecordSlot{ctx, slot, st}();
     HIP_TRY(ctx, hipGetLastError());
-    HIP_TRY(ctx, hipEventRecord(sg.ev, st));
-    sg.used = true;
     for (auto& e : ctx->prof_events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
     ctx->prof_events.clear();
     for (auto& e : ctx->asm_events) { (void)hipEventDestroy(e.second.first); (void)hipEventDestroy(e.second.second); }
@@ -540,7 +550,7 @@ static fhip_status render2d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     }
     HIP_TRY(ctx, hipGetLastError());
     HIP_TRY(ctx, hipEventRecord(ctx->ev_done, ctx->stream));     // (a later pipelined 3D frame that takes this buffer set waits for it)
-    ctx->ev_done_valid = true;
+    ctx->ev_done_valid = true; ctx->last_end = ctx->ev_done;
     if (!out_is_device) {
         HIP_TRY(ctx, hipMemcpyAsync(out, d_out, npix * 4, hipMemcpyDeviceToHost, ctx->stream));
         return finish_render(ctx);
@@ -571,7 +581,7 @@ static void slab_begin(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule&
 // The tile chain of slab k (the idx-th slab rendered) on the schedule's tile stream
 static fhip_status tile_step(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, int k, int idx, const FhHead* head) {
     fs.cur = F.tiles;
-    if (F.pipe && idx >= (int)F.NC) HIP_TRY(ctx, hipStreamWaitEvent(fs.on(), ctx->ev_leaves[idx - (int)F.NC], 0));  // context free again
+    if (waits_leaves(F, idx)) HIP_TRY(ctx, hipStreamWaitEvent(fs.on(), ctx->ev_leaves[idx - (int)F.NC], 0));  // context free again
     const FhHead* const mine = head && idx == 0 ? head : nullptr;      // (the frame's first tile chain: no launch for the slab's reset - in its set-up kernel)
     if (!mine) slab_begin(ctx, R, F, dS, k, fs.on());
     for (uint32_t l = R.S.pre_levels; l < R.S.P.n_levels; l++) launch_tiles(ctx, R, F.level[l], dS, (int)l, true, fs, l == R.S.pre_levels ? mine : nullptr);
@@ -583,8 +593,9 @@ static fhip_status tile_step(fhip_ctx* ctx, const RenderSetup& R, const FrameSch
 static void classify_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, hipStream_t st) {
     const uint32_t class_blocks = (R.n_footprints + FH_CLASSIFY_FP - 1) / FH_CLASSIFY_FP;
     // (by_list: nothing to classify - what is left of the launch is rare mode's blocks for the leaves beyond the leaf kernel's file)
-    if (F.by_list && F.rare && R.S.P.max_regs > R.S.leaf_asm_regs)
-        launch(ctx, st, FHIP_K_OTHER, [&] { FH_KLAUNCH(k_classify3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, 1, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride); });
+    if (F.rare_leaves) {}      // (... and those blocks' work is k_rare_leaves3d's, behind the leaf kernel: normals_work)
+    else if (F.by_list && F.rare && R.S.P.max_regs > R.S.leaf_asm_regs)
+        launch(ctx, st, FHIP_K_OTHER, [&] { ctx->rare_launches++; FH_KLAUNCH(k_classify3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, 1, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride); });
     else if (!F.by_list) launch(ctx, st, FHIP_K_OTHER, [&] {
         FH_KLAUNCH(k_classify3d, dim3(class_blocks + (F.rare ? FH_RARE_BLOCKS : 0u)), dim3(R.S.P.slab / 8 > 16 ? 256 : WAVE), 0, st, dS, R.asm_points ? 1 : 0, class_blocks,
                    rare_file(ctx, dS, F.rare_stride), F.rare_stride);
@@ -641,8 +652,12 @@ static void normals_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedul
         if (F.by_list) {
             // (the leaf that owns a pixel's hit is its column's leaf or nobody: fh_normals takes the slab's leaves one per wave pass and
             // looks at the z-buffer itself; k_hits3d: rare mode's blocks for the footprints the push put on list 2)
-            if (F.rare && R.S.P.max_regs > R.S.norm_asm_regs)
+            // (rare_leaves: the points of the leaves beyond the leaf kernel's file and the normals of their hits in one launch, driven by the slab's leaves)
+            if (F.rare_leaves) { ctx->rare_launches++; FH_KLAUNCH(k_rare_leaves3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, rare_file(ctx, dS, F.rare_stride), F.rare_stride); }
+            else if (F.rare && R.S.P.max_regs > R.S.norm_asm_regs) {
+                ctx->rare_launches++;
                 FH_KLAUNCH(k_hits3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, R.hit_bucket_cap, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride);
+            }
             KaNormals kn = {dS, F.list_waves, R.col_slots, z_lo, z_hi, R.hit_bucket_cap, 1u};
             (void)launch_asm(ctx, st, which, kn.n_waves, &kn, sizeof(kn));
         }
@@ -681,29 +696,32 @@ static FhHead tile_head(const fhip_ctx* ctx, const RenderSetup& R, const FrameSc
     h.slab = (uint32_t)F.slab_first; h.n_root_groups = R.groups_per_slab; h.depmask = R.col_depmask;
     return h;
 }
-static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, const FhHead& head) {
+// (`slot`: the staging slot's guard, recorded where the host leaves the root stream for the first time - beside that hop's own record, behind
+// the root level; a frame that stays on its root stream keeps it armed for render3d_frame)
+static fhip_status coarse_levels(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FrameStreams& fs, FhRenderState* dS, const FhHead& head, StagingGuard& slot) {
     const uint32_t pre = R.S.pre_levels;
     const FhFork& fork = head.fork;
     const bool forked_here = F.coarse && R.zrep;      // (by the flags launch below, or by the head of the tile chain)
+    auto leave = [&](Role to, hipEvent_t ev) { if (to != fs.cur) slot.record(); return hop(fs, to, ev); };
     if (F.coarse) {
         launch_tiles(ctx, R, F.level[0], dS, 0, true, fs);
         if (pre > 1) {
-            HIP_TRY(ctx, hop(fs, F.l1_flags, ctx->ev_l0));
+            HIP_TRY(ctx, leave(F.l1_flags, ctx->ev_l0));
             if (R.zrep) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 4), dim3(WAVE), 0, fs.on(), dS, 1, R.col_depmask, 0, FhFork{}); });
-            HIP_TRY(ctx, hop(fs, F.l1, ctx->ev_l0));
+            HIP_TRY(ctx, leave(F.l1, ctx->ev_l0));
             launch_tiles(ctx, R, F.level[1], dS, 1, true, fs);
         }
-        HIP_TRY(ctx, hop(fs, F.fork_on, pre > 1 ? ctx->ev_l1 : ctx->ev_l0));      // (level 1 did not go through fh_tiles_v64; or one coarse level whose tail goes to the side stream)
+        HIP_TRY(ctx, leave(F.fork_on, pre > 1 ? ctx->ev_l1 : ctx->ev_l0));      // (level 1 did not go through fh_tiles_v64; or one coarse level whose tail goes to the side stream)
         // (the fork of a pipelined frame's slab contexts - or, with ONE context, the frame mark alone - in the same launch)
         if (R.zrep && !head.on) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_tape_flags, dim3(ctx->n_cu * 8 + 1), dim3(WAVE), 0, fs.on(), dS, (int)pre, R.col_depmask, 1, fork); });
         if (!F.pipe && !forked_here) launch(ctx, fs.on(), FHIP_K_OTHER, [&] { FH_KLAUNCH(k_mark_frame, dim3(1), dim3(1), 0, fs.on(), dS); });
     }
     if (F.pipe) {
         if (!forked_here) FH_KLAUNCH(k_fork_state, dim3(1), dim3(1), 0, fs.on(), dS, fork);
-        HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, fs.on()));
+        if (F.rec_fork) HIP_TRY(ctx, hipEventRecord(ctx->ev_fork, fs.on()));
         if (F.fork_to_side) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[SIDE], ctx->ev_fork, 0));
     }
-    if (F.ev_pre) HIP_TRY(ctx, hop(fs, CALLER, ctx->ev_pre));     // (from the stream the last coarse-level kernel went to)
+    if (F.ev_pre) HIP_TRY(ctx, leave(CALLER, ctx->ev_pre));     // (from the stream the last coarse-level kernel went to)
     fs.cur = CALLER;
     if (F.fork_to_tail) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[TAIL], ctx->ev_fork, 0));
     return FHIP_OK;
@@ -728,13 +746,25 @@ static fhip_status render_slabs(fhip_ctx* ctx, const RenderSetup& R, const Frame
         leaf_work(ctx, R, F, dS, (uint32_t)(dS - dS0), fs.s[F.leaf]);
         if (F.aux_edge) { HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[idx], fs.s[F.leaf])); HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.normals], ctx->ev_aux[idx], 0)); }     // the slab's leaf kernel is through
         if (F.normals_on) normals_work(ctx, R, F, dS, k, fs.s[F.normals]);
-        if (F.pipe) HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], fs.s[F.normals]));       // slab context free again; the last one: image complete
+        if (records_leaves(F, idx)) HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], fs.s[F.normals]));       // slab context free again for slab idx + NC; the last one of an aux_edge frame: image complete
     }
     // (the tail stream is serial: the last slab's normals)
     if (F.aux_edge && F.n_rendered > 0) HIP_TRY(ctx, hipStreamWaitEvent(fs.s[CALLER], ctx->ev_leaves[F.n_rendered - 1], 0));
     return FHIP_OK;
 }
 
+// "Is the frame before this one still under way?" - what decides lanes or stage pipeline (lanes_possible) and, under the stage pipeline,
+// whether the frame is alone (frame_schedule.hpp `lone`).  Asked of the event that frame recorded at its end on the caller's stream
+// (fhip_ctx::last_end), at most once per frame: new_frame() at every entry point forgets the last answer.
+static void new_frame(fhip_ctx* ctx) { ctx->before_asked = false; }
+static bool frame_before_under_way(fhip_ctx* ctx) {
+    if (!ctx->before_asked) {
+        ctx->before_asked = true;
+        ctx->before_busy = ctx->last_end && hipEventQuery(ctx->last_end) == hipErrorNotReady;
+        (void)hipGetLastError();
+    }
+    return ctx->before_busy;
+}
 static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_config* cfg, void* out,
                                   int out_is_device, const PartSpec& part) {
     if (ctx->is_cancelled()) return fail(ctx, FHIP_ERR_CANCELLED, "cancelled");
@@ -770,8 +800,7 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
         // (rotate: the current set goes to the back of the ring, the set used longest ago comes forward)
         for (uint32_t i = 0; i < ctx->extra_sets; i++) std::swap(static_cast<FrameBufs&>(*ctx), ctx->others[i]);
         // the frame before this one is still under way (the caller queues frames back to back)
-        in.frames_queued = ctx->extra_sets > 0 && ctx->others[0].ev_done_valid && hipEventQuery(ctx->others[0].ev_done) == hipErrorNotReady;
-        (void)hipGetLastError();
+        in.frames_queued = ctx->extra_sets > 0 && frame_before_under_way(ctx);
     }
     // (clean buffer sets, frame_plan.hpp: what the set's last frame left it clean for - taken off the set before anything of this frame can
     // touch its buffers, prepare()'s growing them included: whatever ends this frame early leaves no record)
@@ -800,11 +829,13 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     want_clean.valid = true; want_clean.pixels = npix; want_clean.mind_words = R.mind_words;
     const bool is_clean = set_is_clean(left_clean, want_clean);      // (then the clears are skipped)
     const FrameClear clear3[3] = {{ctx->zbuf.p, npix * 8, 0u}, {ctx->normals.p, npix * 12, 0u}, {ctx->mind.p, R.mind_words * 4, 0u}}, no_clear[3] = {};
-    st = upload_frame(ctx, fs.on(), tape, R, is_clean ? no_clear : clear3);
+    // (the staging slot's guard: recorded by coarse_levels where the root stream is left, or below beside ev_done - or by whatever returns before that)
+    StagingGuard slot(RecordSlot{});
+    st = upload_frame(ctx, fs.on(), tape, R, is_clean ? no_clear : clear3, &slot);
     if (st) return st;
     FH_SPAN(2);
     const FhHead head = tile_head(ctx, R, F);
-    st = coarse_levels(ctx, R, F, fs, dS0, head);
+    st = coarse_levels(ctx, R, F, fs, dS0, head, slot);
     if (st) return st;
     FH_SPAN(3);
     st = render_slabs(ctx, R, F, fs, dS0, head);
@@ -816,8 +847,9 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
     HIP_TRY(ctx, hipGetLastError());
     if (ctx->launch_failed) { ctx->launch_failed = false; return FHIP_ERR_HIP; }   // (message in fhip_last_error)
     ctx->async_pending = out_is_device != 0;
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_done, ctx->stream));     // (a later pipelined frame that takes this set waits for it)
-    ctx->ev_done_valid = true;
+    HIP_TRY(ctx, hipEventRecord(ctx->ev_done, ctx->stream));     // (a later pipelined frame that takes this set waits for it; the next frame asks it whether this one is under way)
+    ctx->ev_done_valid = true; ctx->last_end = ctx->ev_done;
+    slot.record();      // (a frame that never left its root stream - the caller's: the slot's guard at the end of its chain)
     ctx->clean = set_left_by(kind, want_clean, true);
     if (ctx->opt.stats & 2) { g_spans.mark(5); g_spans.frame(); }
     if (!out_is_device) {
@@ -838,14 +870,12 @@ static fhip_status render3d_frame(fhip_ctx* ctx, const fhip_tape* tape, const fh
 // column shard of eight stays where it is, 0.43 (profiles/r04r/lanes_parts.txt).
 static bool lanes_possible(fhip_ctx* ctx, int out_is_device) {
     if (ctx->opt.frame_lanes < 2 || ctx->is_lane || !out_is_device || ctx->profiling || ctx->probe || (ctx->opt.stats & 1)) return false;
-    if (!ctx->ev_last_valid) return false;
-    const hipError_t q = hipEventQuery(ctx->ev_last);      // the frame before this one: still under way?
-    (void)hipGetLastError();
-    return q == hipErrorNotReady;
+    return frame_before_under_way(ctx);
 }
 static void lane_tune_release(fhip_ctx* ctx);
 static void lanes_release(fhip_ctx* ctx, bool keep_measurements) {
     if (!keep_measurements) lane_tune_release(ctx);       // (what was measured was measured under the options of the moment)
+    for (fhip_ctx* L : ctx->lanes) if (ctx->last_end == L->lane_copied) ctx->last_end = nullptr;      // (the event goes with its lane)
     for (fhip_ctx* L : ctx->lanes) {
         hipStream_t const s = L->lane_stream_owned ? L->stream : nullptr;
         if (L->lane_done) (void)hipEventDestroy(L->lane_done);
@@ -893,7 +923,7 @@ static fhip_status run_on_lane_(fhip_ctx* ctx, uint32_t max_lanes, size_t bytes,
     HIP_TRY(ctx, hipStreamWaitEvent(ctx->stream, L->lane_done, 0));
     HIP_TRY(ctx, hipMemcpyAsync(out, L->lane_img.p, bytes, hipMemcpyDeviceToDevice, ctx->stream));
     HIP_TRY(ctx, hipEventRecord(L->lane_copied, ctx->stream));
-    L->lane_copied_valid = true;
+    L->lane_copied_valid = true; ctx->last_end = L->lane_copied;      // (the end of this frame on the caller's stream)
     ctx->lane_frames++;
     if (ctx->tune_cur < 0) ctx->lane_frames_wanted++;      // (not a frame of a measuring window: somebody's arrangement of choice)
     return FHIP_OK;
@@ -1005,11 +1035,9 @@ static bool lane_mode(fhip_ctx* ctx, const fhip_tape* tape, const fhip_render3d_
     ctx->tune_cur = at;
     return T.phase == 1;
 }
-static fhip_status frame_queued(fhip_ctx* ctx, int out_is_device) {      // (the end of this frame, for the next one's lanes_possible)
+// (a queued frame's end: the marks of the tuner's windows.  What the next frame's lanes_possible asks is `last_end`, which the frame set itself.)
+static fhip_status frame_queued(fhip_ctx* ctx, int out_is_device) {
     if (!out_is_device || ctx->is_lane || ctx->opt.frame_lanes < 2) return FHIP_OK;
-    if (!ctx->ev_last) HIP_TRY(ctx, hipEventCreateWithFlags(&ctx->ev_last, hipEventDisableTiming));
-    HIP_TRY(ctx, hipEventRecord(ctx->ev_last, ctx->stream));
-    ctx->ev_last_valid = true;
     if (ctx->tune_cur >= 0) {       // a frame of a measuring window: its marks
         fhip_ctx::LaneTune& T = ctx->lane_tune[(size_t)ctx->tune_cur];
         ctx->tune_cur = -1;
@@ -1037,6 +1065,7 @@ static fhip_status render3d_part(fhip_ctx* ctx, const fhip_tape* tape, const fhi
         bcfg = *cfg; bcfg.axis_slots = BOUND_AXES; bcfg.var_keys = nullptr; bcfg.var_values = nullptr; bcfg.n_vars = 0;
         cfg = &bcfg;
     }
+    new_frame(ctx);
     fhip_status st = lane_mode(ctx, tape, cfg, out_is_device, part)
         ? run_on_lane(ctx, 8, (size_t)cfg->width * cfg->height * sizeof(FhGeometryPixel), out,
                       [&](fhip_ctx* L, void* img) { return render3d_frame(L, tape, cfg, img, 1, part); })
@@ -1062,6 +1091,7 @@ fhip_status fhip_render2d(fhip_ctx* ctx, const fhip_tape* tape, const fhip_rende
         bcfg = *cfg; bcfg.axis_slots = BOUND_AXES; bcfg.var_keys = nullptr; bcfg.var_values = nullptr; bcfg.n_vars = 0;
         cfg = &bcfg;
     }
+    new_frame(ctx);
     ctx->tune_cur = -1;
     ctx->tune_last_key = 0;       // (a 2D frame between two 3D frames of one kind: their window starts again)
     fhip_status st = lanes_possible(ctx, out_is_device)

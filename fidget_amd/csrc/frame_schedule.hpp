@@ -6,6 +6,10 @@
 // How to read one: a frame is root level -> level 1 (flags, evaluate) -> `fork_on` (flags of the parked parents, frame mark, fork of the
 // slab contexts) -> per slab: tile chain, footprint lists, leaf kernel, normals -> k_finish3d on the caller's stream.  Wherever two
 // consecutive stages have different roles there is an event between them; the edges that are not a plain hop are the fork_* / ev_pre fields.
+// An event is recorded where somebody waits for it and nowhere else: a record between two dependent kernels of one stream costs that chain
+// a gap and the host a runtime call (profiles/event_edges), so WHICH events a frame records is part of its schedule - rec_fork and
+// records_leaves() below, next to the fields that say who waits - and the driver keeps no condition of its own.  The one record that guards
+// host memory, the pinned staging slot's, is made where the root stream leaves the root level or the frame ends (SlotGuard, at the end).
 #pragma once
 #include <stddef.h>
 #include <stdint.h>
@@ -59,12 +63,14 @@ struct FrameSchedule {
     // edges that are not a hop between consecutive stages: ev_fork to the side / tail stream, ev_pre to the caller's stream - or implied by
     // the first tile chain's event; per slab, if `pipe`, ev_tiles (tile chain -> lists, leaf kernel); ev_aux (leaf kernel -> normals), ev_leaves (context free, image complete)
     bool fork_to_side = false, fork_to_tail = false, ev_pre = false, pre_implied = false, aux_edge = false;
+    bool rec_fork = false;      // ev_fork is recorded: the side or the tail stream waits for it (a frame whose tile chain runs where the fork went records none)
     // there is a pre-pass (and something to render); slab contexts in flight, NC of them; every slab's tile chain queued before the first slab's tail work
     bool coarse = false, pipe = false, tiles_first = false; uint32_t NC = 1;
     int slab_first = 0, slab_stop = 0, n_rendered = 0;      // slabs rendered: slab_first down to slab_stop
     bool rare = false; uint32_t rare_stride = 0;            // rare mode; bytes of a rare block's register file
     enum LeafWalk : uint8_t { HIP_LEAVES, BY_LIST, BY_COLUMNS, BY_BLOCKS } leaf_walk = HIP_LEAVES;
     bool by_list = false, by_columns = false; uint32_t g = 0;      // the leaf kernel's walk; group of 2^g layers
+    bool rare_leaves = false;    // rare mode of a by_list frame: ONE launch (k_rare_leaves3d) for the points and the normals of the leaves beyond the leaf kernel's file
     uint32_t list_waves = 0, table_words = 0; int reset_blocks = 1;
     bool normals_on = true;      // (FH_EXP_SKIP_NORMALS)
     LevelPlan level[FH_MAX_LEVELS];
@@ -187,6 +193,7 @@ static FrameSchedule schedule_frame(const RenderSetup& R, const ScheduleInputs& 
     F.tiles = !F.pipe ? CALLER : F.tiles_first ? TAIL : SIDE;
     F.fork_to_side = F.pipe && F.fork_on != SIDE;
     F.fork_to_tail = F.tiles_first;
+    F.rec_fork = F.fork_to_side || F.fork_to_tail;
     // the rest of the frame is the caller's stream's (and the tile stream's, which waits for the fork)
     // (one coarse level, its tail on the side stream, and tile chains to follow there: the caller's stream waits for the first tile
     // chain's event, which lies behind everything queued so far - no event of its own for that)
@@ -209,7 +216,7 @@ static FrameSchedule schedule_frame(const RenderSetup& R, const ScheduleInputs& 
     // registers (its points, then its normals, in the C++ kernels with an LDS file), a parent of a per-slab tile level outside the small
     // slot list (fh_tiles_v64, then fh_tiles) - and find nothing to do in nearly every frame: prospero.vm 1024^3 0.138 -> 0.126 ms per
     // frame without them.  While the last finished frame of this context met no such tape (k_finish3d: host_flags[2]) the slab does not
-    // make them: the last FH_RARE_BLOCKS blocks of k_classify3d, k_hits3d and k_tpush3d do their work - correct for any number of such
+    // make them: the last FH_RARE_BLOCKS blocks of k_classify3d, k_hits3d (or k_rare_leaves3d for both: rare_leaves below) and k_tpush3d do their work - correct for any number of such
     // tapes, slow for many (a wave per block, the register files in HBM), and the first frame that meets one puts the launches back.
     const size_t stride = (std::max(std::max(R.lds_tiles_big, R.lds_points_big), R.lds_normals_big) + 255) / 256 * 256;
     // (a root tape of <= 32 registers has no large leaves, but its per-slab levels still launch fh_tiles_v64 for the other slot list)
@@ -225,6 +232,16 @@ static FrameSchedule schedule_frame(const RenderSetup& R, const ScheduleInputs& 
     const uint32_t layers = P.slab / 8;
     F.by_list = in.column_walk == 1 && R.column_inv && R.split && R.zrep && R.asm_points && R.asm_normals && layers <= 64 && in.has_flags;
     F.table_words = F.by_list ? 0u : R.table_words;
+    // Rare mode in such a frame: all that is left of k_classify3d and k_hits3d are their FH_RARE_BLOCKS blocks for the leaves beyond the assembly
+    // kernels' files - two launches that read n_leaves_lds == 0 and leave, in nearly every frame (5.4 + 5.6 us of the caller's stream, prospero.vm
+    // 1024^3).  A column of a by_list frame has one leaf per slab or none, so a large leaf's hits are final when its own points are through and
+    // its gradient can follow in the same wave: one launch, behind the leaf kernel.  Only where the leaf kernel's and the normals kernel's files
+    // are the same size (40 / 40; with transcendental opcodes 44 / 40): a leaf between the two has its points from fh_columns_t and its normals
+    // from k_hits3d's blocks, and keeps both launches as they are.
+    F.rare_leaves = F.by_list && F.rare && P.max_regs > R.S.leaf_asm_regs && R.S.leaf_asm_regs == R.S.norm_asm_regs;
+#ifdef FH_EXP_TWO_RARE_LAUNCHES      // experiment (tools/build_lib_variant.py): the rare-only k_classify3d and k_hits3d launches as until profiles/event_edges
+    F.rare_leaves = false;
+#endif
     F.list_waves = (R.n_footprints + 63) / 64 * 64;      // (no frame has reported yet: what the column walk launches)
     if (F.by_list && in.last_leaves) F.list_waves = std::min(F.list_waves, (in.last_leaves + in.last_leaves / 8 + 63) / 64 * 64);
     F.reset_blocks = (int)std::max<uint32_t>(1, std::min<uint32_t>(1024, (std::max(F.table_words, n_groups) + 255) / 256));
@@ -258,3 +275,37 @@ static FrameSchedule schedule_frame(const RenderSetup& R, const ScheduleInputs& 
     }
     return F;
 }
+
+// ev_leaves[idx], behind the normals of the idx-th slab rendered, has two waiters: the tile chain of slab idx + NC, which takes the same
+// slab context (capi_render.hpp tile_step), and - for the LAST slab of a frame whose normals run on the tail stream - the caller's stream
+// before k_finish3d.  It is recorded for those and for nobody: the front-slab frame (n_rendered 1) records none.
+static bool waits_leaves(const FrameSchedule& F, int idx) { return F.pipe && idx >= (int)F.NC && idx < F.n_rendered; }      // (the tile chain of slab idx: for ev_leaves[idx - NC])
+static bool records_leaves(const FrameSchedule& F, int idx) {
+    if (!F.pipe || idx < 0 || idx >= F.n_rendered) return false;
+    return idx + (int)F.NC < F.n_rendered || (F.aux_edge && idx == F.n_rendered - 1);
+}
+
+// ---- the pinned staging ring and its guards ---------------------------------------------------------------------------------
+// A frame's state and root groups reach the device through one of FH_STAGING_SLOTS pinned slots, which k_frame_begin reads on the frame's
+// root stream; the slot's next user, FH_STAGING_SLOTS frames later, waits for the slot's event first.  That event has to lie at or behind
+// k_frame_begin on the root stream - and not between k_frame_begin and the root level's first kernel, where it was until profiles/event_edges:
+// it is recorded when the root stream is left for the first time (beside the hop's own record, at the end of the root level) or, for a
+// frame that never leaves its root stream, beside the frame's last record - and on EVERY other way out of the frame, which is why it is
+// an object: whatever returns early (a cancelled frame, a failed launch, a refused level) records it on the way.
+static const uint32_t FH_STAGING_SLOTS = 8;
+struct StagingRing {
+    uint32_t next = 0;
+    bool used[FH_STAGING_SLOTS] = {};      // the slot's event has been recorded at least once: its next user waits for it
+    uint32_t take() { return next++ % FH_STAGING_SLOTS; }
+};
+// `Record`: what records the slot's event behind everything queued on the root stream so far (the driver: hipEventRecord)
+template <class Record> struct SlotGuard {
+    Record record_now;
+    bool armed = false;
+    explicit SlotGuard(Record r) : record_now(r) {}
+    SlotGuard(const SlotGuard&) = delete;
+    SlotGuard& operator=(const SlotGuard&) = delete;
+    void arm() { armed = true; }                                        // k_frame_begin has been queued: the device reads the slot
+    void record() { if (armed) { armed = false; record_now(); } }       // once
+    ~SlotGuard() { record(); }
+};

@@ -1419,6 +1419,28 @@ __global__ void __launch_bounds__(256) k_classify3d(FhRenderState* S, int merge0
 // the leaves of one column does not matter; a leaf whose pixels are all hit in front of it retires
 // after one load.  CLS: leaves of <= 16 registers, 17..32, more (LDS register file).
 // (file: the register file of class 2 - LDS, or a region of HBM; first, stride: this wave's leaves)
+// One leaf under a wave: the voxels of its 64 pixel columns front to back, ZB per lane at a time; the `pending` lanes look for their first
+// voxel inside.  True: this lane found it, at `depth`.  (file: the LDS-class register file, NR == 0)
+template <int NR, int ZB, bool FULL>
+FH_DEV bool leaf_points(const AS4 FhRender& P, const Mat4& mat, ctape_t tape, uint32_t len, char* file, int lane, uint32_t px, uint32_t py, uint32_t lz, uint32_t T, bool pending,
+                        uint32_t& depth) {
+    bool hit = false;
+    for (int k = (int)T - 1; k >= 0; k -= ZB) {
+        float x[ZB], y[ZB], z[ZB], res[ZB];
+        FOR_Z { xf_point(mat, (float)px, (float)py, (float)(lz + k - j), x[j], y[j], z[j]); res[j] = 0.0f; }
+        if (NR) run_points<(NR ? NR : 1), ZB, FULL>(tape, len, P, x, y, z, res);
+        else res[0] = run_points_lds<FULL>(tape, len, P, (float*)file, lane, x[0], y[0], z[0]);
+        FOR_Z {
+            if (pending && res[j] < 0.0f) {  // first voxel inside, front to back
+                depth = lz + (uint32_t)(k - j) + 1;
+                hit = true;
+                pending = false;
+            }
+        }
+        if (ballot(pending) == 0) break;
+    }
+    return hit;
+}
 template <int CLS, int NR, int ZB, bool FULL>
 FH_DEV void leaves3d_body(FhRenderState* S, char* file, uint32_t first, uint32_t stride) {
     const AS4 FhRender& P = *(const AS4 FhRender*)&S->P;
@@ -1441,21 +1463,7 @@ FH_DEV void leaves3d_body(FhRenderState* S, char* file, uint32_t first, uint32_t
         if (ballot(pending) == 0) continue;
         const ctape_t tape = (ctape_t)(S->arena + lf.tape.off);
         const uint32_t len = lf.tape.len;
-        bool hit = false;
-        for (int k = (int)T - 1; k >= 0; k -= ZB) {
-            float x[ZB], y[ZB], z[ZB], res[ZB];
-            FOR_Z { xf_point(mat, (float)px, (float)py, (float)(lz + k - j), x[j], y[j], z[j]); res[j] = 0.0f; }
-            if (NR) run_points<(NR ? NR : 1), ZB, FULL>(tape, len, P, x, y, z, res);
-            else res[0] = run_points_lds<FULL>(tape, len, P, (float*)file, lane, x[0], y[0], z[0]);
-            FOR_Z {
-                if (pending && res[j] < 0.0f) {  // first voxel inside, front to back
-                    depth = lz + (uint32_t)(k - j) + 1;
-                    hit = true;
-                    pending = false;
-                }
-            }
-            if (ballot(pending) == 0) break;
-        }
+        const bool hit = leaf_points<NR, ZB, FULL>(P, mat, tape, len, file, lane, px, py, lz, T, pending, depth);
         if (hit) atomicMax((unsigned long long*)&S->zbuf[pix], ((unsigned long long)depth << 32) | (li + 1));
     }
 }
@@ -1472,6 +1480,23 @@ __global__ void __launch_bounds__(WAVE) k_leaves3d(FhRenderState* S) {
 // (<= 32 registers, small LDS so that many waves fit).
 // z_lo, z_hi: only hits of this slab (z_lo < depth <= z_hi) are this launch's - the leaf kernel of the slab behind may already
 // be running (its hits lie below z_lo and carry leaf numbers of the other slab context).
+// The gradient of one leaf's tape at the voxel above each lane's hit (every lane evaluates; the caller keeps the lanes the leaf owns)
+template <bool FULL>
+FH_DEV GR leaf_gradient(const AS4 FhRender& P, const Mat4& mat, ctape_t tape, uint32_t len, Regs<GR, WAVE> R, uint32_t px, uint32_t py, uint32_t depth) {
+    GR gx, gy, gz, res = gr1(0.0f);
+    xf_grad(mat, gr((float)px, 1, 0, 0), gr((float)py, 0, 1, 0), gr((float)(depth - 1), 0, 0, 1), gx, gy, gz);
+    for (uint32_t q = 0; q < len; q++) {
+        const uint64_t w = tape[q];
+        step<GRAD, WAVE, FULL>(
+            w, R,
+            [&](uint32_t slot) {
+                const uint32_t kd = P.in_kind[slot];
+                return kd == 0 ? gx : (kd == 1 ? gy : (kd == 2 ? gz : gr1(P.in_value[slot])));
+            },
+            [&](uint32_t, GR v) { res = v; }, [&](int) {});
+    }
+    return res;
+}
 template <bool FULL, bool BIG>
 FH_DEV void normals3d_body(FhRenderState* S, uint32_t z_lo, uint32_t z_hi, char* file, uint32_t first, uint32_t stride) {
     const AS4 FhRender& P = *(const AS4 FhRender*)&S->P;
@@ -1505,18 +1530,7 @@ FH_DEV void normals3d_body(FhRenderState* S, uint32_t z_lo, uint32_t z_hi, char*
             const AS4 FhLeaf& lf = *(const AS4 FhLeaf*)&S->leaves[cur - 1];
             const ctape_t tape = (ctape_t)(S->arena + lf.tape.off);
             const uint32_t len = lf.tape.len;
-            GR gx, gy, gz, res = gr1(0.0f);
-            xf_grad(mat, gr((float)px, 1, 0, 0), gr((float)py, 0, 1, 0), gr((float)(depth - 1), 0, 0, 1), gx, gy, gz);
-            for (uint32_t q = 0; q < len; q++) {
-                const uint64_t w = tape[q];
-                step<GRAD, WAVE, FULL>(
-                    w, R,
-                    [&](uint32_t slot) {
-                        const uint32_t kd = P.in_kind[slot];
-                        return kd == 0 ? gx : (kd == 1 ? gy : (kd == 2 ? gz : gr1(P.in_value[slot])));
-                    },
-                    [&](uint32_t, GR v) { res = v; }, [&](int) {});
-            }
+            const GR res = leaf_gradient<FULL>(P, mat, tape, len, R, px, py, depth);
             if (mine) {
                 S->normals[pix * 3 + 0] = res.dx; S->normals[pix * 3 + 1] = res.dy; S->normals[pix * 3 + 2] = res.dz;
                 S->zbuf[pix] = zb & 0xFFFFFFFF00000000ull;  // normal done
@@ -1530,6 +1544,50 @@ template <bool FULL, bool BIG>
 __global__ void __launch_bounds__(WAVE) k_normals3d(FhRenderState* S, uint32_t z_lo, uint32_t z_hi) {
     extern __shared__ __attribute__((aligned(16))) char smem[];
     normals3d_body<FULL, BIG>(S, z_lo, z_hi, BIG ? big_file(S, smem) : smem, blockIdx.x, gridDim.x);
+}
+
+// Rare mode of a frame whose leaf stage goes by the list of leaves (capi_render.hpp, frame_schedule.hpp rare_leaves): the slab's leaves beyond
+// the leaf kernel's register file - none, nearly always: a wave leaves after one uniform load - get their points AND the normals of their
+// hits from one launch of one-wave blocks, block b the leaves b, b + gridDim.x, .. of `leaves` (the list that drives these blocks; fp_list[2],
+// which the push also fills in such a frame, is k_hits3d's and not read here).  In such a frame a pixel column has at most one leaf per slab,
+// the fills of the slab were written by the push before and slabs behind cannot replace a hit: the word the leaf's own atomic max leaves in
+// the z-buffer is final, and where the leaf owns it the gradient follows in the same wave - what the rare-only blocks of k_classify3d
+// (leaves3d_body<2>) and then of k_hits3d (normals3d_body<true, true>) did in two launches, with the same register file and the same
+// z_lo / z_hi test.
+__global__ void __launch_bounds__(WAVE) k_rare_leaves3d(FhRenderState* S, uint32_t z_lo, uint32_t z_hi, char* rare_file, uint32_t rare_stride) {
+    if (S->n_leaves_lds == 0) return;
+    const AS4 FhRender& P = *(const AS4 FhRender*)&S->P;
+    const int lane = threadIdx.x & (WAVE - 1);
+    const uint32_t T = P.tiles[P.n_levels - 1];
+    char* const file = rare_file + (size_t)blockIdx.x * rare_stride;
+    Mat4 mat;
+#pragma unroll
+    for (int i = 0; i < 16; i++) mat.m[i] = P.mat[i];
+    const uint32_t n_leaves = min(S->n_leaves, S->leaf_cap);
+    for (uint32_t li = blockIdx.x; li < n_leaves; li += gridDim.x) {
+        const AS4 FhLeaf& lf = *(const AS4 FhLeaf*)&S->leaves[li];
+        if (lf.tape.n_regs <= S->leaf_asm_regs) continue;
+        const uint32_t px = lf.x + (lane % T), py = lf.y + (lane / T), lz = lf.z;
+        const bool inimg = px < P.width && py < P.height;
+        const size_t pix = (size_t)py * P.width + px;
+        uint32_t depth = inimg ? (uint32_t)(S->zbuf[pix] >> 32) : 0xFFFFFFFFu;
+        const bool pending = depth < lz + T;
+        if (ballot(pending) == 0) continue;
+        const ctape_t tape = (ctape_t)(S->arena + lf.tape.off);
+        const uint32_t len = lf.tape.len;
+        const bool hit = leaf_points<0, 1, true>(P, mat, tape, len, file, lane, px, py, lz, T, pending, depth);
+        bool mine = false;      // the hit is the pixel's (nothing was in front of it) and of this slab's depth range
+        if (hit) {
+            const unsigned long long w = ((unsigned long long)depth << 32) | (li + 1);
+            mine = atomicMax((unsigned long long*)&S->zbuf[pix], w) < w && depth > z_lo && depth <= z_hi;
+        }
+        if (ballot(mine) == 0) continue;
+        const GR res = leaf_gradient<true>(P, mat, tape, len, Regs<GR, WAVE>{(GR*)file, lane}, px, py, depth);
+        if (mine) {
+            S->normals[pix * 3 + 0] = res.dx; S->normals[pix * 3 + 1] = res.dy; S->normals[pix * 3 + 2] = res.dz;
+            S->zbuf[pix] = (uint64_t)depth << 32;  // normal done
+        }
+    }
 }
 
 // The work list of the assembly normals kernel (fh_normals, gen_normals.py): every leaf that owns a hit of this slab's depth range in the

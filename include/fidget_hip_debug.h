@@ -31,6 +31,8 @@ uint64_t fhip_debug_lane_frames(const fhip_ctx* ctx);
 /* 3D frames of this context (its lanes included) rendered in rare mode so far: the launches that exist for tapes beyond the assembly kernels'
  * register files folded into launches the slab makes anyway - taken while the last finished frame met no such tape */
 uint64_t fhip_debug_rare_frames(const fhip_ctx* ctx);
+/* ... and how many launches its frames whose leaf stage goes by the list of leaves made for nothing but rare mode's blocks (one per slab) */
+uint64_t fhip_debug_rare_launches(const fhip_ctx* ctx);
 /* the arrangement tuner's state for the kind of 3D frame (tape, image size) queued last: returns its phase (0 / 1 / 2 measuring the stage pipeline,
  * the lanes, the stage pipeline again; 3 waiting for the last window's end; 4 decided; -1 none); ms[0 .. 2] = ms per frame of the three windows,
  * *lanes = the decision */
