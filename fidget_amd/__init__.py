@@ -30,6 +30,6 @@ from .render import (apply_shading, blur_ssao, compute_ssao, denoise_normals, me
                      to_debug_bitmap, to_rgba_bitmap, to_rgba_distance)
 from .mesher import MESH_LEAF, Mesh, Occupancy, OccupancyStruct, build_mesh, debug_walk_dual, mesh, mesh_merge, mesh_part, mesh_sample, occupancy
 from .voxels import Components, DistanceField, Nesting, Outlines, Surface, ThicknessField, Voxels, voxelize, voxels_unpack
-from .trimesh import EDGE_KINDS, MESH_INFO, SLICES_COUNTS, TOPOLOGY_COUNTS, MeshSlices, Topology, mesh_slices, mesh_topology, read_stl, voxelize_mesh
+from .trimesh import EDGE_KINDS, MESH_INFO, SLICES_COUNTS, SLICE_NESTING_PLANES, TOPOLOGY_COUNTS, MeshSlices, SliceNesting, Topology, mesh_slices, mesh_topology, read_stl, voxelize_mesh
 from .contours import Contours, contour, contour_loops, slice_stack
 from .solver import SOLVE_EXITS, SOLVE_MAX_FREE, Fixed, Free, solve, solve_batch, solve_key

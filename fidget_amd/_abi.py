@@ -208,6 +208,14 @@ SIGNATURES = {
     "fhip_slices_loop_dev": (vp, [vp]),
     "fhip_slices_plane_dev": (vp, [vp]),
     "fhip_slices_free": (None, [vp]),
+    # ---- the nesting of those slices: polygons with holes per plane
+    "fhip_slices_nesting": (i32, [vp, vp, u32, vp]),
+    "fhip_slice_nesting_counts": (None, [vp, vp]),
+    "fhip_slice_nesting_planes": (i32, [vp, vp, vp, vp, vp, vp, vp, vp]),
+    "fhip_slice_nesting_loops": (i32, [vp, vp, vp, vp, vp]),
+    "fhip_slice_nesting_parent_dev": (vp, [vp]),
+    "fhip_slice_nesting_depth_dev": (vp, [vp]),
+    "fhip_slice_nesting_free": (None, [vp]),
     # ---- profiling
     "fhip_profile_enable": (None, [vp, i32]),
     "fhip_profile_read": (i32, [vp, vp, vp]),

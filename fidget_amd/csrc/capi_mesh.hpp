@@ -1379,3 +1379,5 @@ fhip_status fhip_mesh_vertex_grads(fhip_ctx* ctx, const fhip_tape* tape, const f
 #include "capi_nest.hpp"
 // the slices of a triangle mesh (fhip_topology_slices): after capi_topo.hpp, whose fhip_topology it cuts
 #include "capi_slice.hpp"
+// the nesting of those slices (fhip_slices_nesting): after capi_slice.hpp, whose fhip_slices it reads, and capi_nest.hpp
+#include "capi_slice_nest.hpp"

@@ -1265,3 +1265,5 @@ __global__ void __launch_bounds__(256) k_cc_extract(const uint64_t* __restrict__
 #include "nest.hip"
 // k_ms_*: the slices of a triangle mesh - crossings, segments, loops per plane (fhip_topology_slices) - its own file, after topo.hip
 #include "slice.hip"
+// k_sn_*: the nesting of those slices - bands, hits, parity, parents (fhip_slices_nesting) - its own file, after slice.hip
+#include "slice_nest.hip"

@@ -1,5 +1,5 @@
 """The triangle-mesh family - a mesh given as triangles back into the library: `read_stl`, `voxelize_mesh`, `mesh_topology` and its
-`Topology`, `mesh_slices` and its `MeshSlices`."""
+`Topology`, `mesh_slices` and its `MeshSlices`, whose `nesting()` gives a `SliceNesting`."""
 import ctypes as C
 import os
 
@@ -345,8 +345,128 @@ class MeshSlices:
         """... and `.plane` ("<i4")"""
         return self._device("plane", (self.counts["vertices"],), "<i4")
 
+    def nesting(self, bands=0):
+        """fhip_slices_nesting: which regular loop of a plane contains which, on the device from the arrays this call left there ->
+        SliceNesting: polygons with holes per plane.  `bands`: 0, or the number of y-bands of every plane's segment index (tests; no
+        result depends on it)."""
+        h = C.c_void_p()
+        self._hip.check(lib().fhip_slices_nesting(self._hip._h, self._owner.h, int(bands), C.byref(h)))
+        return SliceNesting(self, _Handle(h.value, lib().fhip_slice_nesting_free))
+
     def __repr__(self):
         return f"MeshSlices({', '.join(f'{k}={v}' for k, v in self.counts.items())})"
+
+
+SLICE_NESTING_PLANES = ("regular", "outer", "top", "max_depth", "improper", "misoriented")
+
+
+class SliceNesting:
+    """The containment tree of the regular loops of a `MeshSlices` (`MeshSlices.nesting()`), per plane; the definitions stand in
+    include/fidget_hip.h.  `.slices`; `.n_loops`, `.n_regular`, `.n_outer` (even depth), `.n_top` (no parent), `.max_depth`,
+    `.n_improper` (loops whose parent is not one level up: loops cross), `.n_misoriented` (orientation against depth); `.per_plane`:
+    {regular, outer, top, max_depth, improper, misoriented} uint64 [P], also as `.regular`, `.outer` ...; `.bands` uint32 [P] and
+    `.index` = {bands, entries, hits}: the segment index that was used.  Per loop, [n_loops] with `NONE` = 0xFFFFFFFF for none and for
+    irregular loops, copied when first asked for: `.parent`, `.depth`, `.n_children` uint32, `.region_area2` float64 - area2 of the
+    loop and of its children.  parent and depth also stay in device memory (`.parent_device()`, `.depth_device()`)."""
+    NONE = 0xFFFFFFFF
+
+    def __init__(self, slices, owner):
+        self.slices, self._owner, self._hip = slices, owner, slices._hip
+        c = np.zeros(16, np.uint64)
+        lib().fhip_slice_nesting_counts(owner.h, _p(c))
+        self.n_loops, self.n_regular, self.n_outer, self.n_top, self.max_depth, self.n_improper, self.n_misoriented, self.n_planes = (int(v) for v in c[:8])
+        self.index = {"bands": int(c[8]), "entries": int(c[9]), "hits": int(c[10])}
+        P = self.n_planes
+        self.per_plane = {k: np.zeros(P, np.uint64) for k in SLICE_NESTING_PLANES}
+        self.bands = np.zeros(P, np.uint32)
+        self._hip.check(lib().fhip_slice_nesting_planes(owner.h, *(_p(a) for a in self.per_plane.values()), _p(self.bands)))
+        self._loops = None
+        self._children = None
+
+    regular = property(lambda self: self.per_plane["regular"])
+    outer = property(lambda self: self.per_plane["outer"])
+    top = property(lambda self: self.per_plane["top"])
+    plane_max_depth = property(lambda self: self.per_plane["max_depth"])
+    improper = property(lambda self: self.per_plane["improper"])
+    misoriented = property(lambda self: self.per_plane["misoriented"])
+
+    def _table(self):
+        if self._loops is None:
+            n = self.n_loops
+            t = {key: np.zeros(n, np.float64 if key == "region_area2" else np.uint32) for key in ("parent", "depth", "n_children", "region_area2")}
+            self._hip.check(lib().fhip_slice_nesting_loops(self._owner.h, *(_p(a) for a in t.values())))
+            self._loops = t
+        return self._loops
+
+    parent = property(lambda self: self._table()["parent"])
+    depth = property(lambda self: self._table()["depth"])
+    n_children = property(lambda self: self._table()["n_children"])
+    region_area2 = property(lambda self: self._table()["region_area2"])
+
+    def children(self):
+        """fhip_nesting_children -> (child_start uint64 [n_loops + 1], children uint32): the children of loop l, ascending, are
+        children[child_start[l]:child_start[l + 1]]; loops without a parent are in no list"""
+        if self._children is None:
+            n = self.n_loops
+            start, kids = np.zeros(n + 1, np.uint64), np.zeros(n, np.uint32)
+            self._hip.check(lib().fhip_nesting_children(_p(self.parent), n, _p(start), _p(kids)))
+            self._children = (start, kids[:int(start[n])])
+        return self._children
+
+    def regions(self, p):
+        """plane p's polygons with holes as [(outer loop id, [hole ids])]: every regular loop of even depth of the plane, ascending,
+        with its children - even-odd filling; every regular loop of the plane is in exactly one region where no loops cross"""
+        start, kids = self.children()
+        depth = self.depth
+        return [(int(l), [int(c) for c in kids[int(start[l]):int(start[l + 1])]]) for l in self.slices.loops_of(p) if depth[l] != self.NONE and depth[l] % 2 == 0]
+
+    def _walk(self, l):
+        s = self.slices
+        m, v = int(s.loops["crossings"][l]), int(s.loops["leader"][l])
+        ids = np.zeros(m, np.int64)
+        for k in range(m):
+            ids[k] = v
+            v = int(s.next[v])
+        return s.xy[ids]
+
+    def polygons(self, p):
+        """the same regions as [(outer float32 [m, 2], [holes float32 [m, 2]])], each loop walked from its leader as
+        `MeshSlices.polygons(p)` walks it"""
+        return [(self._walk(l), [self._walk(c) for c in holes]) for l, holes in self.regions(p)]
+
+    def svg(self, p, path=None):
+        """Plane p as one <path fill-rule="evenodd"> per region, the outer boundary and its holes as its subpaths `M x y L x y ... Z`:
+        holes render empty and islands as regions of their own.  Coordinates and viewBox as in `MeshSlices.svg`.  Returns the text;
+        written to `path` when given."""
+        s = self.slices
+        ids = s.loops_of(p)
+        lo = s.loops["lo"][ids].min(axis=0) if len(ids) else np.array([-1.0, -1.0])
+        hi = s.loops["hi"][ids].max(axis=0) if len(ids) else np.array([1.0, 1.0])
+        sub = lambda q: "M " + " L ".join(f"{float(x):.9g} {-float(y):.9g}" for x, y in q) + " Z"          # noqa: E731
+        paths = "".join('<path fill-rule="evenodd" d="' + " ".join(sub(q) for q in [outer] + holes) + '"/>\n' for outer, holes in self.polygons(p))
+        text = (f'<svg xmlns="http://www.w3.org/2000/svg" viewBox="{float(lo[0]):.9g} {-float(hi[1]):.9g} {float(hi[0] - lo[0]):.9g} {float(hi[1] - lo[1]):.9g}">\n'
+                f'{paths}</svg>\n')
+        if path is not None:
+            with open(path, "w") as f:
+                f.write(text)
+        return text
+
+    def _device(self, what):
+        ptr = getattr(lib(), f"fhip_slice_nesting_{what}_dev")(self._owner.h)
+        return _DeviceArray(self._owner, ptr, (self.n_loops,), "<i4") if ptr else None
+
+    def parent_device(self):
+        """`.parent` where it is in device memory ([n_loops] "<i4": the bits of the uint32 ids, NONE as -1) as an object carrying
+        `__cuda_array_interface__` that keeps the result alive; None for an empty result"""
+        return self._device("parent")
+
+    def depth_device(self):
+        """... and `.depth` ("<i4")"""
+        return self._device("depth")
+
+    def __repr__(self):
+        return (f"SliceNesting(planes={self.n_planes}, loops={self.n_loops}, regular={self.n_regular}, outer={self.n_outer}, top={self.n_top}, "
+                f"max_depth={self.max_depth}, improper={self.n_improper}, misoriented={self.n_misoriented})")
 
 
 def mesh_slices(mesh, zs, weld=None, hip=None, table_log2=0):

@@ -829,6 +829,62 @@ const uint32_t* fhip_slices_loop_dev(const void* slices);
 const uint32_t* fhip_slices_plane_dev(const void* slices);
 void fhip_slices_free(void* slices);
 
+/* ---- the nesting of those slices: polygons with holes per plane ---------------------------------------------------
+ * (fhip_outlines_nesting's counterpart for a mesh's slices.  No bitmap lies under these loops: they are float32 polygons, and which
+ * contains which is decided by a ray cast from each loop's leader towards -x against the polygons themselves.  No counterpart in the
+ * reference; the definition below is the specification.)
+ * All of it is over one handle of fhip_topology_slices: its xy, plane, next and loop_of per crossing where they are in device memory,
+ * and its loops' table - leader, plane, crossings, irregular, area2.
+ * LOOPS THAT TAKE PART.  The regular loops: those without an irregular crossing, the closed polygons.  An irregular loop takes no
+ * part: parent = depth = 0xFFFFFFFF (NONE), n_children = 0, region_area2 = 0, and its segments are ignored.  The segments of a regular
+ * loop are v -> next[v] for each of its crossings v, one per crossing.
+ * A HIT.  Leader position q = xy[leader[l]], and a segment s -> d of another regular loop m != l of the same plane.  The segment is hit
+ * iff (1) it straddles q's row under the half-open rule (s.y <= q.y) != (d.y <= q.y), by float32 comparison - each vertex's y is
+ * compared once, so two segments that share a vertex on the row cannot both count or both miss where the loop passes through the row
+ * - and (2) its crossing of the row lies strictly left of q, decided by the sign of
+ * c = (d.x - s.x) * (q.y - s.y) - (q.x - s.x) * (d.y - s.y), the float32 values converted to binary64, every operation rounded on its
+ * own, no contraction: hit iff c < 0 for an upward segment (s.y <= q.y), c > 0 for a downward one; c == 0 is not a hit.  This binary64
+ * sequence IS the definition.  It is not exact for arbitrary float32 input - the differences may round - so a leader within rounding
+ * of another loop's boundary may fall either side, but always the same side: the result is a function of the six floats alone.
+ * CONTAINMENT AND DEPTH.  m contains l iff the number of hit segments of m is odd.  depth[l] is the number of loops that contain l.
+ * PARENT.  parent[l] is the containing loop with the largest depth, the smallest id among equals; NONE if there is none.  For loops that
+ * do not cross each other the containing loops form a chain and depth[parent[l]] == depth[l] - 1; `improper` counts the loops with a
+ * parent where that equation fails, so a caller learns that loops cross without testing it.
+ * MISORIENTED.  The regular loops whose orientation disagrees with their depth: (depth even) != (area2 > 0).  A shell turned inside out
+ * shows up here.  This is the one integer that inherits area2's order of arrival, and only for loops of area near zero.
+ * CHILDREN AND REGIONS.  n_children[l]: the loops whose parent is l.  region_area2[l] (float64): area2[l] plus its children's area2,
+ * added in ascending child id - deterministic given area2.  A region is a loop of even depth with its children: even-odd filling.
+ * PER PLANE.  regular; outer (even depth); top (no parent); max_depth; improper; misoriented - and the number of bands used.
+ * Everything but misoriented and region_area2 is the same bits from run to run; nothing depends on the order of arrival of atomics,
+ * on the number of bands, or on the order of the triangles beyond what the slices fix.
+ * THE PASSES.  The segments of every plane are indexed by bands of y.  band(y) = clamp(floor((y - y0) * scale), 0, nb - 1) in float32,
+ * each operation rounded on its own, NaN -> 0: monotone non-decreasing in y, which alone guarantees that a segment that straddles q's
+ * row is listed in band(q.y).  y0 and scale = nb / (y1 - y0) come from the y-extent of the plane's regular loops (lo, hi); an empty
+ * extent is one band.  CSR: a count pass - a lane per regular segment adds to each band from that of its lower to that of its upper
+ * end - a prefix sum, a fill pass; entries arrive in any order and no result depends on it.  `bands` == 0 is the host's rule: a plane
+ * gets one band per 32 regular segments, at least 1 and at most 2^20; if the count pass reports more than 4 entries per regular segment,
+ * every plane's number is halved and the count repeated, until it fits or all are 1.  `bands` != 0: that many for every plane, used as
+ * given.  2^32 - 1 bands, band entries or hits or more is FHIP_ERR_OVERFLOW.  Then a wave per leader: its lanes stride over the entries
+ * of the leader's band and apply the predicate; hits are counted, prefix-summed over the leaders, and written - the hit loop's id per
+ * hit - at places from ballot and popcount, no atomics: a list of at most 512 stays in the wave's LDS, a longer one goes to global memory.
+ * The ids of odd multiplicity of a leader's list are its containing loops (any length: nothing of fixed size is overrun), their number
+ * its depth; after all depths, the parent and the integer sums.  A band's entry is the segment itself, 20 bytes, read in order.  No kernel waits for another workgroup,
+ * nothing spins, and every loop is bounded by the arrays' sizes.  The scratch stays with the context, as for the slices.
+ * The call blocks.  Refused before any launch: no context, slices or result (FHIP_ERR_BAD_TAPE), slices of another device's context
+ * (FHIP_ERR_UNSUPPORTED).  Zero planes, zero loops, or irregular loops alone give FHIP_OK, an empty result and no device arrays.
+ * counts = {loops, regular, outer, top, max depth, improper, misoriented, planes, bands, band entries, hits, 0 ..}.
+ * fhip_slice_nesting_planes: the six counts (uint64) and the bands per plane; fhip_slice_nesting_loops: a row per loop; any output
+ * pointer may be NULL.  parent and depth stay in device memory with the handle (the _dev getters; NULL for an empty result).  Children
+ * lists: fhip_nesting_children over `parent`. */
+fhip_status fhip_slices_nesting(fhip_ctx* ctx, const void* slices, uint32_t bands, void** out);
+void fhip_slice_nesting_counts(const void* nest, uint64_t out[16]);
+fhip_status fhip_slice_nesting_planes(const void* nest, uint64_t* regular, uint64_t* outer, uint64_t* top, uint64_t* max_depth, uint64_t* improper,
+                                      uint64_t* misoriented, uint32_t* bands);
+fhip_status fhip_slice_nesting_loops(const void* nest, uint32_t* parent, uint32_t* depth, uint32_t* n_children, double* region_area2);
+const uint32_t* fhip_slice_nesting_parent_dev(const void* nest);
+const uint32_t* fhip_slice_nesting_depth_dev(const void* nest);
+void fhip_slice_nesting_free(void* nest);
+
 /* ---- profiling ----------------------------------------------------------------------- */
 /* When enabled, every kernel launch of a render is bracketed by HIP events on the context's
  * stream; fhip_profile_read returns per-kernel-class totals of the last render. */

@@ -222,6 +222,15 @@ extern "C" {
     pub fn fhip_slices_loop_dev(slices: *const c_void) -> *const u32;
     pub fn fhip_slices_plane_dev(slices: *const c_void) -> *const u32;
     pub fn fhip_slices_free(slices: *mut c_void);
+    // the nesting of those slices: per regular loop its parent, depth, children and region sum; children lists by fhip_nesting_children
+    pub fn fhip_slices_nesting(ctx: *mut fhip_ctx, slices: *const c_void, bands: u32, out: *mut *mut c_void) -> fhip_status;
+    pub fn fhip_slice_nesting_counts(nest: *const c_void, out: *mut u64);
+    pub fn fhip_slice_nesting_planes(nest: *const c_void, regular: *mut u64, outer: *mut u64, top: *mut u64, max_depth: *mut u64, improper: *mut u64,
+                                     misoriented: *mut u64, bands: *mut u32) -> fhip_status;
+    pub fn fhip_slice_nesting_loops(nest: *const c_void, parent: *mut u32, depth: *mut u32, n_children: *mut u32, region_area2: *mut f64) -> fhip_status;
+    pub fn fhip_slice_nesting_parent_dev(nest: *const c_void) -> *const u32;
+    pub fn fhip_slice_nesting_depth_dev(nest: *const c_void) -> *const u32;
+    pub fn fhip_slice_nesting_free(nest: *mut c_void);
     // the build sharded by the root's octants (Octree::build_inner_mt across GPUs): a part per process, merged in one
     pub fn fhip_mesh_sample_part(ctx: *mut fhip_ctx, tape: *const fhip_tape, depth: u32, world_to_model: *const f32, axis_slots: *const i32,
                                  var_keys: *const u64, var_values: *const f32, n_vars: u32, part: u32, n_parts: u32,

@@ -7,7 +7,7 @@ the list of the other fragments, one capi_X.hpp per subject, at its end - and me
 (tests/test_mesh_fragments.py).  A change there cannot alter a render kernel or how a frame is launched."""
 import glob, hashlib, os
 ROOT = os.path.dirname(os.path.dirname(os.path.abspath(__file__)))
-MESH_ONLY = ("mesh.hip", "mesh_collapse.hpp", "mesh_qef.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "capi_mesh.hpp", "capi_mesh_util.hpp", "capi_voxels.hpp", "capi_contour.hpp", "capi_cc.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "mesh_nest.hpp", "nest.hip", "capi_nest.hpp", "mesh_slice.hpp", "slice.hip", "capi_slice.hpp")
+MESH_ONLY = ("mesh.hip", "mesh_collapse.hpp", "mesh_qef.hpp", "mesh_edges.hpp", "mesh_walk.hpp", "host_mesh.hpp", "capi_mesh.hpp", "capi_mesh_util.hpp", "capi_voxels.hpp", "capi_contour.hpp", "capi_cc.hpp", "mesh_split.hpp", "mesh_vox.hpp", "mesh_cc.hpp", "mesh_edt.hpp", "edt.hip", "capi_edt.hpp", "mesh_thick.hpp", "thick.hip", "capi_thick.hpp", "mesh_vmesh.hpp", "vmesh.hip", "capi_vmesh.hpp", "mesh_flow.hpp", "flow.hip", "capi_flow.hpp", "mesh_trivox.hpp", "trivox.hip", "capi_trivox.hpp", "mesh_topo.hpp", "topo.hip", "capi_topo.hpp", "mesh_outline.hpp", "outline.hip", "capi_outline.hpp", "mesh_nest.hpp", "nest.hip", "capi_nest.hpp", "mesh_slice.hpp", "slice.hip", "capi_slice.hpp", "mesh_slice_nest.hpp", "slice_nest.hip", "capi_slice_nest.hpp")
 
 
 def source_hash(root=ROOT):
