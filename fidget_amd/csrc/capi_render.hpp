@@ -643,6 +643,13 @@ static void leaf_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& 
         }
     });
 }
+// Rare mode of a by-list frame (frame_schedule.hpp rare_leaves): the points of the leaves beyond the leaf kernel's file and the normals of their hits
+// in one launch, driven by the slab's leaves - behind the leaf kernel, whether the frame's normals kernels run or not
+static void rare_leaves_launch(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, int k, hipStream_t st) {
+    const uint32_t z_lo = (uint32_t)k * R.S.P.slab, z_hi = z_lo + R.S.P.slab;
+    ctx->rare_launches++;
+    FH_KLAUNCH(k_rare_leaves3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, rare_file(ctx, dS, F.rare_stride), F.rare_stride);
+}
 // The normals of slab k's hits
 static void normals_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedule& F, FhRenderState* dS, int k, hipStream_t st) {
     const uint32_t z_lo = (uint32_t)k * R.S.P.slab, z_hi = z_lo + R.S.P.slab;
@@ -652,8 +659,7 @@ static void normals_work(fhip_ctx* ctx, const RenderSetup& R, const FrameSchedul
         if (F.by_list) {
             // (the leaf that owns a pixel's hit is its column's leaf or nobody: fh_normals takes the slab's leaves one per wave pass and
             // looks at the z-buffer itself; k_hits3d: rare mode's blocks for the footprints the push put on list 2)
-            // (rare_leaves: the points of the leaves beyond the leaf kernel's file and the normals of their hits in one launch, driven by the slab's leaves)
-            if (F.rare_leaves) { ctx->rare_launches++; FH_KLAUNCH(k_rare_leaves3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, rare_file(ctx, dS, F.rare_stride), F.rare_stride); }
+            if (F.rare_leaves) rare_leaves_launch(ctx, R, F, dS, k, st);
             else if (F.rare && R.S.P.max_regs > R.S.norm_asm_regs) {
                 ctx->rare_launches++;
                 FH_KLAUNCH(k_hits3d, dim3(FH_RARE_BLOCKS), dim3(WAVE), 0, st, dS, z_lo, z_hi, R.hit_bucket_cap, 0u, rare_file(ctx, dS, F.rare_stride), F.rare_stride);
@@ -746,6 +752,7 @@ static fhip_status render_slabs(fhip_ctx* ctx, const RenderSetup& R, const Frame
         leaf_work(ctx, R, F, dS, (uint32_t)(dS - dS0), fs.s[F.leaf]);
         if (F.aux_edge) { HIP_TRY(ctx, hipEventRecord(ctx->ev_aux[idx], fs.s[F.leaf])); HIP_TRY(ctx, hipStreamWaitEvent(fs.s[F.normals], ctx->ev_aux[idx], 0)); }     // the slab's leaf kernel is through
         if (F.normals_on) normals_work(ctx, R, F, dS, k, fs.s[F.normals]);
+        else if (F.rare_leaves) launch(ctx, fs.s[F.normals], FHIP_K_NORMALS, [&] { rare_leaves_launch(ctx, R, F, dS, k, fs.s[F.normals]); });      // (a frame without normals: the large leaves' points all the same)
         if (records_leaves(F, idx)) HIP_TRY(ctx, hipEventRecord(ctx->ev_leaves[idx], fs.s[F.normals]));       // slab context free again for slab idx + NC; the last one of an aux_edge frame: image complete
     }
     // (the tail stream is serial: the last slab's normals)

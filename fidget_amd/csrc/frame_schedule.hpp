@@ -72,7 +72,7 @@ struct FrameSchedule {
     bool by_list = false, by_columns = false; uint32_t g = 0;      // the leaf kernel's walk; group of 2^g layers
     bool rare_leaves = false;    // rare mode of a by_list frame: ONE launch (k_rare_leaves3d) for the points and the normals of the leaves beyond the leaf kernel's file
     uint32_t list_waves = 0, table_words = 0; int reset_blocks = 1;
-    bool normals_on = true;      // (FH_EXP_SKIP_NORMALS)
+    bool normals_on = true;      // the slabs' normals kernels run: not in a whole front-slab-only frame, whose hits are all clamped (below; FH_EXP_SKIP_NORMALS)
     LevelPlan level[FH_MAX_LEVELS];
 };
 
@@ -266,6 +266,15 @@ static FrameSchedule schedule_frame(const RenderSetup& R, const ScheduleInputs& 
     F.g = F.by_columns ? 6u : (R.smooth_tape && g_opt > 1 ? g_opt - 1 : g_opt);
     F.leaf_walk = !R.asm_points ? FrameSchedule::HIP_LEAVES : F.by_list ? FrameSchedule::BY_LIST
                 : ((F.by_columns && layers <= 64) || (!F.by_columns && F.g > 0)) ? FrameSchedule::BY_COLUMNS : FrameSchedule::BY_BLOCKS;
+    // The normals of a WHOLE front-slab-only frame were computed and thrown away.  No tape of such a frame reads anything that changes along
+    // a pixel column, so a pixel that is inside is inside at every z: its hit is the top voxel of the top leaf layer of the volume, its depth
+    // >= the image's depth, and k_finish3d writes (0, 0, 1, depth) for every pixel of depth >= depth - 1 whatever its normal (the reference's
+    // clamp: voxel.rs:533-539) - fh_normals evaluated a gradient for every hit of the slab, 25 us of the caller's stream and a launch, and
+    // nothing read it.  The frame makes no normals launch; its hits keep their leaf's number in the z-buffer word, which k_finish3d does not
+    // look at.  What stays is k_rare_leaves3d where the frame has it: the POINTS of the leaves beyond the leaf kernel's file are that
+    // launch's (its gradients follow in the same wave and are clamped like the others).  A part of a frame (shard, block: `whole` false)
+    // keeps its normals - a back z-block's hits lie below the volume's top -, and so does every frame with z in a tape.
+    F.normals_on = !(R.front_only && in.whole);
 #ifdef FH_EXP_SKIP_NORMALS      // experiment (tools/build_lib_variant.py): a frame without its normals kernels - what they cost beside the leaf kernels
     F.normals_on = false;
 #endif
